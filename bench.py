@@ -1,6 +1,7 @@
 """Headline benchmark: image-text pairs/sec of the CLIP ViT-B/32 contrastive step on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--mode train|fwd|image|caption] [--batch 1024] [--dtype bf16|fp16|fp8]
+                    [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): CLIP/train.py's step `model(image, text)` -> symmetric CE ->
 backward -> AdamW, scaled to bs = 1024 pairs per GPU, synthetic 224x224 N(0,1) images + 77-token captions
@@ -13,7 +14,13 @@ Those are extras with their own metric names; the default line is always the tra
 N > 1: one process per GPU (torchrun contract), weak scaling (per-GPU batch fixed), embedding
 all-gather + reduce-scatter and SUM all-reduce of the flat gradient arena over RCCL.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (metric / value / unit / higher_is_better /
+dtype / ms_per_step = wall-clock milliseconds per timed step); nothing else is measured.  `--dump-outputs DIR` writes
+what the last timed step computed (features, loss; in train / caption mode a fixed seeded sample of the updated fp32
+parameters and of the gradients) as DIR/<name>.npy in float32: the inputs are seeded, so two builds can be compared.
+`--full` adds everything below, measured after the headline steps.
+
+With --full, rank 0's line carries two extra objects:
   roofline     - dominant kernel family cclip_gemm_bf16 = gemm_bf16_kernel<*> / gemm_a4*_kernel / gemm_stream_kernel<*> (97 % of the step's
                  FLOPs, ~78 % of its time): algorithmic FLOPs of
                  every launch in the timed region (2*M*N*K) / their summed durations (HIP events on the launch
@@ -22,7 +29,7 @@ Rank 0 prints ONE JSON line (contract in the task statement) with two extra obje
                  on the host cores, SURVEY.md 8d's procedure (bs 64, 3 warm-up + 5 timed, median): the train step and,
                  beside it, the forward-only encode+logits figure.
 The text tower runs on PACKED rows by default (each caption's positions 0..EOT; `config.text_rows`) and the last block of each tower on its pooled rows; the `all_rows` leg times the same step with both switched off.
-and, in the default (train, one GPU) run, extra objects timed after the headline steps: `encode_image`
+and, in a --full train run on one GPU, extra objects timed after the headline steps: `encode_image`
 (images/s + fraction of the bf16 MFMA peak - BASELINE.md's 40 % target), `encode_image_fp8` (the same with the block
 projections in e4m3: BASELINE configs[4]'s path on the headline model), `forward_only`, `parity_mode` (the same step
 with fp16 operands).  `roofline.traffic` / `mfma_busy` are REPLAYED from committed rocprofv3 --pmc summaries and only
@@ -229,15 +236,21 @@ def caption_main(args, rank, world, dev, B, cdt):
         tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
-    nprof = min(2, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(loss=loss.detach().reshape(1), **arena_outputs(model.arena)))
+    roof = None
+    if args.full:                    # roofline leg: the same step again with every GEMM launch bracketed by HIP events
+        nprof = min(2, args.steps)
+        if rank == 0:
+            ops.GEMM_EVENTS = []
+        os.environ["CCLIP_WGRAD_STREAM"] = "0"
+        for _ in range(nprof):
+            step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            ev, ops.GEMM_EVENTS = ops.GEMM_EVENTS, None
+            roof = gemm_roofline(ev, nprof)
     if rank == 0:
-        ops.GEMM_EVENTS = []
-    os.environ["CCLIP_WGRAD_STREAM"] = "0"
-    for _ in range(nprof):
-        step()
-    torch.cuda.synchronize()
-    if rank == 0:
-        ev, ops.GEMM_EVENTS = ops.GEMM_EVENTS, None
         S = geo.prefix_length + geo.attribute_length + Lc
         out = {"metric": f"caption samples/sec (ClipCaptionModel train step: MLP mapper + GPT-2-small, bs={B})",
                "value": round(B * world * args.steps / dt, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
@@ -248,15 +261,15 @@ def caption_main(args, rank, world, dev, B, cdt):
                           "global_batch": B * world, "parallelism": f"dp{world}", "mode": "caption"},
                "not_executed_flops_view": {"frac_of_bf16_peak": {"step": round(3 * CAPTION_FWD_FLOPS * B * world / (dt / args.steps) / (PEAK_BF16 * world), 4)},
                                            "note": "nominal FLOPs (every row of every sequence), although the packed step does not compute them all"},
-               "loss": round(float(loss.item()), 5), "roofline": gemm_roofline(ev, nprof), "cpu_baseline": None}
-        roof = out["roofline"]
-        out["step_mfu_bf16"] = round(roof["flops_per_launch"] * roof["launches_per_step"] / (dt / args.steps) / PEAK_BF16, 4)   # executed GEMM FLOPs
+               "loss": round(float(loss.item()), 5), "roofline": roof, "cpu_baseline": None}
+        out["step_mfu_bf16"] = (round(roof["flops_per_launch"] * roof["launches_per_step"] / (dt / args.steps) / PEAK_BF16, 4)   # executed GEMM FLOPs
+                                if roof else None)
         lens = ((tokens != 0) * torch.arange(1, Lc + 1, device=dev)[None, :]).amax(dim=1)
         out["config"]["rows"] = {"rows_dense": B * S, "rows_live": int((S - Lc + lens - 1).clamp(min=1).sum().item()), "packed": model._pack_rows(),
                                  "note": "GPT-2 is causal and the loss ignores zero targets (train.py:357): of a sequence only the rows up to the one "
                                          "that predicts its last non-zero token matter; caption_loss runs the stack on those rows, sequences back "
                                          "to back (CCLIP_PACK_TEXT=0: all P + A + L rows)"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = caption_cpu_baseline(geo, Lc)
         print(json.dumps(out))
     if world > 1:
@@ -392,6 +405,34 @@ def extra_legs(model, image, text, geo, B, args):
     return out
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger output (params / grads arenas): fixed seed, sorted indices
+DUMP_LIMIT = 64 << 20
+
+
+def _sample(t: torch.Tensor, seed: int) -> torch.Tensor:
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= DUMP_SAMPLE:
+        return flat
+    idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def arena_outputs(arena) -> dict:
+    """what a train step leaves in the model: the fp32 master parameters after the optimiser and the step's gradients"""
+    return {"params_sample": _sample(arena.flat, 1), "grads_sample": _sample(arena.gflat, 2)}
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    log(f"dumped {', '.join(sorted(host))} ({total / 2**20:.1f} MB) to {out_dir}")
+
+
 def log(msg: str):
     print(f"[bench +{time.perf_counter() - _T0:7.1f}s] {msg}", file=sys.stderr, flush=True)
 
@@ -408,9 +449,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="pairs per GPU (default 1024; 256 for --mode caption)")
     ap.add_argument("--mode", choices=["train", "fwd", "image", "caption"], default="train")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the roofline leg, the extra legs (train mode, one GPU) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; large arrays as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="train mode: skip the extra encode_image / forward-only / fp16-operand legs timed after the headline steps")
+                    help="--full, train mode: skip the extra encode_image / forward-only / fp16-operand legs timed after the headline steps")
     ap.add_argument("--text-prefetch", action="store_true",
                     help="announce the next token batch one step ahead (model.prefetch_text) instead of reading the packed text tower's row count "
                          "back at the start of the step; measured SLOWER (51.6-51.7 vs 50.8 ms, DESIGN.md 6.0) and therefore off")
@@ -471,17 +516,22 @@ def main():
         turn[0] += 1
         return model.encode_image_text(image, t)
 
+    last = {}                        # the latest step's outputs (references only: --dump-outputs reads them after the timed steps)
+
     def step():
         if args.mode == "image":
             with torch.no_grad():
-                return [model.encode_image(image).float().sum()]
+                last["image_features"] = model.encode_image(image)
+                return [last["image_features"].float().sum()]
         if args.mode == "fwd":
             with torch.no_grad():
                 fi, ft = encode_both()
                 loss, stats = clip.contrastive_loss(fi, ft, model.logit_scale, group)
+            last.update(image_features=fi, text_features=ft)
             return stats
         opt.zero_grad()
         fi, ft = encode_both()
+        last.update(image_features=fi, text_features=ft)
         loss, stats = clip.contrastive_loss(fi, ft, model.logit_scale, group)
         reducer.begin()              # N > 1: gradient buckets are all-reduced from inside backward, block group by block group
         loss.backward()
@@ -512,38 +562,48 @@ def main():
         dt = tmax.item()
     loss_val = float(stats[0].item())
     log(f"timed {args.steps} steps in {dt:.3f}s")
+    if args.dump_outputs and rank == 0:
+        outs = dict(last)
+        if args.mode == "image":
+            outs["feature_sum"] = stats[0].reshape(1)
+        else:
+            outs.update(loss=stats[0:1], n_correct=stats[1:2])
+        if args.mode == "train":
+            outs.update(arena_outputs(model.arena))
+        dump_outputs(args.dump_outputs, outs)
 
-    # ---- roofline leg: same steps again with every GEMM launch bracketed by HIP events ----
+    # ---- roofline leg (--full): same steps again with every GEMM launch bracketed by HIP events ----
     roof = None
-    nprof = min(2, args.steps)
-    if rank == 0:
-        ops.GEMM_EVENTS = []
-    os.environ["CCLIP_TOWER_STREAMS"] = "1"   # kernel durations are measured with the launches serialised on one stream
-    os.environ["CCLIP_WGRAD_STREAM"] = "0"
-    prev_lanes = os.environ.get("CCLIP_IMAGE_LANES")
-    os.environ["CCLIP_IMAGE_LANES"] = "1"     # (inference encode_image otherwise runs two half-batch lanes on two streams)
-    for _ in range(nprof):          # every rank steps (the step contains collectives); only rank 0 records events
-        step()
-    torch.cuda.synchronize()
-    os.environ["CCLIP_TOWER_STREAMS"] = str(args.tower_streams)
-    if prev_lanes is None:
-        del os.environ["CCLIP_IMAGE_LANES"]
-    else:
-        os.environ["CCLIP_IMAGE_LANES"] = prev_lanes
-    if rank == 0:
-        ev = ops.GEMM_EVENTS
-        ops.GEMM_EVENTS = None
-        roof = gemm_roofline(ev, nprof, None, None)
-        attach_replayed_pmc(roof, args, B, world, ops.kernel_source_hash())
-    if world > 1:
-        dist.barrier()
+    if args.full:
+        nprof = min(2, args.steps)
+        if rank == 0:
+            ops.GEMM_EVENTS = []
+        os.environ["CCLIP_TOWER_STREAMS"] = "1"   # kernel durations are measured with the launches serialised on one stream
+        os.environ["CCLIP_WGRAD_STREAM"] = "0"
+        prev_lanes = os.environ.get("CCLIP_IMAGE_LANES")
+        os.environ["CCLIP_IMAGE_LANES"] = "1"     # (inference encode_image otherwise runs two half-batch lanes on two streams)
+        for _ in range(nprof):          # every rank steps (the step contains collectives); only rank 0 records events
+            step()
+        torch.cuda.synchronize()
+        os.environ["CCLIP_TOWER_STREAMS"] = str(args.tower_streams)
+        if prev_lanes is None:
+            del os.environ["CCLIP_IMAGE_LANES"]
+        else:
+            os.environ["CCLIP_IMAGE_LANES"] = prev_lanes
+        if rank == 0:
+            ev = ops.GEMM_EVENTS
+            ops.GEMM_EVENTS = None
+            roof = gemm_roofline(ev, nprof, None, None)
+            attach_replayed_pmc(roof, args, B, world, ops.kernel_source_hash())
+        if world > 1:
+            dist.barrier()
 
-    # ---- extra legs of the default run (one GPU, train mode): the figures BASELINE.md's targets are quoted on, timed in
-    # the driver's own run so that they are driver-observable: encode_image alone (the ">= 40 % of the bf16 MFMA roofline"
+    # ---- extra legs of a --full run (one GPU, train mode): the figures BASELINE.md's targets are quoted on, timed in
+    # the benchmark's own run: encode_image alone (the ">= 40 % of the bf16 MFMA roofline"
     # target), encode+logits forward only (the metric's own wording), and the same train step with fp16 operands (the
     # operand type that meets north_star's 1e-3 parity bar, tests/test_clip_parity_gpu.py) ----
     extras = None
-    if args.mode == "train" and world == 1 and not args.no_extras:
+    if args.full and args.mode == "train" and world == 1 and not args.no_extras:
         extras = extra_legs(model, image, text, geo, B, args)
         log("extra legs done")
 
@@ -570,8 +630,9 @@ def main():
         }
         # whole-step MFU from the GEMM FLOPs the step EXECUTES (the roofline leg's launches): with the text tower on packed rows
         # that is less than the dense-equivalent 3 x 14.78 GFLOP per pair, which is reported beside it and labelled as such
+        # (null without --full: only the roofline leg counts the executed FLOPs)
         exe = roof["flops_per_launch"] * roof["launches_per_step"] if roof else None
-        out["step_mfu_bf16"] = round((exe if exe else step_flops) / (dt / args.steps) / PEAK_BF16, 4)
+        out["step_mfu_bf16"] = round((exe if exe else step_flops) / (dt / args.steps) / PEAK_BF16, 4) if args.full else None
         nominal_step = round(step_flops / (dt / args.steps) / PEAK_BF16, 4)
         # the number BASELINE.json's target is about, inside the driver-parsed roofline object: encode_image ViT-B/32 bs 1024 as a
         # fraction of the bf16 MFMA peak on EXECUTED FLOPs (this run's own figure in --mode image; the extra leg's in train mode)
@@ -593,11 +654,12 @@ def main():
                         "row, so later positions influence neither features nor gradients" + (
                             " - it runs on the live rows only, sequences back to back (CCLIP_PACK_TEXT=0: all 77 positions)" if packed
                             else " - run on all 77 positions (CCLIP_PACK_TEXT=0)")}
-        log("roofline leg done")
+        if roof is not None:
+            log("roofline leg done")
         if extras is not None:
             out.update(extras)
         out.setdefault("not_executed_flops_view", {"frac_of_bf16_peak": {}})["frac_of_bf16_peak"]["step"] = nominal_step
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.mode)
             log("cpu baseline done")
         else:

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r2
 mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extras"
 # (gpurun MERGES gpurun_out/ back: drop an earlier call's files of the same pass first, the fold would mix them)
 kt() { rm -rf $O/$1; rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -- $2 > $O/$1.log 2>&1 || echo "FAILED $1"; }
 pmc() { rm -rf $O/$1; rocprofv3 --pmc $3 --output-format csv -d $O/$1 -- $2 > $O/$1.log 2>&1 || echo "FAILED $1"; }
@@ -29,7 +29,7 @@ pmc caption_mfma "$B --mode caption --steps 1 --warmup 1" "SQ_VALU_MFMA_BUSY_CYC
 fi
 if [ -z "$PROF_ONLY" ] || [ "$PROF_ONLY" = l14 ]; then
 # 4. BASELINE configs[4]: ViT-L/14@336px encode_image, bs 256, fp8 projections
-L="python3 $R/bench.py --no-cpu-baseline --mode image --model ViT-L/14@336px --batch 256 --dtype fp8"
+L="python3 $R/bench.py --full --no-cpu-baseline --mode image --model ViT-L/14@336px --batch 256 --dtype fp8"
 kt l14_fp8 "$L --steps 4 --warmup 2"
 pmc l14_fp8_fetch "$L --steps 1 --warmup 1" FETCH_SIZE
 pmc l14_fp8_write "$L --steps 1 --warmup 1" WRITE_SIZE

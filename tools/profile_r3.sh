@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_r3_${PROF_TAG:-final}
 mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-extras --mode image"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extras --mode image"
 kt() { rm -rf $O/$1; rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -- $2 > $O/$1.log 2>&1 || echo "FAILED $1"; }
 pmc() { rm -rf $O/$1; rocprofv3 --pmc $3 --output-format csv -d $O/$1 -- $2 > $O/$1.log 2>&1 || echo "FAILED $1"; }
 # 1. kernel trace: two half-batch lanes (the default; kernels of the two lanes overlap, durations inflated by co-residency)

@@ -2,6 +2,8 @@
 set -e
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_default -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline > $R/gpurun_out/prof_default.log 2>&1
+O=${OUT:-$R/tool_out}      # output folder (absolute)
+mkdir -p "$O"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O"/prof_default -- python3 "$R"/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline > "$O"/prof_default.log 2>&1
 export CCLIP_WGRAD_STREAM=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_single -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --tower-streams 1 > $R/gpurun_out/prof_single.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$O"/prof_single -- python3 "$R"/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --tower-streams 1 > "$O"/prof_single.log 2>&1
