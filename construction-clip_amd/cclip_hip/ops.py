@@ -229,9 +229,27 @@ def _nearest_tuned(key: str, unbounded: bool = False):
     cfg |= order
     if tok == 3 and sp > 1:
         sp = max(1, min(sp, round(sp * want / toks[best])))
-    if tok == 3 and cfg == 11 and (want % 64 or want // 64 < 2 * sp):
-        cfg = 2               # the hand-scheduled weight-gradient kernel needs whole 64-token K-tiles, >= 2 per split
+    if tok == 3 and cfg == 11:
+        # the hand-scheduled weight-gradient kernel needs whole 64-token K-tiles, >= 2 in every split, the last one included:
+        # fewer splits until the dispatcher's split arithmetic allows that, the 8-wave kernel when no split count does
+        if want % 64 == 0:
+            while sp > 1 and not cfg11_splits_ok(want // 64, sp):
+                sp -= 1
+        if want % 64 or not cfg11_splits_ok(want // 64, sp):
+            cfg = 2
     return (cfg, sp)
+
+
+def cfg11_splits_ok(nkt: int, split_k: int) -> bool:
+    """The split arithmetic of the GEMM dispatcher (csrc/gemm_bf16.hip) and the test of configuration 11's launcher
+    (csrc/gemm_bf16_cfg11.hip, cclip_gemm_launch_cfg11): with nkt 64-deep K-tiles and split_k requested splits, every split -
+    the last, shorter one included - must hold at least two K-tiles, or the launch is refused."""
+    splits = min(max(split_k, 1), nkt)
+    if splits < 1:
+        return False
+    ktps = -(-nkt // splits)
+    splits = -(-nkt // ktps)
+    return ktps >= 2 and nkt - (splits - 1) * ktps >= 2
 
 
 def load_tuned_table(path=None, force: bool = False) -> int:

@@ -231,6 +231,76 @@ def test_gemm_tile_lookup_takes_the_nearest_token_count(monkeypatch):
         ops._DERIVED.clear(); ops._DERIVED.update(saved_d)
 
 
+def _cfg11_launches(nkt, split_k):
+    """Restated from the C side, not imported: csrc/gemm_bf16.hip (CCLIP_GEMM_FN) clamps the split count to nkt, takes
+    ktiles_per_split = ceil(nkt / splits) and then splits = ceil(nkt / ktiles_per_split) (no empty split);
+    csrc/gemm_bf16_cfg11.hip (cclip_gemm_launch_cfg11) computes last = nkt - (splits - 1) * ktiles_per_split and refuses the
+    launch when ktiles_per_split < 2 or last < 2."""
+    splits = min(max(split_k, 1), nkt)
+    ktps = (nkt + splits - 1) // splits
+    splits = (nkt + ktps - 1) // ktps
+    last = nkt - (splits - 1) * ktps
+    return ktps >= 2 and last >= 2
+
+
+def test_derived_cfg11_choices_are_launchable_for_every_token_count():
+    """Every configuration-11 entry of the committed gemm_tune.json (both dtypes): at every 64-multiple token count up to 16x the
+    entry, the choice _nearest_tuned derives is one the dispatcher launches (a refused launch raises in the middle of a step;
+    e.g. 56384 tokens on the 512x512 text weight gradient once gave split 46 with a one-K-tile last split).  Configuration 11 is
+    kept whenever some split count is launchable, and the split is never raised above the scaled one."""
+    import json
+    from cclip_hip import ops
+    path = os.path.join(os.path.dirname(ops.__file__), "gemm_tune.json")
+    with open(path) as f:
+        table = {k: tuple(v) for k, v in json.load(f)["table"].items()}
+    c11 = [k for k, v in table.items() if v[0] & 255 == 11]
+    assert {k.split("|")[0] for k in c11} == {"bfloat16", "float16"}
+    saved, saved_d = dict(ops._TUNED), dict(ops._DERIVED)
+    try:
+        ops._TUNED.clear(); ops._DERIVED.clear()
+        ops._TUNED.update(table)
+        def family(k):
+            f = k.split("|")
+            return "|".join(f[:3] + f[4:])
+        all11 = {family(k) for k in c11} - {family(k) for k, v in table.items() if v[0] & 255 != 11}
+        bad, dropped, kept = [], [], 0
+        for key in c11:
+            f = key.split("|")
+            for want in range(64, 16 * int(f[3]) + 1, 64):
+                q = "|".join(f[:3] + [str(want)] + f[4:])
+                choice = ops._nearest_tuned(q)
+                if choice is None:
+                    continue
+                if choice[0] & 255 != 11:
+                    # in a family of configuration-11 entries only, the 8-wave fallback is for counts no split count launches
+                    if family(key) in all11 and _cfg11_launches(want // 64, 1):
+                        dropped.append((q, choice))
+                    continue
+                kept += 1
+                if not _cfg11_launches(want // 64, choice[1]):
+                    bad.append((q, choice))
+        assert not bad, f"{len(bad)} derived configuration-11 choices the dispatcher refuses, e.g. {bad[:4]}"
+        assert not dropped, f"{len(dropped)} counts fell back to configuration 2 although configuration 11 launches, e.g. {dropped[:4]}"
+        assert kept > 100000
+        # the reproduced counts: 512x512 text-tower weight gradient (table entry 78848 tokens, split 64)
+        for dt in ("bfloat16", "float16"):
+            for want in (56384, 57664, 58944, 60224):
+                cfg, sp = ops._nearest_tuned(f"{dt}|512|512|{want}|0|0|0|1|0|0|0|0|-1|1|0")
+                assert cfg == 11 and _cfg11_launches(want // 64, sp) and sp <= round(64 * want / 78848), (want, cfg, sp)
+    finally:
+        ops._TUNED.clear(); ops._TUNED.update(saved)
+        ops._DERIVED.clear(); ops._DERIVED.update(saved_d)
+
+
+def test_cfg11_split_predicate_matches_the_dispatcher_restatement():
+    """ops.cfg11_splits_ok (what _nearest_tuned applies) == the restatement above, over every (K-tiles, split) pair up to 200."""
+    from cclip_hip import ops
+    for nkt in range(1, 201):
+        for sp in range(1, 201):
+            assert ops.cfg11_splits_ok(nkt, sp) == _cfg11_launches(nkt, sp), (nkt, sp)
+    assert ops.cfg11_splits_ok(10, 5) and not ops.cfg11_splits_ok(881, 46) and not ops.cfg11_splits_ok(1, 1)
+
+
 def test_gemm_tile_lookup_stays_flat_over_many_row_counts():
     """A run that meets a new packed row count every step (shuffled captions) must not grow the tuned table nor slow its lookups
     down: derived choices live in a bounded cache, the table holds timed / persisted entries only, and the nearest-token search is
