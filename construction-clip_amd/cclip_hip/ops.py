@@ -607,6 +607,25 @@ def attention_bwd(q, k, v, o, lse, dout, dq, dk, dv, *, B: int, T: int, H: int, 
     check(_fn("cclip_attention_bwd", q, k, v, o, dout, dq, dk, dv)(ctypes.byref(d), _stream()), "cclip_attention_bwd")
 
 
+def attention_relevance(q, k, v, lse, da, R, *, B: int, T: int, H: int, causal: bool = False, scale=None, cu=None,
+                        grad_scale: float = 1.0) -> None:
+    """One layer's attention relevance (Chefer et al.), T <= 128: C = 1/(H grad_scale) sum_h max(P_h * dP_h, 0) with
+    P = softmax(scale q k^T) (rebuilt from the forward's lse) and dP = da v^T, then R[b, :T_b, :T_b] += R[b, :T_b, :T_b] C.
+    q/k/v/da as for attention_bwd (da = the gradient at the attention output); lse fp32 [B, H, T]; R fp32 [B, T, T] contiguous,
+    updated in place (rows / columns >= T_b of a packed sequence are left as they are)."""
+    _req16(da, "da")
+    assert da.stride(-1) == 1
+    _req(lse, torch.float32, "lse")
+    _req(R, torch.float32, "R")
+    assert R.is_contiguous() and tuple(R.shape) == (B, T, T), f"R: expected contiguous [{B}, {T}, {T}], got {tuple(R.shape)}"
+    assert lse.is_contiguous() and lse.numel() >= B * H * T
+    d = _attn_desc(q, k, v, da, lse, B, T, H, causal, None, scale)     # (o is not read: da stands in as the dtype witness)
+    _attn_cu(d, cu, B)
+    d.dout, d.lddo = da.data_ptr(), da.stride(-2)
+    check(_fn("cclip_attention_relevance", q, k, v, da)(ctypes.byref(d), c_float(grad_scale), _p(R), _stream()),
+          "cclip_attention_relevance")
+
+
 def attention_small_fwd(q, k, v, o, *, B: int, T: int, H: int, head_dim: int, lse=None, scale=None) -> None:
     """Generic-head_dim unmasked attention (TransformerMapper): same tensor conventions as attention_fwd."""
     d = _attn_desc(q, k, v, o, lse, B, T, H, False, None, scale, head_dim)

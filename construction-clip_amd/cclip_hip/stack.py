@@ -375,7 +375,8 @@ class BlockStack:
         ws = (scratch or self.scratch).floats(ops.colsum_ws_floats(M, C))
         ops.colsum(dy, gb, ws, R=M, C=C, ld=dy.stride(0), accumulate=acc)
 
-    def backward(self, dx: torch.Tensor, dxb: torch.Tensor, saved: dict, acc: Dict[int, bool]) -> torch.Tensor:
+    def backward(self, dx: torch.Tensor, dxb: torch.Tensor, saved: dict, acc: Dict[int, bool], *,
+                 param_grads: bool = True, relevance=None) -> torch.Tensor:
         """dx (fp32) / dxb (16-bit copy): gradient w.r.t. the stack output, [B*T, D] - or [R, D] on the kept rows when the forward
         ran with tail_rows.  dx is updated in place layer by layer; the fp32 gradient w.r.t. the stack input is left in
         saved["dx_in"] (the argument itself unless the tail was compact) and the matching 16-bit copy is RETURNED.
@@ -385,7 +386,13 @@ class BlockStack:
         weight/bias gradients hang off it as leaves.  They are therefore issued on a SIDE stream (every dY / dX
         copy gets its own buffer - 288 GB makes that free - so nothing is overwritten under a running wgrad): the
         long MFMA-bound wgrad launches fill the CUs while the chain's LN / attention / epilogue phases wait on HBM.
-        CCLIP_WGRAD_STREAM=0 keeps everything on one stream."""
+        CCLIP_WGRAD_STREAM=0 keeps everything on one stream.
+
+        param_grads=False: the dgrad chain only - every block is treated as frozen (no weight / bias gradient, no side stream,
+        no grad_hook).  relevance=(R, stop_layer, grad_scale): at every layer l >= stop_layer the attention relevance of that
+        layer (ops.attention_relevance: R <- R + R C_l, R fp32 [B, T, T]) runs on the layer's attention-output gradient before
+        its attention backward; the walk ends at stop_layer, whose input gradient is not formed (dx / the return value are
+        then meaningless).  grad_scale: the loss scale dx was multiplied by."""
         import os
         geo = self.geo
         D, H = geo.width, geo.heads
@@ -398,7 +405,7 @@ class BlockStack:
         kc = geo.linear_layout
         dact = _DACT[geo.act]
         bf, xs, st, lse = saved["bf"], saved["xs"], saved["st"], saved["lse"]
-        trainable = any(b.grads is not None for b in self.blocks)
+        trainable = param_grads and any(b.grads is not None for b in self.blocks)
         if getattr(self, "refresh_transposed", None) is not None:
             self.refresh_transposed()            # rebuilt once per optimiser step (no-op while the shadows are unchanged)
         side = None
@@ -436,7 +443,7 @@ class BlockStack:
         for l in range(L - 1, -1, -1):
             duet.interleave_point()
             w = self.blocks[l]
-            gr = w.grads
+            gr = w.grads if param_grads else None
             row = bf[l]
             xn1, qkv, a = row[:, 0:D], row[:, D:4 * D], row[:, 4 * D:5 * D]
             xn2, h, g = row[:, 5 * D:6 * D], row[:, 6 * D:6 * D + Hd], row[:, 6 * D + Hd:6 * D + 2 * Hd]
@@ -522,6 +529,12 @@ class BlockStack:
                         self._wgrad(dxb, a, gr["w_o"], M, A("w_o", gr), sc, gr["b_o"], A("b_o", gr), pad=True)
                     leaf(f3)
                 ops.gemm_bf16(dxb, wd("w_o")[0], b_kcontig=wd("w_o")[1], out_bf16=dsm, M=M)
+            if relevance is not None:
+                assert geo.head_dim == 64 and T <= 128, "attention relevance: head_dim 64, T <= 128"
+                ops.attention_relevance(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], lse[l], dsm, relevance[0], B=B, T=T,
+                                        H=H, causal=geo.causal, cu=saved.get("cu"), grad_scale=relevance[2])
+                if l <= relevance[1]:
+                    break
             if geo.head_dim == 64:
                 ops.attention_bwd(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], a, lse[l], dsm, dqkv[:, 0:D],
                                   dqkv[:, D:2 * D], dqkv[:, 2 * D:3 * D], B=B, T=T, H=H, causal=geo.causal,

@@ -625,6 +625,77 @@ class CLIP(nn.Module):
         logits_per_image = _Logits.apply(fi, ft, self.logit_scale)
         return logits_per_image, logits_per_image.t()
 
+    # -- relevance maps (clip/explain.py) ---------------------------------------------------------
+    def relevance(self, image: torch.Tensor, text: torch.Tensor, start_layer: int = -1,
+                  start_layer_text: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Chefer et al. relevance of pair i = (image i, text i) for the score sum_i logits_per_image[i, i] (the reference's
+        interpret(), attention.py:14-69): per tower R = (I + C_{L-1}) ... (I + C_s), C_l the head mean of
+        max(P_l (.) dP_l, 0), over the blocks l >= s (start -1 = the last block only, as in the reference).  Returns
+        (R_image fp32 [N, T_img, T_img], R_text fp32 [N, context_length, context_length]).
+
+        One training-shaped forward of both towers, then a dgrad-only backward from dlogits = I that runs the fused relevance
+        kernel on each block's attention-output gradient and stops at block s.  No parameter gradient is formed: the arena's
+        gradient slots and every .grad stay as they are."""
+        _require_cuda(image, "relevance")
+        _require_cuda(text, "relevance")
+        geo = self.geo
+        if geo.vision_tokens > 128 or geo.context_length > 128 or geo.vision_width % 64 or geo.transformer_width % 64:
+            raise NotImplementedError(
+                f"relevance maps: the fused relevance kernel handles sequences of at most 128 tokens with 64-wide heads; this "
+                f"model has {geo.vision_tokens} image tokens and {geo.context_length} text tokens (ViT-B/16, ViT-L/14 are out of range)")
+        N = image.shape[0]
+        if N == 0 or text.shape[0] != N:
+            raise ValueError(f"relevance: need N >= 1 image / text pairs, got {N} images and {text.shape[0]} texts")
+        with torch.no_grad():
+            fi, ci = self._image_forward(image, train=True)
+            ft, ct = self._text_forward(text, train=True)
+            ls = self.logit_scale.detach().float().reshape(1).contiguous()
+            _, i_n, t_n, inv_i, inv_t = normalized_logits(fi, ft, ls)
+            # _Logits.backward with dlogits = I
+            dl = torch.eye(N, device=fi.device, dtype=torch.float32)
+            d_in, d_tn = torch.empty_like(i_n), torch.empty_like(t_n)
+            ops.gemm_f32(dl, t_n.t(), d_in, alpha_log_dev=ls)
+            ops.gemm_f32(dl.t(), i_n.t(), d_tn, alpha_log_dev=ls)
+            dfi, dft = torch.empty_like(i_n), torch.empty_like(t_n)
+            ops.l2norm_bwd(d_in, i_n, inv_i, dfi)
+            ops.l2norm_bwd(d_tn, t_n, inv_t, dft)
+            r_img = self._tower_relevance("vis", ci, dfi, start_layer)
+            r_txt = self._tower_relevance("txt", ct, dft, start_layer_text)
+        C = geo.context_length
+        if r_txt.shape[1] < C:                  # trim_text_padding ran the tower on fewer positions: the rest stays identity
+            full = torch.eye(C, device=r_txt.device, dtype=torch.float32).repeat(N, 1, 1)
+            full[:, :r_txt.shape[1], :r_txt.shape[1]] = r_txt
+            r_txt = full
+        return r_img, r_txt
+
+    def _tower_relevance(self, tower: str, c: dict, dfeat: torch.Tensor, start: int) -> torch.Tensor:
+        """Pooled LayerNorm backward of one tower, then BlockStack.backward(param_grads=False, relevance=...) from R = I."""
+        ar, st = self._arena, self._rt[tower]
+        p = ar.params
+        vis = tower == "vis"
+        proj, lnw = ("visual.proj", "visual.ln_post.weight") if vis else ("text_projection", "ln_final.weight")
+        B, saved = c["B"], c["saved"]
+        T, L = saved["T"], len(st.blocks)
+        dev = dfeat.device
+        R = torch.eye(T, device=dev, dtype=torch.float32).repeat(B, 1, 1)
+        s = L - 1 if start == -1 else start     # (the reference: only -1 means "last block"; any other value keeps blocks i >= it)
+        if s >= L:
+            return R
+        S = ar.loss_scale()                     # fp16 operands: the dgrad chain runs on S x dfeat (as in training)
+        dfeat = dfeat.contiguous().float()
+        if S != 1.0:
+            dfeat = dfeat * S
+        D = st.geo.width
+        dpooled = torch.empty(B, D, device=dev, dtype=torch.float32)
+        ops.gemm_f32(dfeat, p[proj].data, dpooled)
+        Mo = c["xo"].shape[0]
+        dx = torch.zeros(Mo, D, device=dev, dtype=torch.float32)
+        dxb = torch.zeros(Mo, D, device=dev, dtype=self.compute_dtype)
+        ops.layernorm_bwd(dpooled, c["xo"], p[lnw].data, c["stp"][0], c["stp"][1], rows=B, row_index=c["rows"], dx_out=dx,
+                          dx_out_bf16=dxb)
+        st.backward(dx, dxb, saved, {}, param_grads=False, relevance=(R, max(s, 0), S))
+        return R
+
 
 # ------------------------------------------------------------------------------------------------
 # autograd nodes: forward = kernel sequence; backward = hand-written kernel sequence that writes the

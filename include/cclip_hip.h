@@ -173,6 +173,13 @@ typedef struct cclip_attn_desc {
 } cclip_attn_desc;
 int cclip_attention_fwd(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_bwd(const cclip_attn_desc* d, hipStream_t stream);
+/* Attention relevance of one layer (Chefer et al.; the step of the reference's interpret(), attention.py:14-69), T <= 128:
+ * C = 1 / (H grad_scale) sum_h max(P_h (.) dP_h, 0) with P_h = exp(scale Q_h K_h^T - lse_h) (causal / lengths as in
+ * cclip_attention_bwd) and dP_h = dA_h V_h^T, then R[:T_b, :T_b] += R[:T_b, :T_b] C per sequence; the rest of R is not touched.
+ * Reads q, k, v, lse, B, T, H, causal, scale, cu_seqlens of d; dA is d->dout / d->lddo (the gradient at the attention output,
+ * as for the backward).  R: fp32 [B, T, T], updated in place.  grad_scale > 0: the loss scale the dgrad chain runs under.
+ * Neither P nor dP is written anywhere. */
+int cclip_attention_relevance(const cclip_attn_desc* d, float grad_scale, float* R, hipStream_t stream);
 /* Generic small attention for the reference's TransformerMapper (CLIP_prefix_caption/train.py:141-171: 8 heads of
  * 96 over 40 tokens): any head_dim <= 128 (multiple of 8), T <= 64, no mask; same descriptor; LDS must hold one
  * (batch, head): 4*T*(head_dim+2) + 2*T*(T+1) + T floats <= 160 KiB in backward. */
@@ -418,6 +425,7 @@ int cclip_layernorm_bwd_f16(const void* dy, int32_t dy_is_f16, int64_t lddy, con
                             float* ws, hipStream_t stream);
 int cclip_attention_fwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_bwd_f16(const cclip_attn_desc* d, hipStream_t stream);
+int cclip_attention_relevance_f16(const cclip_attn_desc* d, float grad_scale, float* R, hipStream_t stream);
 int cclip_attention_small_fwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_small_bwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_decode_f16(const void* q, int64_t ldq, const void* kcache, const void* vcache, int64_t ld_pos,
