@@ -1051,6 +1051,31 @@ def add_positional(emb, wpe, x, *, rows: int, S: int) -> None:
           "cclip_add_positional")
 
 
+def caption_prompt(feat, prompts, head_start, logit_scale, table, probs, index, ids) -> None:
+    """The zero-shot heads over N image feature rows and the attribute ids their arg-maxes select, in one launch
+    (cclip_caption_prompt): feat fp32 [N, E] (rows may be strided), prompts fp32 [K, E] of len(head_start) - 1 heads laid one
+    after another, head_start a host sequence of ints (head g = prompt rows [head_start[g], head_start[g+1])), logit_scale a
+    device scalar holding log(scale), table int32 [prod K_g, A].  Fills probs fp32 [N, K] (softmax per head), index int32
+    [N, G] (arg-max per head, the lowest index on a tie) and ids int32 [N, A] = table[combination of the arg-maxes]."""
+    for t, name in ((feat, "feat"), (prompts, "prompts"), (logit_scale, "logit_scale"), (probs, "probs")):
+        _req(t, torch.float32, name)
+    for t, name in ((table, "table"), (index, "index"), (ids, "ids")):
+        _req(t, torch.int32, name)
+    hs = [int(v) for v in head_start]
+    G = len(hs) - 1
+    N, E = feat.shape
+    K = prompts.shape[0]
+    A = table.shape[1]
+    assert feat.stride(1) == 1 and prompts.is_contiguous() and prompts.shape[1] == E and table.is_contiguous()
+    assert logit_scale.numel() == 1
+    assert probs.is_contiguous() and probs.shape == (N, K) and index.is_contiguous() and index.shape == (N, max(G, 0))
+    assert ids.is_contiguous() and ids.shape == (N, A)
+    arr = (c_int * (G + 1))(*hs) if G >= 0 else None
+    check(lib.cclip_caption_prompt(_p(feat), c_long(feat.stride(0)), c_int(N), c_int(E), _p(prompts), c_int(K), arr, c_int(G),
+                                   _p(logit_scale), _p(table), c_int(table.shape[0]), c_int(A), _p(probs), _p(index), _p(ids),
+                                   _stream()), "cclip_caption_prompt")
+
+
 def colsum_ws_floats(R: int, C: int) -> int:
     return lib.cclip_colsum_ws_floats(c_int(R), c_int(C))
 

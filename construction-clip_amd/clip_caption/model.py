@@ -695,6 +695,16 @@ class ClipCaptionModel(nn.Module):
         64 // beam_size captions of cclip_gpt2_beam_search_batch, one host sync each.  Returns (tokens [N, beams, n] int64,
         seq_lengths [N, beams], scores [N, beams], n_sel [N]); caption i's tokens are valid up to n_sel[i] columns (where its
         own loop stops), the columns after that are zero."""
+        return self.beam_batch_collect(self.beam_batch_enqueue(inputs_embeds, beam_size, entry_length, temperature, stop_token,
+                                                               grid_cap=grid_cap))
+
+    @torch.no_grad()
+    def beam_batch_enqueue(self, inputs_embeds: torch.Tensor, beam_size: int, entry_length: int, temperature: float,
+                           stop_token: int, grid_cap: int = 0, positions_added: bool = False):
+        """The device half of beam_search_native_batch: every prefill and every batched launch is enqueued on the current
+        stream and nothing is read back, so the host does not wait for the device here.  positions_added: the rows already
+        hold `+ wpe[s]` (what cclip_caption_embed writes), so the positional add is skipped.  Returns the pending launches for
+        beam_batch_collect."""
         self._ensure_runtime()
         self._arena.refresh_shadows()
         g, st = self.model.geo, self._stack
@@ -712,21 +722,21 @@ class ClipCaptionModel(nn.Module):
         emb = inputs_embeds.detach().float().contiguous()
         pre = KVCache(g.n_layer, N, S, D, dev, self.compute_dtype)
         first_all = torch.empty(N, g.vocab_size, device=dev, dtype=torch.float32)
-        last = torch.tensor([S - 1], device=dev, dtype=torch.int32)
+        last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)    # (a fill launch: no host-to-device copy to wait for)
         for i in range(N):
-            x = torch.empty(S, D, device=dev, dtype=torch.float32)
-            ops.add_positional(emb[i], wpe, x, rows=S, S=S)
+            if positions_added:
+                x = emb[i].clone()                                       # (the stack works in place on its input rows)
+            else:
+                x = torch.empty(S, D, device=dev, dtype=torch.float32)
+                ops.add_positional(emb[i], wpe, x, rows=S, S=S)
             xo = st.forward(x, 1, T=S, kv_out=(pre.k[:, i:i + 1], pre.v[:, i:i + 1]))
             first_all[i] = self._lm_rows(xo, last, False)[0].view(-1)
         if getattr(self, "_decode_ptrs", None) is None or self._decode_ptrs[0] is not self._arena:
             self._decode_ptrs = (self._arena, ops.block_ptr_array(st.blocks))
         hidden = st.geo.hidden or 4 * D
         per = max(1, ops.BEAM_BATCH_MAX_ROWS // beam_size)
-        tokens = torch.zeros(N, beam_size, entry_length, device=dev, dtype=torch.int64)
-        lengths = torch.empty(N, beam_size, device=dev, dtype=torch.float32)
-        scores = torch.empty(N, beam_size, device=dev, dtype=torch.float32)
-        n_sel = torch.empty(N, dtype=torch.int64)
         grid_cap = grid_cap or int(os.environ.get("CCLIP_BEAM_GRID", "0"))
+        launches = []
         for c0 in range(0, N, per):
             n = min(per, N - c0)
             R = n * beam_size
@@ -742,6 +752,19 @@ class ClipCaptionModel(nn.Module):
                                        wte_f32=p["model.transformer.wte.weight"].data, wpe_f32=wpe, temperature=float(temperature),
                                        stop_token=int(stop_token), first_logits=first_all[c0:c0 + n].contiguous(), grid_cap=grid_cap,
                                        linear_layout=bool(st.geo.linear_layout))
+            launches.append((c0, n, bs, (k, v, scratch)))                # (the buffers live until the launch has been read)
+        return dict(N=N, beams=beam_size, entry_length=entry_length, device=dev, launches=launches)
+
+    @torch.no_grad()
+    def beam_batch_collect(self, pending):
+        """The host half of beam_search_native_batch: reads every pending launch back (one host sync per launch) and returns
+        what beam_search_native_batch returns."""
+        N, beam_size, entry_length, dev = pending["N"], pending["beams"], pending["entry_length"], pending["device"]
+        tokens = torch.zeros(N, beam_size, entry_length, device=dev, dtype=torch.int64)
+        lengths = torch.empty(N, beam_size, device=dev, dtype=torch.float32)
+        scores = torch.empty(N, beam_size, device=dev, dtype=torch.float32)
+        n_sel = torch.empty(N, dtype=torch.int64)
+        for c0, n, bs, _ in pending["launches"]:
             state, cap = bs.state.tolist(), bs.cap_state.cpu()          # the one host sync of the launch
             if state[1]:
                 raise RuntimeError("cclip_gpt2_beam_search_batch: a grid barrier timed out (workgroups not co-resident?)")
@@ -751,6 +774,7 @@ class ClipCaptionModel(nn.Module):
             tokens[c0:c0 + n] = (bs.tokens.view(n, beam_size, entry_length).long() * keep.to(dev)[:, None, :])
             lengths[c0:c0 + n] = bs.seq_lengths.view(n, beam_size)
             scores[c0:c0 + n] = bs.scores.view(n, beam_size)
+        pending["launches"] = []
         return tokens[:, :, :int(n_sel.max())], lengths, scores, n_sel
 
     def _embed_and_run(self, tokens, prefix, attribute, mask, train: bool, pack: bool = False):

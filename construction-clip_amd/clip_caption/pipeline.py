@@ -1,0 +1,223 @@
+"""One call from image to caption: what the reference serves as `/predict` (/root/reference/application.py:80-108, root
+predict.py:62-76, `predict()` of CLIP_prefix_caption/test.py:516-549) - encode the image, two zero-shot heads (caption type,
+violation type), the attribute string they select as decoder prompt, the prefix projection, beam search - with the device
+stage enqueued back to back and nothing read by the host in between.
+
+The attribute string `f"{caption_type} {violation_type} "` has only len(caption_types) * len(violation_types) = 18 values.  All
+of them are tokenised ONCE, when the Captioner is built, into an id table on the device; which row an image gets is an
+index the device computes from its feature vector (cclip_caption_prompt: both heads' softmax, arg-max and the table row in one
+launch for all N images).  The reference's per-image `.cpu()` / arg-max / `tokenizer.encode` / host-built id tensor / `wte` /
+`torch.cat` between encode_image and the decoder are gone; `cclip_caption_embed` writes the decoder's input rows from the
+projected prefix and the selected ids.
+
+Labels: like `extract_embeddings` (parse_coco.py:47,54) and test.py:527,532 a head reports `caption_types.values()` (現況 / 缺失)
+and the entries of `violation_types`; application.py's English keys are only the CLIP prompts.
+"""
+from __future__ import annotations
+
+from typing import Callable, Dict, List, Optional, Sequence
+
+import torch
+
+from cclip_hip import ops
+
+from .data import CAPTION_TYPES, VIOLATION_TYPES
+from .generate import _beam_outputs, generate2_batch, generate_beam_batch
+
+
+def attribute_strings(caption_labels: Sequence[str], violation_labels: Sequence[str]) -> List[str]:
+    """every attribute string test.py:534 can form, caption type slowest (row i * len(violation_labels) + j)"""
+    return [f"{c} {v} " for c in caption_labels for v in violation_labels]
+
+
+def build_attribute_table(tokenizer, caption_labels: Sequence[str], violation_labels: Sequence[str],
+                          attribute_length: int) -> torch.Tensor:
+    """int32 [len(caption_labels) * len(violation_labels), attribute_length]: `tokenizer.encode` of every attribute string, right
+    padded with id 0 (test.py:536-538).  A string that needs more ids than attribute_length raises ValueError (the reference
+    fails there with a negative pad size)."""
+    strings = attribute_strings(caption_labels, violation_labels)
+    table = torch.zeros(len(strings), attribute_length, dtype=torch.int32)
+    for r, s in enumerate(strings):
+        enc = list(tokenizer.encode(s))
+        if len(enc) > attribute_length:
+            raise ValueError(f"attribute {s!r} needs {len(enc)} token ids, attribute_length is {attribute_length}")
+        table[r, :len(enc)] = torch.tensor(enc, dtype=torch.int32)
+    return table
+
+
+class PendingCaptions:
+    """What Captioner.submit returns: the device work is enqueued; result() reads it back and decodes the text."""
+
+    def __init__(self, cap: "Captioner", n: int, probs, index, ids, greedy: bool, pending=None, eager=None):
+        self._cap, self._n, self._probs, self._index, self._ids = cap, n, probs, index, ids
+        self._greedy, self._pending, self._eager = greedy, pending, eager
+        self._done = None
+
+    def result(self, return_tokens: bool = False):
+        if self._done is None:
+            cap, tok = self._cap, self._cap.tokenizer
+            if self._pending is not None:                                 # the read-back of the batched launches
+                tokens, lengths, scores, n_sel = cap.caption_model.beam_batch_collect(self._pending)
+                self._pending = None
+                texts, per = [], []
+                for i in range(self._n):
+                    rows = tokens[i, :, :int(n_sel[i])]
+                    if self._greedy:                                       # generate2_batch's decode of the one-beam row
+                        texts.append(tok.decode(list(rows.squeeze(0).cpu().numpy())))
+                        per.append(rows)
+                    else:                                                  # generate_beam_batch's: best beam first
+                        t, tk, ln, sc = _beam_outputs(tok, rows, lengths[i], scores[i], True)
+                        texts.append(t[0])
+                        per.append((tk, ln, sc))
+            else:
+                texts, per = self._eager
+            probs, index, ids = self._probs.cpu(), self._index.cpu(), self._ids.cpu()
+            k0 = cap.head_start[1]
+            records = []
+            for i in range(self._n):
+                c, v = int(index[i, 0]), int(index[i, 1])
+                records.append({"caption_type": cap.caption_labels[c], "violation_type": cap.violation_labels[v],
+                                "attribute": cap.attributes[c * len(cap.violation_labels) + v], "prediction": texts[i],
+                                "type_probs": probs[i, :k0].tolist(), "violation_probs": probs[i, k0:].tolist()})
+            self._done = (records, {"ids": ids, "index": index, "tokens": per})
+        return self._done if return_tokens else self._done[0]
+
+
+class Captioner:
+    """Captioner(clip_model, caption_model, tokenizer).describe(images) -> one record per image:
+    {"caption_type", "violation_type", "attribute", "prediction", "type_probs", "violation_probs"}.
+
+    clip_tokenize turns the prompt strings into CLIP token rows (default clip.tokenize); the prompts are
+    `caption_types.keys()` and `violation_types`, the reported labels `caption_types.values()` and `violation_types` (as
+    extract_embeddings / test.py do; application.py reports the keys).  caption_model may be None for a Captioner that is only
+    asked to `embed`.  preprocess (default clip.DevicePreprocess at the model's
+    resolution) is applied to PIL images / uint8 HWC arrays; float tensors [N, 3, R, R] are taken as preprocessed."""
+
+    def __init__(self, clip_model, caption_model, tokenizer, clip_tokenize: Optional[Callable] = None,
+                 caption_types: Optional[Dict[str, str]] = None, violation_types: Optional[Sequence[str]] = None,
+                 prefix_length: int = 20, attribute_length: int = 20, preprocess: Optional[Callable] = None):
+        if clip_tokenize is None:
+            from clip import tokenize as clip_tokenize
+        caption_types = dict(CAPTION_TYPES if caption_types is None else caption_types)
+        violation_types = list(VIOLATION_TYPES if violation_types is None else violation_types)
+        self.clip_model, self.caption_model, self.tokenizer = clip_model, caption_model, tokenizer
+        self.prefix_length, self.attribute_length = prefix_length, attribute_length
+        self.caption_labels, self.violation_labels = list(caption_types.values()), violation_types
+        self.attributes = attribute_strings(self.caption_labels, self.violation_labels)
+        self.device = clip_model.logit_scale.device
+        self._preprocess = preprocess
+        with torch.no_grad():                                              # the prompts of both heads, encoded once
+            heads = [clip_model.encode_text(clip_tokenize(p).to(self.device)).float()
+                     for p in (list(caption_types.keys()), violation_types)]
+        self.prompts = torch.cat(heads).contiguous()
+        self.head_start = (0, heads[0].shape[0], heads[0].shape[0] + heads[1].shape[0])
+        self.table = build_attribute_table(tokenizer, self.caption_labels, self.violation_labels, attribute_length).to(self.device)
+
+    # ---- input ----
+    def _images(self, images) -> torch.Tensor:
+        if isinstance(images, torch.Tensor) and images.is_floating_point():
+            if images.dim() != 4 or images.shape[1] != 3:
+                raise ValueError(f"preprocessed images must be [N, 3, R, R], got {tuple(images.shape)}")
+            return images.to(self.device, non_blocking=True)
+        if self._preprocess is None:
+            from clip import DevicePreprocess
+            self._preprocess = DevicePreprocess(self.clip_model.visual.input_resolution, self.device)
+        return torch.stack([self._preprocess(im).to(self.device) for im in images])
+
+    # ---- device stage ----
+    def _classify(self, feat: torch.Tensor):
+        N = feat.shape[0]
+        probs = torch.empty(N, self.prompts.shape[0], device=feat.device, dtype=torch.float32)
+        index = torch.empty(N, 2, device=feat.device, dtype=torch.int32)
+        ids = torch.empty(N, self.attribute_length, device=feat.device, dtype=torch.int32)
+        scale = self.clip_model.logit_scale.detach().float().reshape(1)
+        ops.caption_prompt(feat, self.prompts, self.head_start, scale, self.table, probs, index, ids)
+        return probs, index, ids
+
+    @torch.no_grad()
+    def embed(self, images, batch_size: int = 256):
+        """(features [N, E] fp32, index int32 [N, 2], ids int32 [N, attribute_length]) on the device, without decoding: what
+        parse_coco.py:38-56 computes per annotation (the embedding, the two zero-shot arg-maxes, the attribute's ids)."""
+        images = self._images(images)
+        feat = torch.cat([self.clip_model.encode_image(images[s:s + batch_size]).float() for s in range(0, images.shape[0], batch_size)])
+        _, index, ids = self._classify(feat.contiguous())
+        return feat, index, ids
+
+    def _features_one_by_one(self, images: torch.Tensor) -> torch.Tensor:
+        # image by image, like the decoder's prefills: the tiled GEMMs choose tiles / splits by row count, so a batched tower
+        # would make an image's features - and through the 16-bit prefix its tokens - depend on the images around it
+        return torch.cat([self.clip_model.encode_image(images[i:i + 1]).float() for i in range(images.shape[0])]).contiguous()
+
+    def _project(self, feat: torch.Tensor) -> torch.Tensor:
+        N = feat.shape[0]
+        return torch.cat([self.caption_model.clip_project(feat[i:i + 1]).reshape(1, -1) for i in range(N)]).contiguous()
+
+    @torch.no_grad()
+    def submit(self, images: torch.Tensor, beam_size: int = 3, entry_length: int = 100, temperature: float = 0.5,
+               stop_token: int = 102, greedy: bool = False, top_p: float = 0.8) -> PendingCaptions:
+        """Enqueue the whole device stage for preprocessed images [N, 3, R, R] - encode_image, the zero-shot heads and attribute
+        ids, clip_project, the decoder's input rows, the prefills and the batched beam launches - and return without waiting
+        for the device; `.result()` reads back and decodes.  Where the batched kernel does not apply
+        (ClipCaptionModel.beam_batch_native_ok) the work is done here, through generate_beam_batch / generate2_batch."""
+        model = self.caption_model
+        images = self._images(images)
+        N = images.shape[0]
+        if N < 1:
+            raise ValueError("need at least one image")
+        P, A = self.prefix_length, self.attribute_length
+        beams = 1 if greedy else beam_size
+        ok = getattr(model, "beam_batch_native_ok", None)
+        native = ok is not None and (top_p > 0 or not greedy) and ok(beams, P + A, entry_length)
+        was_training = getattr(model, "training", None)
+        try:
+            feat = self._features_one_by_one(images)
+            probs, index, ids = self._classify(feat)
+            proj = self._project(feat)                                     # test.py:521,540: on the fp32 features
+            if native:
+                D = proj.shape[1] // P
+                x = torch.empty(N * (P + A), D, device=feat.device, dtype=torch.float32)
+                tr = model.gpt.transformer
+                ops.caption_embed(proj, ids, tr.wte.weight.data, tr.wpe.weight.data, x, B=N, P=P, Lt=A)
+                pending = model.beam_batch_enqueue(x.view(N, P + A, D), beams, entry_length, temperature, stop_token,
+                                                   positions_added=True)
+                return PendingCaptions(self, N, probs, index, ids, greedy, pending=pending)
+            emb = torch.cat((proj.view(N, P, -1), model.gpt.transformer.wte(ids.long())), dim=1)      # test.py:540-542
+            if greedy:
+                eager = generate2_batch(model, self.tokenizer, emb, entry_length=entry_length, top_p=top_p, temperature=temperature,
+                                        stop_token=stop_token, return_tokens=True)
+            else:
+                texts, per = generate_beam_batch(model, self.tokenizer, emb, beam_size=beam_size, entry_length=entry_length,
+                                                 temperature=temperature, stop_token=stop_token, return_tokens=True)
+                eager = ([t[0] for t in texts], per)
+            return PendingCaptions(self, N, probs, index, ids, greedy, eager=eager)
+        finally:
+            if was_training is not None and model.training != was_training:   # (generate_* switch the model to eval)
+                model.train(was_training)
+
+    def describe(self, images, beam_size: int = 3, entry_length: int = 100, temperature: float = 0.5, stop_token: int = 102,
+                 greedy: bool = False, top_p: float = 0.8, return_tokens: bool = False):
+        """The records of `images` (a preprocessed float tensor [N, 3, R, R], or a sequence of PIL images / uint8 HWC arrays).
+        More images than one batched launch holds (64 // beams) go in chunks of that size; the next chunk is enqueued before
+        the previous one is read back.  return_tokens: also {"ids" [N, A], "index" [N, 2], "tokens": per caption what
+        generate_beam_batch (generate2_batch with greedy) returns with return_tokens}."""
+        images = self._images(images)
+        per = max(1, ops.BEAM_BATCH_MAX_ROWS // (1 if greedy else max(1, beam_size)))
+        kw = dict(beam_size=beam_size, entry_length=entry_length, temperature=temperature, stop_token=stop_token, greedy=greedy,
+                  top_p=top_p)
+        records, extras, prev = [], [], None
+        for s in range(0, images.shape[0], per):
+            nxt = self.submit(images[s:s + per], **kw)
+            if prev is not None:
+                r, e = prev.result(True)
+                records += r
+                extras.append(e)
+            prev = nxt
+        if prev is None:
+            raise ValueError("need at least one image")
+        r, e = prev.result(True)
+        records += r
+        extras.append(e)
+        if not return_tokens:
+            return records
+        return records, {"ids": torch.cat([e["ids"] for e in extras]), "index": torch.cat([e["index"] for e in extras]),
+                         "tokens": [t for e in extras for t in e["tokens"]]}

@@ -252,6 +252,23 @@ int cclip_colsum_ws_floats(int32_t R, int32_t C);
 int cclip_colsum(const void* in, int32_t in_is_bf16, int64_t ld, int32_t R, int32_t C, float* out,
                  int32_t accumulate, float* ws, hipStream_t stream);
 
+/* ---- image features -> zero-shot heads -> attribute ids (CLIP_prefix_caption/test.py:521-542) -----------------
+ * One launch for N feature rows feat [N, E] fp32 (row stride ldf, as encode_image returns them: not normalised) against
+ * the text features prompts [K, E] fp32 of G heads laid one after another (as encode_text returns them; the kernel
+ * normalises them).  head_start is a HOST array of G + 1 ints read during the call: head g owns prompt rows
+ * [head_start[g], head_start[g+1]), head_start[0] = 0, head_start[G] = K.  With K_g the size of head g:
+ *   logit[n,k] = exp(*logit_scale_dev) * <feat_n, prompt_k> / (|feat_n| |prompt_k|)
+ *   probs[n,k] = exp(logit[n,k]) / sum_{j in head(k)} exp(logit[n,j])                                   fp32 [N, K]
+ *   index[n,g] = arg-max of logit[n, head g], counted from the head's first row, the LOWEST on a tie   int32 [N, G]
+ *   ids[n,:]   = table[((index[n,0] * K_1) + index[n,1]) * K_2 + ...]                                   int32 [N, A]
+ * table: int32 [table_rows, A] on the device with table_rows = prod_g K_g (head 0 slowest).  fp32 arithmetic in a fixed
+ * order (no atomics): two launches are bitwise equal.  CCLIP_ERR_ARG: a null pointer; N, E, K, G or A <= 0; G > 16; a head
+ * with no prompts; table_rows != prod_g K_g; E % 4, E > 1024, ldf < E, ldf % 4, feat or prompts not 16-byte aligned;
+ * (K * E + 4 K) floats above 64 KiB (the prompt rows live in LDS).  It touches no 16-bit operand: one form, no _f16 twin. */
+int cclip_caption_prompt(const float* feat, int64_t ldf, int32_t N, int32_t E, const float* prompts, int32_t K,
+                         const int32_t* head_start, int32_t G, const float* logit_scale_dev, const int32_t* table,
+                         int32_t table_rows, int32_t A, float* probs, int32_t* index, int32_t* ids, hipStream_t stream);
+
 /* ---- loss side (fp32) ------------------------------------------------------------------------
  * cclip_l2norm_fwd/bwd: y = x / ||x||_2 per row (image_features / image_features.norm(dim=1)).
  * cclip_xent_rows: per row r with label labels[r]: loss_row = logsumexp(row) - row[label]
