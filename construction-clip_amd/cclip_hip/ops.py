@@ -626,6 +626,42 @@ def attention_relevance(q, k, v, lse, da, R, *, B: int, T: int, H: int, causal: 
           "cclip_attention_relevance")
 
 
+ATTENTION_PROBS_MAX_T = 256
+
+
+def attention_probs(q, k, P, *, B: int, T: int, H: int, causal: bool = False, scale=None, key_keep=None, lse=None,
+                    q_rows=None) -> None:
+    """Attention probabilities of one layer: P[b, h, i, :T] = softmax_j(scale q_t k_j + mask), t = q_rows[i] (q_rows: int32
+    device tensor [n_q] of query positions shared by all sequences, values outside 0 .. T-1 are clamped; None = all T
+    positions).  q / k as for attention_fwd; P fp32 [B, H, n_q, >= T] with inner stride 1 (any other strides), may be
+    uninitialised: every element [.., :T] is written, masked and above-diagonal entries with exactly 0.  key_keep: fp32
+    [B, T], 0 masks a key.  lse is accepted for symmetry with the other attention bindings and not read (the kernel
+    normalises from the scores it holds).  T <= 256."""
+    if T > ATTENTION_PROBS_MAX_T:
+        raise NotImplementedError(f"attention_probs: T = {T} above the kernel's limit of {ATTENTION_PROBS_MAX_T} key positions")
+    for t, n in ((q, "q"), (k, "k")):
+        _req16(t, n)
+        assert t.dim() == 2 and t.stride(-1) == 1 and t.shape[0] >= B * T and t.shape[1] >= H * 64, \
+            f"{n}: expected [>= {B * T}, >= {H * 64}] rows of heads, got {tuple(t.shape)}"
+    _req(P, torch.float32, "P")
+    n_q = T
+    if q_rows is not None:
+        assert q_rows.dtype == torch.int32 and q_rows.is_cuda and q_rows.is_contiguous() and q_rows.dim() == 1 and q_rows.numel() >= 1
+        n_q = q_rows.numel()
+    assert P.dim() == 4 and tuple(P.shape[:3]) == (B, H, n_q) and P.shape[3] >= T and P.stride(3) == 1, \
+        f"P: expected [{B}, {H}, {n_q}, >= {T}] with inner stride 1, got {tuple(P.shape)} / {P.stride()}"
+    if key_keep is not None:
+        _req(key_keep, torch.float32, "key_keep")
+        assert key_keep.is_contiguous() and key_keep.numel() == B * T
+    d = AttnDesc()
+    d.q, d.k, d.ldq, d.ldk = q.data_ptr(), k.data_ptr(), q.stride(-2), k.stride(-2)
+    d.key_keep = 0 if key_keep is None else key_keep.data_ptr()
+    d.B, d.T, d.H, d.head_dim, d.causal = B, T, H, 64, int(causal)
+    d.scale = 64 ** -0.5 if scale is None else scale
+    check(_fn("cclip_attention_probs", q, k)(ctypes.byref(d), _p(q_rows), c_int(n_q), _p(P), c_long(P.stride(0)),
+                                             c_long(P.stride(1)), c_long(P.stride(2)), _stream()), "cclip_attention_probs")
+
+
 def attention_small_fwd(q, k, v, o, *, B: int, T: int, H: int, head_dim: int, lse=None, scale=None) -> None:
     """Generic-head_dim unmasked attention (TransformerMapper): same tensor conventions as attention_fwd."""
     d = _attn_desc(q, k, v, o, lse, B, T, H, False, None, scale, head_dim)

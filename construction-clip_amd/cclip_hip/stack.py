@@ -170,11 +170,14 @@ class BlockStack:
     def forward(self, x: torch.Tensor, B: int, *, saved: Optional[dict] = None,
                 key_keep: Optional[torch.Tensor] = None, T: Optional[int] = None, kv_out=None,
                 cu: Optional[torch.Tensor] = None, tail_rows: Optional[torch.Tensor] = None,
-                weights_version=None) -> torch.Tensor:
+                weights_version=None, attn_probe=None) -> torch.Tensor:
         """x: fp32 [B*T, D] residual stream entering block 0; returns the stream leaving the last block.
         saved=None (inference) keeps nothing and updates x in place; otherwise x must be saved["xs"][0,0].
         kv_out = (kcache, vcache), each [L, B, Smax, D] 16-bit: every layer's keys / values of positions [0, T) are
-        kept there (prefill of the KV-cached decode, see decode_step)."""
+        kept there (prefill of the KV-cached decode, see decode_step).
+        attn_probe(l, q, k, key_keep): called once per layer while that layer's packed q / k rows ([M, D] views of the qkv
+        buffer, which the next layer overwrites) are live - the tap ops.attention_probs reads (output_attentions).  It only
+        reads: the launches of the pass itself are the same with and without it."""
         geo = self.geo
         D, H = geo.width, geo.heads
         Hd = geo.hidden or 4 * D
@@ -187,6 +190,7 @@ class BlockStack:
         # kernel simply sees M = x.shape[0] rows, only the attention needs the row ranges
         M = x.shape[0] if cu is not None else B * T
         assert cu is None or (geo.head_dim == 64 and T <= 128 and kv_out is None)
+        assert attn_probe is None or (cu is None and geo.head_dim == 64)
         L = len(self.blocks)
         dev = x.device
         kc = geo.linear_layout
@@ -258,6 +262,8 @@ class BlockStack:
             if kv_out is not None:       # data movement only
                 kv_out[0][l, :B, :T].copy_(qkv[:M, D:2 * D].view(B, T, D))
                 kv_out[1][l, :B, :T].copy_(qkv[:M, 2 * D:3 * D].view(B, T, D))
+            if attn_probe is not None:
+                attn_probe(l, qkv[:M, 0:D], qkv[:M, D:2 * D], key_keep)
             if geo.head_dim == 64:
                 a_mx = f8 and wide and H % 2 == 0 and not (tail_rows is not None and l == L - 1)   # the attention writes the out-proj's block-scaled e4m3 operand itself
                 ops.attention_fwd(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], a, B=B, T=T, H=H, causal=geo.causal,

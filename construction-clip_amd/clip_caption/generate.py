@@ -9,14 +9,58 @@ arg-max) is the reference's.  For GPT-2 geometry `generate_beam` / `generate2` r
 one persistent kernel launch (ClipCaptionModel.beam_search_native); the host-side search below (class _Beams) covers what that
 kernel does not.  The reference's loops themselves are restated only in oracle/caption_oracle.py, the checker.
 
-Not carried over: the attention-map dump that the reference's test.py copy of generate_beam interleaves with decoding
-(`output_attentions=True`, test.py:381-390, `attention_map(...)` :438) - visualisation, SURVEY.md section 8 out of scope.
+Attention maps (`output_attentions=True` at every step of the reference's test.py copy of generate_beam, test.py:381-390, and
+`attention_map(...)`, :438): `return_attention=True` on the four generate functions.  The decode kernels are not instrumented.
+GPT-2 is causal, so row t of ONE forward over a finished sequence is the distribution the decode step at position t formed:
+after the search, every returned beam's own sequence [prefix, wte(tokens[:n-1])] goes through one batched forward with a
+probability launch on the n query rows (ClipCaptionModel.attention_probs, csrc/attention_probs.hip), whichever path - native
+kernel, batched kernel, host loop - produced the tokens.  `caption_attention_map` is the reference's `attention_map`.
 """
 from __future__ import annotations
 
 from typing import List, Optional
 
 import torch
+
+
+def _replay_attention(model, prefixes, generated, layer: int) -> List[torch.Tensor]:
+    """Per sequence i the rows [H, n_i, S0 + n_i - 1] of layer `layer`: row j = the attention of query position S0-1+j, the
+    one whose logits produced generated[i][j].  prefixes: [S0, D] embeddings (one shared S0), generated: 1-D token tensors.
+    One forward over all sequences, right-padded to the longest: no mask is needed, a row below a sequence's length only
+    sees real keys, and what lies beyond is cut off here."""
+    probs = getattr(model, "attention_probs", None)
+    if probs is None:
+        raise NotImplementedError("return_attention needs ClipCaptionModel.attention_probs")
+    S0 = prefixes[0].shape[0]
+    ns = [int(g.numel()) for g in generated]
+    if min(ns) < 1:
+        raise ValueError("return_attention: a sequence without a generated token has no attention row")
+    nmax, dev = max(ns), prefixes[0].device
+    x = torch.stack([p.detach().float() for p in prefixes])
+    if nmax > 1:
+        ids = torch.zeros(len(ns), nmax - 1, dtype=torch.long, device=dev)
+        for i, g in enumerate(generated):                                 # (the last generated token is never fed)
+            ids[i, :ns[i] - 1] = g[:ns[i] - 1].to(dev)
+        x = torch.cat((x, model.gpt.transformer.wte(ids)), dim=1)
+    att = probs(x, None, layers=[layer], q_rows=range(S0 - 1, S0 - 1 + nmax))[0]
+    return [att[i, :, :n, :S0 + n - 1].clone() for i, n in enumerate(ns)]
+
+
+def caption_attention_map(attention: torch.Tensor, head: Optional[int] = -1, pad_value: float = 1.0) -> torch.Tensor:
+    """`attention_map` of test.py:342-349 for one sequence's rows [H, n, S0 + n - 1] (what return_attention yields): the rows
+    of one head (`head=-1`: the last, the reference's `[:, -1, -1, :]`; None: the mean over heads), each cut to its causal
+    length S0 + j and right-padded with pad_value (the reference pads with 1) to the last row's length -> [n, S0 + n - 1]."""
+    if attention.dim() != 3:
+        raise ValueError(f"attention must be [H, n, S0 + n - 1], got {tuple(attention.shape)}")
+    rows = attention.mean(dim=0) if head is None else attention[head]
+    n, width = rows.shape
+    causal_len = torch.arange(width - n + 1, width + 1, device=rows.device)[:, None]
+    return torch.where(torch.arange(width, device=rows.device)[None, :] < causal_len, rows, torch.full_like(rows, pad_value))
+
+
+def _beam_rows(tokens, seq_lengths, n_prompt: int):
+    """the generated part of every beam: its int(seq_length) tokens after the prompt"""
+    return [tokens[b, n_prompt:n_prompt + int(n)] for b, n in enumerate(seq_lengths.tolist())]
 
 
 def _step_logits(model, embeds: torch.Tensor, cache):
@@ -26,12 +70,24 @@ def _step_logits(model, embeds: torch.Tensor, cache):
 
 @torch.no_grad()
 def generate_beam(model, tokenizer, beam_size: int = 3, prompt=None, embed=None, entry_length: int = 100,
-                  temperature: float = 0.5, stop_token: int = 102, return_tokens: bool = False):
+                  temperature: float = 0.5, stop_token: int = 102, return_tokens: bool = False,
+                  return_attention: bool = False, attention_layer: int = -1):
     """Beam search over length-normalised log-probabilities (test.py:353-441).  Returns the decoded texts best-first;
-    with return_tokens also (token tensor [beams, steps], lengths, scores) in beam order."""
+    with return_tokens also (token tensor [beams, steps], lengths, scores) in beam order.  return_attention appends one more
+    element: per beam, in the row order of the token tensor, the fp32 rows [H, n, S0 + n - 1] of layer attention_layer
+    (n = the beam's length, S0 = the prefix / prompt length; row j = the distribution that produced generated token j)."""
     model.eval()
     device = next(model.parameters()).device
     tokens = None
+
+    def finish(prefix, prompt_tokens, tokens, seq_lengths, scores):
+        out = _beam_outputs(tokenizer, tokens, seq_lengths, scores, return_tokens)
+        if not return_attention:
+            return out
+        n_prompt = 0 if prompt_tokens is None else prompt_tokens.shape[1]
+        gen = _beam_rows(tokens, seq_lengths, n_prompt)
+        att = _replay_attention(model, [prefix[0]] * len(gen), gen, attention_layer)
+        return (*out, att) if return_tokens else (out, att)
     if getattr(model, "beam_native_ok", None) is not None and model.beam_native_ok(beam_size) and entry_length >= 1:
         # prefill, then ONE persistent kernel for every decode step and every selection (csrc/decode_persist.hip); the
         # host loop below is the same arithmetic op by op and stays as its parity reference (CCLIP_BEAM_NATIVE=0)
@@ -40,9 +96,10 @@ def generate_beam(model, tokenizer, beam_size: int = 3, prompt=None, embed=None,
         else:
             tokens = torch.tensor(tokenizer.encode(prompt)).unsqueeze(0).to(device)
             generated = model.gpt.transformer.wte(tokens)
+        prompt_tokens = tokens
         tokens, seq_lengths, scores = model.beam_search_native(generated, beam_size, entry_length, temperature, stop_token,
-                                                               prompt_tokens=tokens)
-        return _beam_outputs(tokenizer, tokens, seq_lengths, scores, return_tokens)
+                                                               prompt_tokens=prompt_tokens)
+        return finish(generated, prompt_tokens, tokens, seq_lengths, scores)
     # Host-side search (nn.Linear-layout stacks, > 8 beams, CPU stubs in the tests, CCLIP_BEAM_NATIVE=0): one KV-cached decode
     # step per position, the beam bookkeeping kept in a _Beams record.  Same selection rule as the reference (a stopped beam
     # may only extend by token 0 at no cost; candidates ranked by total log-probability / length), written as one masked
@@ -67,7 +124,7 @@ def generate_beam(model, tokenizer, beam_size: int = 3, prompt=None, embed=None,
         # looking every 4th step (and on the last) returns the same texts, lengths and scores while the host runs ahead
         if ((step & 3) == 3 or step == entry_length - 1) and bool((beams.stopped | beams.last_token().eq(stop_token)).all()):
             break
-    return _beam_outputs(tokenizer, beams.tokens, beams.lengths, beams.total, return_tokens)
+    return finish(prefix, tokens, beams.tokens, beams.lengths, beams.total)
 
 
 class _Beams:
@@ -124,13 +181,16 @@ def _beam_outputs(tokenizer, tokens, seq_lengths, scores, return_tokens: bool):
 
 @torch.no_grad()
 def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_count: int = 1, entry_length: int = 67,
-              top_p: float = 0.8, temperature: float = 1.0, stop_token: int = 102, return_tokens: bool = False):
+              top_p: float = 0.8, temperature: float = 1.0, stop_token: int = 102, return_tokens: bool = False,
+              return_attention: bool = False, attention_layer: int = -1):
     """Nucleus-filtered greedy decoding (test.py:443-514): tokens outside the top-p mass are removed, the arg-max of the
-    rest is taken.  As in the reference's live code the sequence always starts from `embed` (test.py:472)."""
+    rest is taken.  As in the reference's live code the sequence always starts from `embed` (test.py:472).
+    return_attention appends a one-element list: the rows [H, n, S0 + n - 1] of the n tokens emitted (by the last entry)."""
     model.eval()
     device = next(model.parameters()).device
     generated_list: List[str] = []
     out_tokens: Optional[torch.Tensor] = tokens
+    replay = None                                                        # (start embeddings, emitted tokens) of the last entry
     for _ in range(entry_count):
         if embed is None:
             if out_tokens is None:
@@ -146,12 +206,14 @@ def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_coun
             new_tokens, _, _ = model.beam_search_native(step_in, 1, entry_length, temperature, stop_token,
                                                         prompt_tokens=prev if embed is None else None)
             # (from a prompt the kernel's token row starts with the prompt; from `embed` the running token list is kept in front)
+            replay = (step_in, new_tokens[0, prev.shape[1]:] if embed is None else new_tokens[0])
             out_tokens = new_tokens if embed is None or prev is None else torch.cat((prev.to(new_tokens.device), new_tokens), dim=1)
             generated_list.append(tokenizer.decode(list(out_tokens.squeeze(0).cpu().numpy())))
             continue
         # host-side loop (stacks the persistent kernel does not cover, CPU stubs): the same observation makes the sort / cumulative
         # sum of the nucleus filter unnecessary for the arg-max - one KV-cached step and one arg-max per position
         cache = None
+        start, n_before = step_in, 0 if out_tokens is None else out_tokens.shape[1]
         for _ in range(entry_length):
             logits, cache = _step_logits(model, step_in, cache)
             pick = logits.argmax(dim=-1, keepdim=True)                  # [1, 1]; the temperature does not move an arg-max
@@ -159,10 +221,14 @@ def generate2(model, tokenizer, tokens=None, prompt=None, embed=None, entry_coun
             if int(pick) == stop_token:
                 break
             step_in = model.gpt.transformer.wte(pick)
+        if out_tokens is not None:
+            replay = (start, out_tokens[0, n_before:])
         generated_list.append(tokenizer.decode(list(out_tokens.squeeze(0).cpu().numpy())))
-    if return_tokens:
-        return generated_list[0], out_tokens
-    return generated_list[0]
+    out = (generated_list[0], out_tokens) if return_tokens else generated_list[0]
+    if not return_attention:
+        return out
+    att = _replay_attention(model, [replay[0][0]], [replay[1]], attention_layer)
+    return (*out, att) if return_tokens else (out, att)
 
 
 def _check_embeds(embeds) -> None:
@@ -178,12 +244,14 @@ def _batch_native(model, beam_size: int, embeds, entry_length: int) -> bool:
 
 @torch.no_grad()
 def generate_beam_batch(model, tokenizer, embeds, beam_size: int = 3, entry_length: int = 100, temperature: float = 0.5,
-                        stop_token: int = 102, return_tokens: bool = False):
+                        stop_token: int = 102, return_tokens: bool = False, return_attention: bool = False,
+                        attention_layer: int = -1):
     """generate_beam for N prefixes at once: embeds [N, S, D] (every caption the same S).  Returns a list of N lists of
     texts, list i best-first and equal to generate_beam(model, tokenizer, embed=embeds[i:i+1], ...); with return_tokens also
     the N per-caption (tokens [beams, n], lengths, scores) that generate_beam returns.  All captions of a launch run in one
     batched persistent kernel (ClipCaptionModel.beam_search_native_batch); where that kernel does not apply, the captions
-    go one by one through generate_beam."""
+    go one by one through generate_beam.  return_attention appends, per caption, generate_beam's list of per-beam rows
+    (all N x beams sequences replayed in one forward)."""
     _check_embeds(embeds)
     model.eval()
     N = embeds.shape[0]
@@ -191,22 +259,34 @@ def generate_beam_batch(model, tokenizer, embeds, beam_size: int = 3, entry_leng
         outs = [generate_beam(model, tokenizer, beam_size=beam_size, embed=embeds[i:i + 1], entry_length=entry_length,
                               temperature=temperature, stop_token=stop_token, return_tokens=True) for i in range(N)]
         texts = [o[0] for o in outs]
-        return (texts, [tuple(o[1:]) for o in outs]) if return_tokens else texts
-    tokens, lengths, scores, n_sel = model.beam_search_native_batch(embeds, beam_size, entry_length, temperature, stop_token)
-    texts, per = [], []
-    for i in range(N):
-        t, tk, ln, sc = _beam_outputs(tokenizer, tokens[i, :, :int(n_sel[i])], lengths[i], scores[i], True)
-        texts.append(t)
-        per.append((tk, ln, sc))
-    return (texts, per) if return_tokens else texts
+        per = [tuple(o[1:]) for o in outs]
+    else:
+        tokens, lengths, scores, n_sel = model.beam_search_native_batch(embeds, beam_size, entry_length, temperature, stop_token)
+        texts, per = [], []
+        for i in range(N):
+            t, tk, ln, sc = _beam_outputs(tokenizer, tokens[i, :, :int(n_sel[i])], lengths[i], scores[i], True)
+            texts.append(t)
+            per.append((tk, ln, sc))
+    out = (texts, per) if return_tokens else texts
+    if not return_attention:
+        return out
+    gen = [_beam_rows(tk, ln, 0) for tk, ln, _ in per]
+    flat = _replay_attention(model, [embeds[i] for i, g in enumerate(gen) for _ in g], [r for g in gen for r in g], attention_layer)
+    att, at = [], 0
+    for g in gen:
+        att.append(flat[at:at + len(g)])
+        at += len(g)
+    return (*out, att) if return_tokens else (out, att)
 
 
 @torch.no_grad()
 def generate2_batch(model, tokenizer, embeds, entry_length: int = 67, top_p: float = 0.8, temperature: float = 1.0,
-                    stop_token: int = 102, return_tokens: bool = False):
+                    stop_token: int = 102, return_tokens: bool = False, return_attention: bool = False,
+                    attention_layer: int = -1):
     """generate2 for N prefixes at once (embeds [N, S, D]): a list of N strings, string i equal to
     generate2(model, tokenizer, embed=embeds[i:i+1], ...); with return_tokens also the N token rows [1, n].  The greedy
-    search is the one-beam batched kernel, for the reason given in generate2's native branch."""
+    search is the one-beam batched kernel, for the reason given in generate2's native branch.  return_attention appends,
+    per caption, generate2's one-element list of rows (all N sequences replayed in one forward)."""
     _check_embeds(embeds)
     model.eval()
     N = embeds.shape[0]
@@ -214,8 +294,13 @@ def generate2_batch(model, tokenizer, embeds, entry_length: int = 67, top_p: flo
         outs = [generate2(model, tokenizer, embed=embeds[i:i + 1], entry_length=entry_length, top_p=top_p, temperature=temperature,
                           stop_token=stop_token, return_tokens=True) for i in range(N)]
         texts = [o[0] for o in outs]
-        return (texts, [o[1] for o in outs]) if return_tokens else texts
-    tokens, _, _, n_sel = model.beam_search_native_batch(embeds, 1, entry_length, temperature, stop_token)
-    rows = [tokens[i, :, :int(n_sel[i])] for i in range(N)]
-    texts = [tokenizer.decode(list(r.squeeze(0).cpu().numpy())) for r in rows]
-    return (texts, rows) if return_tokens else texts
+        rows = [o[1] for o in outs]
+    else:
+        tokens, _, _, n_sel = model.beam_search_native_batch(embeds, 1, entry_length, temperature, stop_token)
+        rows = [tokens[i, :, :int(n_sel[i])] for i in range(N)]
+        texts = [tokenizer.decode(list(r.squeeze(0).cpu().numpy())) for r in rows]
+    out = (texts, rows) if return_tokens else texts
+    if not return_attention:
+        return out
+    att = [[a] for a in _replay_attention(model, [embeds[i] for i in range(N)], [r[0] for r in rows], attention_layer)]
+    return (*out, att) if return_tokens else (out, att)

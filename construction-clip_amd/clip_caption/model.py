@@ -246,11 +246,13 @@ class GPT2LMHeadModel(_Holder):
         return m
 
     def forward(self, inputs_embeds=None, attention_mask=None, labels=None, input_ids=None, past_key_values=None,
-                use_cache: bool = False, **kw):
+                use_cache: bool = False, output_attentions: bool = False, **kw):
         """`.logits` of GPT2LMHeadModel(inputs_embeds=..., attention_mask=...).  With use_cache / past_key_values (a
         KVCache) only the NEW positions are computed: prefill of a whole prefix when past_key_values is None, one
         token per sequence afterwards (what HF's own use_cache does; the reference's generate loops never pass it and
-        recompute the full sequence every step, test.py:381)."""
+        recompute the full sequence every step, test.py:381).
+        output_attentions=True (test.py:381) adds `.attentions`: a tuple of n_layer fp32 tensors [B, n_head, S, S], HF's
+        shape, so `outputs.attentions[-1][:, -1, -1, :]` (test.py:383) reads the newest position's row of the last head."""
         if self._owner is None:
             raise RuntimeError("GPT2LMHeadModel must be used as ClipCaptionModel.model")
         if labels is not None:
@@ -258,10 +260,16 @@ class GPT2LMHeadModel(_Holder):
         if inputs_embeds is None:
             inputs_embeds = self.transformer.wte(input_ids)
         if use_cache or past_key_values is not None:
+            if output_attentions:
+                raise NotImplementedError("output_attentions with a KV cache: a cached step never forms the full rows; run the "
+                                          "sequence without use_cache, or ask generate_* for return_attention")
             if attention_mask is not None:
                 raise NotImplementedError("KV-cached decode: no key padding (the generate loops pass none)")
             logits, cache = self._owner()._cached_logits(inputs_embeds, past_key_values)
             return SimpleNamespace(logits=logits, past_key_values=cache)
+        if output_attentions:
+            logits, att = self._owner()._logits_and_attentions(inputs_embeds, attention_mask, None, None, True)
+            return SimpleNamespace(logits=logits, attentions=tuple(att.unbind(0)))
         return SimpleNamespace(logits=self._owner()._logits_from_embeds(inputs_embeds, attention_mask))
 
 
@@ -582,6 +590,67 @@ class ClipCaptionModel(nn.Module):
         xo = self._hidden_forward(x, B, S, attention_mask, None)
         rows = torch.arange(B * S, device=x.device, dtype=torch.int32)
         return self._lm_rows(xo, rows, False)[0].unflatten(0, (B, S))
+
+    def _logits_and_attentions(self, inputs_embeds: torch.Tensor, attention_mask, layers, q_rows, want_logits: bool):
+        """The pass of _logits_from_embeds with a tap on the requested layers: while layer l's packed q / k rows are live, one
+        ops.attention_probs launch writes its probabilities.  Returns (logits or None, fp32 [len(layers), B, H, n_q, S])."""
+        if torch.is_grad_enabled() and inputs_embeds.requires_grad:
+            raise NotImplementedError("attention maps are inference only: detach the embeddings (or use torch.no_grad())")
+        self._ensure_runtime()
+        self._arena.refresh_shadows()
+        g = self.model.geo
+        B, S, D = inputs_embeds.shape
+        dev = inputs_embeds.device
+        if S > ops.ATTENTION_PROBS_MAX_T:
+            raise NotImplementedError(f"attention maps: sequence of {S} positions above the kernel's limit of "
+                                      f"{ops.ATTENTION_PROBS_MAX_T}")
+        L, H = g.n_layer, g.n_head
+        layers = list(range(L)) if layers is None else [int(l) for l in layers]
+        if not layers or any(not -L <= l < L for l in layers):
+            raise IndexError(f"layers {layers} out of range for {L} layers")
+        slot = {}
+        for i, l in enumerate(layers):
+            slot.setdefault(l % L, []).append(i)
+        rows = None
+        n_q = S
+        if q_rows is not None:
+            pos = [int(r) for r in (q_rows.tolist() if isinstance(q_rows, torch.Tensor) else q_rows)]
+            if not pos or any(not -S <= r < S for r in pos):
+                raise IndexError(f"q_rows {pos} out of range for {S} positions")
+            rows = torch.tensor([r % S for r in pos], dtype=torch.int32).to(dev)
+            n_q = len(pos)
+        out = torch.empty(len(layers), B, H, n_q, S, device=dev, dtype=torch.float32)
+        causal = self._stack.geo.causal
+
+        def probe(l, q, k, key_keep):
+            idx = slot.get(l)
+            if idx:
+                ops.attention_probs(q, k, out[idx[0]], B=B, T=S, H=H, causal=causal, key_keep=key_keep, q_rows=rows)
+                for i in idx[1:]:                                           # a layer named twice
+                    out[i].copy_(out[idx[0]])
+
+        with torch.no_grad():
+            x = torch.empty(B * S, D, device=dev, dtype=torch.float32)
+            ops.add_positional(inputs_embeds.detach().float().contiguous().view(B * S, D),
+                               self._arena.params["model.transformer.wpe.weight"].data, x, rows=B * S, S=S)
+            keep = None
+            if attention_mask is not None:
+                keep = attention_mask.detach().to(torch.float32).contiguous()
+                assert keep.shape == (B, S), f"attention_mask {tuple(attention_mask.shape)} vs sequence {(B, S)}"
+            xo = self._stack.forward(x, B, key_keep=keep, T=S, attn_probe=probe)
+            logits = None
+            if want_logits:
+                logits = self._lm_rows(xo, torch.arange(B * S, device=dev, dtype=torch.int32), False)[0].unflatten(0, (B, S))
+        return logits, out
+
+    def attention_probs(self, inputs_embeds: torch.Tensor, attention_mask=None, layers=None, q_rows=None) -> torch.Tensor:
+        """GPT-2's attention probabilities for `inputs_embeds` [B, S, D] (S <= 256): fp32 [len(layers), B, n_head, n_q, S], what
+        HF returns as `.attentions` under output_attentions=True.  layers: layer indices (negative ones count from the top),
+        None = all; q_rows: query positions (a sequence of ints, negative ones count from the end), None = all S.  Entry
+        [.., i, j] is the weight query position q_rows[i] puts on key j: 0 for j above it and for masked keys.
+        One forward of the stack and one probability launch per requested layer; inference only - no gradient slot, `.grad`
+        or KV cache is touched."""
+        return self._logits_and_attentions(inputs_embeds, attention_mask, layers, q_rows, False)[1]
 
     def _cached_logits(self, inputs_embeds: torch.Tensor, cache: Optional[KVCache]):
         """(logits [B, S_new, V], cache) for the new positions `inputs_embeds` [B, S_new, D] appended after cache.length."""

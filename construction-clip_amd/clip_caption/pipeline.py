@@ -22,7 +22,7 @@ import torch
 from cclip_hip import ops
 
 from .data import CAPTION_TYPES, VIOLATION_TYPES
-from .generate import _beam_outputs, generate2_batch, generate_beam_batch
+from .generate import _beam_outputs, _beam_rows, _replay_attention, generate2_batch, generate_beam_batch
 
 
 def attribute_strings(caption_labels: Sequence[str], violation_labels: Sequence[str]) -> List[str]:
@@ -48,10 +48,22 @@ def build_attribute_table(tokenizer, caption_labels: Sequence[str], violation_la
 class PendingCaptions:
     """What Captioner.submit returns: the device work is enqueued; result() reads it back and decodes the text."""
 
-    def __init__(self, cap: "Captioner", n: int, probs, index, ids, greedy: bool, pending=None, eager=None):
+    def __init__(self, cap: "Captioner", n: int, probs, index, ids, greedy: bool, pending=None, eager=None, proj=None):
         self._cap, self._n, self._probs, self._index, self._ids = cap, n, probs, index, ids
         self._greedy, self._pending, self._eager = greedy, pending, eager
+        self._proj = proj                                                 # the projected prefixes, kept for return_attention
         self._done = None
+
+    def _attention(self, per):
+        """the best beam's rows [H, n, S0 + n - 1] of the last layer for every image: one replay forward for all of them"""
+        cap = self._cap
+        model = cap.caption_model
+        emb = torch.cat((self._proj.view(self._n, cap.prefix_length, -1), model.gpt.transformer.wte(self._ids.long())), dim=1)
+        if self._greedy:
+            gen = [rows[0] for rows in per]
+        else:                                                              # scores are length-normalised: _beam_outputs' order
+            gen = [_beam_rows(tk, ln, 0)[int(sc.argsort(descending=True)[0])] for tk, ln, sc in per]
+        return _replay_attention(model, [emb[i] for i in range(self._n)], gen, -1)
 
     def result(self, return_tokens: bool = False):
         if self._done is None:
@@ -79,6 +91,9 @@ class PendingCaptions:
                 records.append({"caption_type": cap.caption_labels[c], "violation_type": cap.violation_labels[v],
                                 "attribute": cap.attributes[c * len(cap.violation_labels) + v], "prediction": texts[i],
                                 "type_probs": probs[i, :k0].tolist(), "violation_probs": probs[i, k0:].tolist()})
+            if self._proj is not None:
+                for rec, att in zip(records, self._attention(per)):
+                    rec["attention"] = att
             self._done = (records, {"ids": ids, "index": index, "tokens": per})
         return self._done if return_tokens else self._done[0]
 
@@ -154,11 +169,13 @@ class Captioner:
 
     @torch.no_grad()
     def submit(self, images: torch.Tensor, beam_size: int = 3, entry_length: int = 100, temperature: float = 0.5,
-               stop_token: int = 102, greedy: bool = False, top_p: float = 0.8) -> PendingCaptions:
+               stop_token: int = 102, greedy: bool = False, top_p: float = 0.8, return_attention: bool = False) -> PendingCaptions:
         """Enqueue the whole device stage for preprocessed images [N, 3, R, R] - encode_image, the zero-shot heads and attribute
         ids, clip_project, the decoder's input rows, the prefills and the batched beam launches - and return without waiting
         for the device; `.result()` reads back and decodes.  Where the batched kernel does not apply
-        (ClipCaptionModel.beam_batch_native_ok) the work is done here, through generate_beam_batch / generate2_batch."""
+        (ClipCaptionModel.beam_batch_native_ok) the work is done here, through generate_beam_batch / generate2_batch.
+        return_attention: every record of `.result()` also gets "attention", the best beam's last-layer rows
+        [H, n, S0 + n - 1] on the device (S0 = prefix_length + attribute_length; generate_beam's return_attention)."""
         model = self.caption_model
         images = self._images(images)
         N = images.shape[0]
@@ -180,7 +197,7 @@ class Captioner:
                 ops.caption_embed(proj, ids, tr.wte.weight.data, tr.wpe.weight.data, x, B=N, P=P, Lt=A)
                 pending = model.beam_batch_enqueue(x.view(N, P + A, D), beams, entry_length, temperature, stop_token,
                                                    positions_added=True)
-                return PendingCaptions(self, N, probs, index, ids, greedy, pending=pending)
+                return PendingCaptions(self, N, probs, index, ids, greedy, pending=pending, proj=proj if return_attention else None)
             emb = torch.cat((proj.view(N, P, -1), model.gpt.transformer.wte(ids.long())), dim=1)      # test.py:540-542
             if greedy:
                 eager = generate2_batch(model, self.tokenizer, emb, entry_length=entry_length, top_p=top_p, temperature=temperature,
@@ -189,21 +206,21 @@ class Captioner:
                 texts, per = generate_beam_batch(model, self.tokenizer, emb, beam_size=beam_size, entry_length=entry_length,
                                                  temperature=temperature, stop_token=stop_token, return_tokens=True)
                 eager = ([t[0] for t in texts], per)
-            return PendingCaptions(self, N, probs, index, ids, greedy, eager=eager)
+            return PendingCaptions(self, N, probs, index, ids, greedy, eager=eager, proj=proj if return_attention else None)
         finally:
             if was_training is not None and model.training != was_training:   # (generate_* switch the model to eval)
                 model.train(was_training)
 
     def describe(self, images, beam_size: int = 3, entry_length: int = 100, temperature: float = 0.5, stop_token: int = 102,
-                 greedy: bool = False, top_p: float = 0.8, return_tokens: bool = False):
+                 greedy: bool = False, top_p: float = 0.8, return_tokens: bool = False, return_attention: bool = False):
         """The records of `images` (a preprocessed float tensor [N, 3, R, R], or a sequence of PIL images / uint8 HWC arrays).
         More images than one batched launch holds (64 // beams) go in chunks of that size; the next chunk is enqueued before
         the previous one is read back.  return_tokens: also {"ids" [N, A], "index" [N, 2], "tokens": per caption what
-        generate_beam_batch (generate2_batch with greedy) returns with return_tokens}."""
+        generate_beam_batch (generate2_batch with greedy) returns with return_tokens}.  return_attention: as for submit."""
         images = self._images(images)
         per = max(1, ops.BEAM_BATCH_MAX_ROWS // (1 if greedy else max(1, beam_size)))
         kw = dict(beam_size=beam_size, entry_length=entry_length, temperature=temperature, stop_token=stop_token, greedy=greedy,
-                  top_p=top_p)
+                  top_p=top_p, return_attention=return_attention)
         records, extras, prev = [], [], None
         for s in range(0, images.shape[0], per):
             nxt = self.submit(images[s:s + per], **kw)

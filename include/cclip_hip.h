@@ -180,6 +180,16 @@ int cclip_attention_bwd(const cclip_attn_desc* d, hipStream_t stream);
  * as for the backward).  R: fp32 [B, T, T], updated in place.  grad_scale > 0: the loss scale the dgrad chain runs under.
  * Neither P nor dP is written anywhere. */
 int cclip_attention_relevance(const cclip_attn_desc* d, float grad_scale, float* R, hipStream_t stream);
+/* Attention probabilities of one layer, T <= 256 (what HF's `output_attentions=True` returns; the reference's generate_beam
+ * logs them, CLIP_prefix_caption/test.py:381-390): P[b, h, i, 0:T] = softmax_j(scale q_t k_j + mask) in fp32 for the query
+ * position t = q_rows[i] (q_rows: optional int32 DEVICE array of n_q positions shared by all sequences, values clamped to
+ * 0 .. T-1; NULL = all T positions, n_q is then ignored).  Element (b, h, i, j) is at P[b*ld_p_b + h*ld_p_h + i*ld_p_q + j],
+ * ld_p_q >= T.  Reads q, k, ldq, ldk, B, T, H, head_dim (64), causal, scale, key_keep of d (cu_seqlens must be NULL); lse is
+ * NOT read - the row maximum and sum are formed in registers from the scores themselves.  Entries above the causal diagonal
+ * and entries of keys with key_keep == 0 are exactly 0 (a row that sees no key is all zeros); every element 0 .. T-1 of a
+ * produced row is written, nothing else is.  T > 256 returns CCLIP_ERR_ARG. */
+int cclip_attention_probs(const cclip_attn_desc* d, const int32_t* q_rows, int32_t n_q, float* P, int64_t ld_p_b,
+                          int64_t ld_p_h, int64_t ld_p_q, hipStream_t stream);
 /* Generic small attention for the reference's TransformerMapper (CLIP_prefix_caption/train.py:141-171: 8 heads of
  * 96 over 40 tokens): any head_dim <= 128 (multiple of 8), T <= 64, no mask; same descriptor; LDS must hold one
  * (batch, head): 4*T*(head_dim+2) + 2*T*(T+1) + T floats <= 160 KiB in backward. */
@@ -466,6 +476,8 @@ int cclip_layernorm_bwd_f16(const void* dy, int32_t dy_is_f16, int64_t lddy, con
 int cclip_attention_fwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_bwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_relevance_f16(const cclip_attn_desc* d, float grad_scale, float* R, hipStream_t stream);
+int cclip_attention_probs_f16(const cclip_attn_desc* d, const int32_t* q_rows, int32_t n_q, float* P, int64_t ld_p_b,
+                              int64_t ld_p_h, int64_t ld_p_q, hipStream_t stream);
 int cclip_attention_small_fwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_small_bwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_decode_f16(const void* q, int64_t ldq, const void* kcache, const void* vcache, int64_t ld_pos,

@@ -38,6 +38,9 @@ def build_parser():
     ap.add_argument("--entry_length", type=int, default=None, help="default: 100 (beam), 67 (--greedy), as the reference")
     ap.add_argument("--greedy", action="store_true", help="generate2 (nucleus-filtered greedy) instead of generate_beam")
     ap.add_argument("--half", action="store_true", help="IEEE fp16 operands for the caption model (default bf16)")
+    ap.add_argument("--attention-out", default=None, metavar="FILE.npz",
+                    help="also store, per image i, attention_<i> [H, n, S0+n-1] (the best beam's last-layer rows) and map_<i> "
+                         "(clip_caption.caption_attention_map of them: the reference's attention_map, test.py:342-349)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=9, help="--synthetic: images to describe")
     ap.add_argument("--clip_synthetic", default="test-tiny", help="--synthetic: CLIP geometry")
@@ -89,12 +92,18 @@ def main(argv=None):
     from PIL import Image
     cap, annotations, image_path, tmp = setup(args)
     log = {"caption": []}
+    arrays = {}
     entry_length = args.entry_length or (67 if args.greedy else 100)
     for i in range(0, len(annotations), args.bs):
         chunk = annotations[i:i + args.bs]
         images = [Image.open(os.path.join(image_path, a["file_name"])) for a in chunk]
-        records = cap.describe(images, beam_size=args.beam_size, entry_length=entry_length, greedy=args.greedy)
-        for a, r in zip(chunk, records):
+        records = cap.describe(images, beam_size=args.beam_size, entry_length=entry_length, greedy=args.greedy,
+                               return_attention=args.attention_out is not None)
+        for j, (a, r) in enumerate(zip(chunk, records)):
+            if args.attention_out is not None:
+                from clip_caption import caption_attention_map
+                arrays[f"attention_{i + j}"] = r["attention"].cpu().numpy()
+                arrays[f"map_{i + j}"] = caption_attention_map(r["attention"]).cpu().numpy()
             log["caption"].append({                                                        # test.py:626-633
                 "caption_type": r["caption_type"],
                 "violation_type": r["violation_type"],
@@ -110,6 +119,10 @@ def main(argv=None):
     with open(path, "w") as f:
         json.dump(log, f, indent=2, ensure_ascii=False)
     C.log_line(saved=path)
+    if args.attention_out is not None:
+        import numpy as np
+        np.savez(args.attention_out, **arrays)
+        C.log_line(saved=args.attention_out)
     return path
 
 
