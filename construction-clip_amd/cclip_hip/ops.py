@@ -662,6 +662,60 @@ def attention_probs(q, k, P, *, B: int, T: int, H: int, causal: bool = False, sc
                                              c_long(P.stride(1)), c_long(P.stride(2)), _stream()), "cclip_attention_probs")
 
 
+SIMILARITY_TOPK_MAX_K = 64
+SIMILARITY_TOPK_MAX_D = 1024
+
+
+def similarity_topk_workspace(Q: int, N: int, k: int) -> int:
+    """bytes of candidate workspace cclip_similarity_topk needs for this problem (Q * splits * k * 8)"""
+    fn = lib.cclip_similarity_topk_workspace
+    fn.restype = c_long
+    return int(fn(c_int(Q), c_long(N), c_int(k)))
+
+
+def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
+    """Exact top-k of s[i, n] = <q[i], g[n]> for every query row: q [Q, D] and g [N, D] 16-bit (same dtype), inner stride 1,
+    row strides multiples of 8 elements, 16-byte aligned.  Returns (scores fp32 [Q, k] descending, index int32 [Q, k]); equal
+    scores by the lower gallery index, NaN last.  The Q x N matrix is never formed: the only scratch is the per-split
+    candidate workspace.  1 <= k <= 64, k <= N, D % 32 == 0, D <= 1024, N < 2^31.  Enqueues two launches; no host read."""
+    for t, n in ((q, "q"), (g, "g")):
+        _req16(t, n)
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"similarity_topk: {n} must be a 2-D view with inner stride 1, got {tuple(t.shape)} / {t.stride()}")
+    Q, D = q.shape
+    N = g.shape[0]
+    if g.shape[1] != D:
+        raise ValueError(f"similarity_topk: q has {D} columns, g has {g.shape[1]}")
+    if Q < 1 or N < 1:
+        raise ValueError(f"similarity_topk: empty operand (Q = {Q}, N = {N})")
+    if not 1 <= k <= SIMILARITY_TOPK_MAX_K:
+        raise ValueError(f"similarity_topk: k = {k} outside the kernel's range 1 .. {SIMILARITY_TOPK_MAX_K}")
+    if k > N:
+        raise ValueError(f"similarity_topk: k = {k} above the gallery's {N} rows")
+    if D % 32 or D > SIMILARITY_TOPK_MAX_D:
+        raise NotImplementedError(f"similarity_topk: D = {D}; the kernel needs D % 32 == 0 and D <= {SIMILARITY_TOPK_MAX_D}")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"similarity_topk: N = {N}; the kernel's gallery index is int32 (N < 2^31)")
+    for t, n in ((q, "q"), (g, "g")):
+        if (t.shape[0] > 1 and t.stride(0) % 8) or t.data_ptr() % 16:
+            raise ValueError(f"similarity_topk: {n} must be 16-byte aligned with a row stride that is a multiple of 8 elements "
+                             f"(stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16})")
+    fn = _fn("cclip_similarity_topk", q, g)
+    if out_scores is None:
+        out_scores = torch.empty(Q, k, device=q.device, dtype=torch.float32)
+    if out_index is None:
+        out_index = torch.empty(Q, k, device=q.device, dtype=torch.int32)
+    _req(out_scores, torch.float32, "out_scores"); _req(out_index, torch.int32, "out_index")
+    assert out_scores.is_contiguous() and out_index.is_contiguous() and tuple(out_scores.shape) == (Q, k) == tuple(out_index.shape)
+    nbytes = similarity_topk_workspace(Q, N, k)
+    ws = torch.empty(nbytes // 8, device=q.device, dtype=torch.int64)
+    ldq = q.stride(0) if Q > 1 else max(D, q.stride(0) // 8 * 8)
+    ldg = g.stride(0) if N > 1 else max(D, g.stride(0) // 8 * 8)
+    check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(N), c_int(D), c_int(k), _p(out_scores), _p(out_index),
+             _p(ws), c_long(nbytes), _stream()), "cclip_similarity_topk")
+    return out_scores, out_index
+
+
 def attention_small_fwd(q, k, v, o, *, B: int, T: int, H: int, head_dim: int, lse=None, scale=None) -> None:
     """Generic-head_dim unmasked attention (TransformerMapper): same tensor conventions as attention_fwd."""
     d = _attn_desc(q, k, v, o, lse, B, T, H, False, None, scale, head_dim)

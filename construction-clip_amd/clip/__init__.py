@@ -6,3 +6,4 @@ from .model import CLIP, build_model  # noqa: F401
 from .loss import contrastive_loss, ContrastiveLoss  # noqa: F401
 from .preprocess_device import DevicePreprocess  # noqa: F401
 from .explain import interpret, image_relevance_map, text_token_scores  # noqa: F401  (attention.py:14, 88-92, 115-117)
+from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)

@@ -1,0 +1,173 @@
+"""Retrieval over stored embeddings: "which photos match this description / this photo?" and recall@k.
+
+The reference stops at the embedding pickle (CLIP_prefix_caption/parse_coco.py) and an in-batch accuracy among 8
+(CLIP/train_caption.py:124-136).  `EmbeddingIndex` keeps the L2-normalised rows on the device in the 16-bit type the towers
+compute in and answers a batch of queries with the fused similarity top-k kernel (csrc/embed_topk.hip): exact, the Q x N
+score matrix is never formed, no host read.  `retrieval_recall` is the usual image <-> text R@k on top of it.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import torch
+
+from cclip_hip import ops
+
+HALF_TYPES = (torch.bfloat16, torch.float16)
+
+
+def _device(t: Optional[torch.Tensor] = None) -> torch.device:
+    if t is not None and t.is_cuda:
+        return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def normalize_rows(features: torch.Tensor, dtype: torch.dtype, device: Optional[torch.device] = None) -> torch.Tensor:
+    """[N, E] of any float dtype, anywhere -> device rows L2-normalised in fp32 (cclip_l2norm_fwd), then rounded to `dtype`."""
+    if features.dim() != 2 or not features.is_floating_point():
+        raise ValueError(f"expected a 2-D float tensor of features, got {tuple(features.shape)} {features.dtype}")
+    if dtype not in HALF_TYPES:
+        raise ValueError(f"dtype must be torch.bfloat16 or torch.float16, got {dtype}")
+    dev = device if device is not None else _device(features)
+    x = features.detach().to(device=dev, dtype=torch.float32).contiguous()
+    N, E = x.shape
+    out = torch.empty(N, E, device=dev, dtype=dtype)
+    if N == 0:
+        return out
+    y = torch.empty_like(x)
+    inv = torch.empty(N, device=dev, dtype=torch.float32)
+    ops.l2norm_fwd(x, y, inv)
+    ops.cast_f32_to_bf16(y, out)
+    return out
+
+
+class EmbeddingIndex:
+    """Stored embeddings [N, E] on the device, searchable.  `metadata`: an optional list of N entries (the embedding pickle's
+    `captions` dicts carry `file_name`).  `dtype`: the 16-bit type of the stored rows and of the queries (default bfloat16,
+    pass `model.compute_dtype` to match a model)."""
+
+    def __init__(self, features: torch.Tensor, dtype: Optional[torch.dtype] = None, metadata: Optional[Sequence] = None):
+        self.dtype = torch.bfloat16 if dtype is None else dtype
+        rows = normalize_rows(features, self.dtype)
+        if rows.shape[1] % 32 or rows.shape[1] > ops.SIMILARITY_TOPK_MAX_D:
+            raise NotImplementedError(f"EmbeddingIndex: embedding width {rows.shape[1]}; the search kernel needs a multiple of 32 "
+                                      f"up to {ops.SIMILARITY_TOPK_MAX_D}")
+        if metadata is not None and len(metadata) != rows.shape[0]:
+            raise ValueError(f"metadata has {len(metadata)} entries for {rows.shape[0]} rows")
+        self._buf = rows                     # capacity rows; the first _n are live
+        self._n = rows.shape[0]
+        self.metadata = None if metadata is None else list(metadata)
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def dim(self) -> int:
+        return self._buf.shape[1]
+
+    @property
+    def features(self) -> torch.Tensor:
+        """The stored normalised 16-bit rows [N, E] (a view)."""
+        return self._buf[:self._n]
+
+    def add(self, features: torch.Tensor, metadata: Optional[Sequence] = None) -> "EmbeddingIndex":
+        """Append rows (amortised growth: capacity doubles).  Rows are normalised one by one, so the stored bits equal a bulk build's."""
+        if features.dim() != 2 or features.shape[1] != self.dim:
+            raise ValueError(f"add: expected [*, {self.dim}] features, got {tuple(features.shape)}")
+        if (metadata is None) != (self.metadata is None) and self._n > 0:
+            raise ValueError("add: metadata must be given for every row of the index or for none")
+        if metadata is not None and len(metadata) != features.shape[0]:
+            raise ValueError(f"add: metadata has {len(metadata)} entries for {features.shape[0]} rows")
+        rows = normalize_rows(features, self.dtype, self._buf.device)
+        need = self._n + rows.shape[0]
+        if need > self._buf.shape[0]:
+            grown = torch.empty(max(need, 2 * self._buf.shape[0]), self.dim, device=self._buf.device, dtype=self.dtype)
+            grown[:self._n].copy_(self._buf[:self._n])
+            self._buf = grown
+        self._buf[self._n:need].copy_(rows)
+        self._n = need
+        if metadata is not None:
+            self.metadata = (self.metadata or []) + list(metadata)
+        return self
+
+    @classmethod
+    def from_pickle(cls, path: str, dtype: Optional[torch.dtype] = None) -> "EmbeddingIndex":
+        """The embedding file of clip_caption.data.save_embeddings / scripts/extract_embeddings.py (parse_coco.py's layout):
+        row captions[i]["clip_embedding"] of `clip_embedding` belongs to captions[i]."""
+        from clip_caption.data import load_embeddings
+        data = load_embeddings(path)
+        emb, captions = data["clip_embedding"], data["captions"]
+        order = [int(c["clip_embedding"]) if isinstance(c, dict) and "clip_embedding" in c else i for i, c in enumerate(captions)]
+        if order != list(range(emb.shape[0])):
+            emb = emb[torch.tensor(order, dtype=torch.long)]
+        return cls(emb, dtype=dtype, metadata=captions)
+
+    @torch.no_grad()
+    def search(self, queries: torch.Tensor, k: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
+        """queries [Q, E] (any float dtype, anywhere) -> (scores fp32 [Q, k] descending, indices int64 [Q, k]) on the device:
+        cosine similarity of the normalised 16-bit rows, equal scores by the lower index."""
+        if self._n == 0:
+            raise ValueError("search: the index is empty")
+        if queries.dim() == 1:
+            queries = queries[None]
+        if queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"search: expected [*, {self.dim}] queries, got {tuple(queries.shape)}")
+        q = normalize_rows(queries, self.dtype, self._buf.device)
+        scores, index = ops.similarity_topk(q, self.features, int(k))
+        return scores, index.long()
+
+    @torch.no_grad()
+    def search_text(self, model, tokens: torch.Tensor, k: int = 10):
+        return self.search(model.encode_text(tokens.to(self._buf.device)), k)
+
+    @torch.no_grad()
+    def search_image(self, model, images: torch.Tensor, k: int = 10):
+        return self.search(model.encode_image(images.to(self._buf.device)), k)
+
+
+def recall_from_indices(indices: torch.Tensor, query_labels: torch.Tensor, gallery_labels: torch.Tensor,
+                        ks: Sequence[int]) -> torch.Tensor:
+    """The hit rule: indices [Q, K] (best first) -> for each k in ks the share of queries with a gallery item of the query's
+    label among their first k hits.  A [len(ks)] float64 tensor on indices' device; no host read."""
+    Q, K = indices.shape
+    if query_labels.shape != (Q,):
+        raise ValueError(f"query_labels: expected [{Q}], got {tuple(query_labels.shape)}")
+    if gallery_labels.dim() != 1:
+        raise ValueError(f"gallery_labels: expected one label per gallery row, got {tuple(gallery_labels.shape)}")
+    ks = [int(k) for k in ks]
+    if not ks or min(ks) < 1 or max(ks) > K:
+        raise ValueError(f"ks = {ks} must lie in 1 .. {K}")
+    dev = indices.device
+    hit = gallery_labels.to(dev)[indices.long()] == query_labels.to(dev)[:, None]          # [Q, K]
+    first = torch.where(hit.any(dim=1), hit.to(torch.int64).argmax(dim=1), torch.full((Q,), K, device=dev, dtype=torch.int64))
+    kk = torch.tensor(ks, device=dev, dtype=torch.int64)
+    return (first[None, :] < kk[:, None]).to(torch.float64).mean(dim=1)
+
+
+@torch.no_grad()
+def retrieval_recall(query_features: torch.Tensor, gallery_features: torch.Tensor, ks: Sequence[int] = (1, 5, 10),
+                     query_labels: Optional[torch.Tensor] = None, gallery_labels: Optional[torch.Tensor] = None,
+                     dtype: Optional[torch.dtype] = None) -> Dict[int, float]:
+    """Recall@k of retrieving `gallery_features` rows with `query_features` rows: the share of queries whose top k holds a
+    gallery item with the query's label.  Default labels pair query i with gallery row i (needs Q == N); pass labels when
+    several gallery rows answer one query (the reference's data repeats `violation_list` strings).  One search at max(ks),
+    the hit test on the device, one read-back of len(ks) numbers.  Every k must be <= min(64, N)."""
+    Q, N = query_features.shape[0], gallery_features.shape[0]
+    if (query_labels is None) != (gallery_labels is None):
+        raise ValueError("retrieval_recall: give both query_labels and gallery_labels, or neither")
+    if query_labels is None:
+        if Q != N:
+            raise ValueError(f"retrieval_recall: without labels query i pairs with gallery row i, but Q = {Q} and N = {N}")
+        query_labels = torch.arange(Q)
+        gallery_labels = torch.arange(N)
+    ks = [int(k) for k in ks]
+    if not ks or min(ks) < 1 or max(ks) > min(N, ops.SIMILARITY_TOPK_MAX_K):
+        raise ValueError(f"retrieval_recall: ks = {ks} must lie in 1 .. min(N, {ops.SIMILARITY_TOPK_MAX_K}) = "
+                         f"{min(N, ops.SIMILARITY_TOPK_MAX_K)}")
+    if tuple(gallery_labels.shape) != (N,) or tuple(query_labels.shape) != (Q,):
+        raise ValueError(f"retrieval_recall: labels must be [{Q}] and [{N}], got {tuple(query_labels.shape)} and "
+                         f"{tuple(gallery_labels.shape)}")
+    index = EmbeddingIndex(gallery_features, dtype=dtype)
+    _, idx = index.search(query_features, max(ks))
+    r = recall_from_indices(idx, query_labels, gallery_labels, ks).tolist()
+    return {k: v for k, v in zip(ks, r)}

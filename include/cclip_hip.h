@@ -279,6 +279,24 @@ int cclip_caption_prompt(const float* feat, int64_t ldf, int32_t N, int32_t E, c
                          const int32_t* head_start, int32_t G, const float* logit_scale_dev, const int32_t* table,
                          int32_t table_rows, int32_t A, float* probs, int32_t* index, int32_t* ids, hipStream_t stream);
 
+/* ---- exact top-k retrieval over stored embeddings (csrc/embed_topk.hip) ---------------------------------------
+ * For queries q [Q, D] and a gallery g [N, D], both bf16 (fp16 in the twin) with row strides ldq / ldg in elements, the
+ * k largest s[i, n] = sum_d q[i, d] g[n, d] of every query, fp32 accumulation on the MFMA:
+ *   scores[i, j]  fp32 [Q, k] contiguous, descending          index[i, j]  int32 [Q, k]: the gallery row of scores[i, j]
+ * Exact, not approximate, and the Q x N matrix is never written.  Order: higher score first; equal fp32 scores (-0 == +0)
+ * by the LOWER gallery index; a NaN score ranks below every number.  A pair's score does not depend on where the gallery
+ * row sits (identical gallery rows give bitwise identical scores), and there are no atomics: the result does not depend
+ * on how the launcher splits the gallery, and two launches are bitwise equal.
+ * Two launches on `stream`: per-split selection into `workspace`, then the merge.  workspace: at least
+ * cclip_similarity_topk_workspace(Q, N, k) bytes (0 for arguments the call would refuse), 8-byte aligned, device memory
+ * the caller owns; its contents before and after are meaningless.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): a null pointer; Q <= 0; N <= 0 or N >= 2^31; k < 1, k > 64 or k > N; D <= 0, D % 32
+ * or D > 1024; ldq or ldg below D or not a multiple of 8; q or g not 16-byte aligned; workspace too small or misaligned. */
+int64_t cclip_similarity_topk_workspace(int32_t Q, int64_t N, int32_t k);
+int cclip_similarity_topk(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                          int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
+                          hipStream_t stream);
+
 /* ---- loss side (fp32) ------------------------------------------------------------------------
  * cclip_l2norm_fwd/bwd: y = x / ||x||_2 per row (image_features / image_features.norm(dim=1)).
  * cclip_xent_rows: per row r with label labels[r]: loss_row = logsumexp(row) - row[label]
@@ -505,6 +523,9 @@ int cclip_adamw_step_f16(float* param, const float* grad, float* exp_avg, float*
                          int32_t correct_bias, float grad_scale, int32_t mode, void* f16_shadow,
                          hipStream_t stream);
 int cclip_cast_f32_to_f16(const float* in, void* out, int64_t n, hipStream_t stream);
+int cclip_similarity_topk_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                              int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
+                              hipStream_t stream);
 
 #ifdef __cplusplus
 }
