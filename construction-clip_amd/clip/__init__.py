@@ -3,7 +3,7 @@ executing on MI355X through libcclip_hip.so.  See clip.py / model.py."""
 from .clip import available_models, load, tokenize, _transform  # noqa: F401
 from . import simple_tokenizer  # noqa: F401  (attention.py:114 uses clip.simple_tokenizer.SimpleTokenizer)
 from .model import CLIP, build_model  # noqa: F401
-from .loss import contrastive_loss, ContrastiveLoss  # noqa: F401
+from .loss import contrastive_loss, ContrastiveLoss, class_ids, unique_texts  # noqa: F401
 from .preprocess_device import DevicePreprocess  # noqa: F401
 from .explain import interpret, image_relevance_map, text_token_scores  # noqa: F401  (attention.py:14, 88-92, 115-117)
 from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)

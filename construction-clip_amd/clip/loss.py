@@ -11,6 +11,11 @@ every rank forms its row blocks  L_i = s I_loc T_all^T  and  L_t = s T_loc I_all
 and the cross-rank part of the feature gradient comes back through ONE reduce-scatter.  The
 result equals the single-GPU loss at N = world * N_loc (tests/test_dp_gloo.py).
 
+With `labels=` the loss is class-aware (the reference keeps every batch to distinct classes by construction; a large batch
+of this data cannot): the positives of a row are all columns of its class, the row kernel is ops.xent_rows_classes, and the
+text side may be the U distinct texts of the batch (`unique_texts`), a rectangular [N, U] problem.  `class_ids` numbers equal
+token rows equally across ranks for the data-parallel (square) form.
+
 All arithmetic goes through cclip_hip.ops (HIP kernels); torch.distributed only moves bytes.
 """
 from __future__ import annotations
@@ -112,12 +117,159 @@ class _Contrastive(torch.autograd.Function):
         return dfi, dft, dscale.reshape(()), None
 
 
+class _ContrastiveClasses(torch.autograd.Function):
+    """The class-aware form: row i of the image side carries class a_i, row j of the text side class b_j, and the positives of
+    a row are the columns of its class (uniform soft targets, both directions; DESIGN.md 'Class-aware contrastive loss').
+    Single process: I [N,E] against T [M,E], M free.  Data parallel: the square form (text j carries a_j), with the choreography
+    of _Contrastive plus ONE all-gather of the int32 class vector."""
+
+    @staticmethod
+    def forward(ctx, fi, ft, logit_scale, group, a_loc, b_loc):
+        dp = _collectives(group)
+        world = _world(group)[1] if dp else 1
+        dev = fi.device
+        fi, ft = fi.contiguous().float(), ft.contiguous().float()
+        ls = logit_scale.detach().float().reshape(1).contiguous()
+        nloc, E = fi.shape
+        mloc = ft.shape[0]
+        N, M = nloc * world, mloc * world
+        need_grad = any(ctx.needs_input_grad[:3])
+
+        inv_i = torch.empty(nloc, device=dev, dtype=torch.float32)
+        inv_t = torch.empty(mloc, device=dev, dtype=torch.float32)
+        if dp:                                                                   # square: one packed buffer, as _Contrastive
+            packed = torch.empty(nloc, 2 * E, device=dev, dtype=torch.float32)  # [ In | Tn ]
+            i_n, t_n = packed[:, :E], packed[:, E:]
+        else:
+            i_n = torch.empty(nloc, E, device=dev, dtype=torch.float32)
+            t_n = torch.empty(mloc, E, device=dev, dtype=torch.float32)
+        ops.l2norm_fwd(fi, i_n, inv_i)
+        ops.l2norm_fwd(ft, t_n, inv_t)
+        if dp:
+            gathered = torch.empty(N, 2 * E, device=dev, dtype=torch.float32)
+            dist.all_gather_into_tensor(gathered, packed, group=group)
+            i_all, t_all = gathered[:, :E], gathered[:, E:]
+            a_all = torch.empty(N, device=dev, dtype=torch.int32)
+            dist.all_gather_into_tensor(a_all, a_loc, group=group)
+            b_all = a_all
+        else:
+            i_all, t_all, a_all, b_all = i_n, t_n, a_loc, b_loc
+
+        L_i = torch.empty(nloc, M, device=dev, dtype=torch.float32)
+        L_t = torch.empty(mloc, N, device=dev, dtype=torch.float32)
+        ops.gemm_f32(i_n, t_all, L_i, alpha_log_dev=ls)
+        ops.gemm_f32(t_n, i_all, L_t, alpha_log_dev=ls)
+        loss_rows = torch.empty(nloc + mloc, device=dev, dtype=torch.float32)
+        rowdot = torch.empty(nloc + mloc, device=dev, dtype=torch.float32) if need_grad else None
+        hit = torch.empty(nloc, device=dev, dtype=torch.float32)
+        gs_i, gs_t = 1.0 / (2.0 * N), 1.0 / (2.0 * M)                            # fixed GLOBAL denominators: host constants
+        # gradients of the GLOBAL mean loss overwrite the logits in place (nothing else needs them)
+        ops.xent_rows_classes(L_i, a_loc, b_all, loss_row=loss_rows[:nloc], hit=hit, dlogits=L_i if need_grad else None,
+                              grad_scale=gs_i, rowdot=rowdot[:nloc] if need_grad else None)
+        ops.xent_rows_classes(L_t, b_loc, a_all, loss_row=loss_rows[nloc:], dlogits=L_t if need_grad else None,
+                              grad_scale=gs_t, rowdot=rowdot[nloc:] if need_grad else None)
+        out = torch.empty(2, device=dev, dtype=torch.float32)                    # [loss, #correct by class]
+        ops.reduce_dot(loss_rows[:nloc], None, out[0:1], alpha=gs_i)
+        ops.reduce_dot(loss_rows[nloc:], None, out[0:1], alpha=gs_t, accumulate=True)
+        ops.reduce_dot(hit, None, out[1:2])
+        if dp:
+            dist.all_reduce(out, group=group)
+        if need_grad:
+            # d/d(normalised features): local rows + the other ranks' rows that used our features
+            if dp:
+                cross = torch.empty(N, 2 * E, device=dev, dtype=torch.float32)
+                cross_i, cross_t = cross[:, :E], cross[:, E:]
+            else:
+                cross_i = torch.empty(N, E, device=dev, dtype=torch.float32)
+                cross_t = torch.empty(M, E, device=dev, dtype=torch.float32)
+            ops.gemm_f32(L_t.t(), t_n.t(), cross_i, alpha_log_dev=ls)            # -> d I_all = s dL_t^T T_loc
+            ops.gemm_f32(L_i.t(), i_n.t(), cross_t, alpha_log_dev=ls)            # -> d T_all = s dL_i^T I_loc
+            if dp:
+                d = torch.empty(nloc, 2 * E, device=dev, dtype=torch.float32)
+                dist.reduce_scatter_tensor(d, cross, group=group)
+                d_i, d_t = d[:, :E], d[:, E:]
+            else:
+                d_i, d_t = cross_i, cross_t
+            ops.gemm_f32(L_i, t_all.t(), d_i, alpha_log_dev=ls, beta=1.0)        # += s dL_i T_all
+            ops.gemm_f32(L_t, i_all.t(), d_t, alpha_log_dev=ls, beta=1.0)        # += s dL_t I_all
+            ctx.saved = (d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot)
+        ctx.mark_non_differentiable(out)
+        loss = out[0].clone()
+        ctx.stats = out
+        return loss, out
+
+    @staticmethod
+    def backward(ctx, dloss, _dout):
+        d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot = ctx.saved
+        g = dloss.detach().float().reshape(1).contiguous()
+        dfi = torch.empty(i_n.shape, device=i_n.device, dtype=torch.float32)
+        dft = torch.empty(t_n.shape, device=i_n.device, dtype=torch.float32)
+        ops.l2norm_bwd(d_i, i_n, inv_i, dfi, mul_dev=g)
+        ops.l2norm_bwd(d_t, t_n, inv_t, dft, mul_dev=g)
+        dscale = torch.empty(1, device=i_n.device, dtype=torch.float32)
+        ops.reduce_dot(rowdot, None, dscale, mul_dev=g)
+        ctx.saved = None
+        return dfi, dft, dscale.reshape(()), None, None, None
+
+
+def _as_classes(labels: torch.Tensor, rows: int, device, name: str) -> torch.Tensor:
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{name}: expected int32 or int64 class ids, got {labels.dtype}")
+    if labels.shape != (rows,):
+        raise ValueError(f"{name}: expected shape [{rows}] (one class id per feature row), got {tuple(labels.shape)}")
+    return labels.to(device=device, dtype=torch.int32).contiguous()
+
+
 def contrastive_loss(image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
-                     group: Optional["dist.ProcessGroup"] = None):
+                     group: Optional["dist.ProcessGroup"] = None, labels: Optional[torch.Tensor] = None,
+                     text_labels: Optional[torch.Tensor] = None):
     """Returns (loss, stats) where stats = tensor([global mean loss, global #correct image->text]).
     `loss` is the GLOBAL mean loss; its gradient w.r.t. this rank's features is exact, so parameter
-    gradients must be SUMMED over ranks (clip.parallel.allreduce_gradients does that)."""
-    return _Contrastive.apply(image_features, text_features, logit_scale, group)
+    gradients must be SUMMED over ranks (clip.parallel.allreduce_gradients does that).
+
+    `labels` (int32/int64 [N_loc]) makes the loss class-aware: image i carries class labels[i], and every text of that class is
+    a positive of image i (uniform soft targets; the same from the text side); `#correct` then counts arg-max columns of the
+    row's class.  Without `text_labels` text i carries labels[i] too (square).  With `text_labels` ([M_loc], M_loc free) the
+    text side has its own classes - e.g. the U distinct texts of a batch, each encoded once (`unique_texts`); single process
+    only.  A negative id is 'unlabelled': such a row adds no loss and no gradient, such a column is a negative for every row.
+    The means divide by the fixed global row counts N and M.  `labels=None` is the pairwise loss (positives on the diagonal)."""
+    if labels is None:
+        if text_labels is not None:
+            raise ValueError("text_labels needs labels (the image side's class ids)")
+        return _Contrastive.apply(image_features, text_features, logit_scale, group)
+    if text_labels is not None and _collectives(group):
+        raise NotImplementedError("class-aware contrastive loss with text_labels (rectangular) is single-process only; "
+                                  "under data parallelism pass labels alone (class_ids(tokens, group) gives them)")
+    a = _as_classes(labels, image_features.shape[0], image_features.device, "labels")
+    if text_labels is None:
+        if text_features.shape[0] != image_features.shape[0]:
+            raise ValueError("labels without text_labels is the square form: image and text features need equal row counts")
+        b = a
+    else:
+        b = _as_classes(text_labels, text_features.shape[0], image_features.device, "text_labels")
+    return _ContrastiveClasses.apply(image_features, text_features, logit_scale, group, a, b)
+
+
+def class_ids(tokens: torch.Tensor, group: Optional["dist.ProcessGroup"] = None) -> torch.Tensor:
+    """int32 [N_loc] class ids for `labels=`: equal token rows get equal ids, different rows different ids - across ranks too
+    when a group is live (the token rows are all-gathered and numbered on the global set; every rank computes the same map)."""
+    tokens = tokens.contiguous()
+    if _collectives(group):
+        rank, world = _world(group)
+        every = torch.empty((world * tokens.shape[0],) + tuple(tokens.shape[1:]), device=tokens.device, dtype=tokens.dtype)
+        dist.all_gather_into_tensor(every, tokens, group=group)
+    else:
+        rank, every = 0, tokens
+    inverse = torch.unique(every, dim=0, return_inverse=True)[1]
+    n = tokens.shape[0]
+    return inverse[rank * n:(rank + 1) * n].to(torch.int32)
+
+
+def unique_texts(tokens: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(unique_tokens [U, L], inverse int32 [N]) with unique_tokens[inverse] == tokens: encode the U distinct texts once and
+    call contrastive_loss(fi, ft_u, logit_scale, labels=inverse, text_labels=arange(U))."""
+    uniq, inverse = torch.unique(tokens, dim=0, return_inverse=True)
+    return uniq, inverse.to(torch.int32)
 
 
 class ContrastiveLoss(torch.nn.Module):
@@ -125,5 +277,5 @@ class ContrastiveLoss(torch.nn.Module):
         super().__init__()
         self.group = group
 
-    def forward(self, image_features, text_features, logit_scale):
-        return contrastive_loss(image_features, text_features, logit_scale, self.group)
+    def forward(self, image_features, text_features, logit_scale, labels=None, text_labels=None):
+        return contrastive_loss(image_features, text_features, logit_scale, self.group, labels=labels, text_labels=text_labels)

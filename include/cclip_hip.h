@@ -314,6 +314,18 @@ int cclip_l2norm_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy,
 int cclip_xent_rows(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* labels,
                     int32_t ignore_index, float grad_scale, float* loss_row, int32_t* pred,
                     void* dlogits, int32_t dlogits_is_bf16, int64_t ldd, float* rowdot, hipStream_t stream);
+/* cclip_xent_rows_classes: the class-aware form (fp32 only).  Row r carries row_class[r], column c carries col_class[c];
+ *   the positives of row r are P = { c : col_class[c] == row_class[r] }, empty when row_class[r] < 0 (a negative id means
+ *   "unlabelled": such a row contributes nothing, such a column is a negative for every row).  Uniform soft targets over P:
+ *   loss_row = logsumexp(row) - mean_{c in P} row[c] (0 when P is empty), pred = argmax(row) (first max),
+ *   hit = 1.0f when row_class[r] >= 0 and col_class[pred] == row_class[r], else 0.0f,
+ *   dlogits = (softmax(row) - [c in P] / |P|) * grad_scale (fp32, may alias logits; an all-zero row when P is empty),
+ *   rowdot = sum_c dlogits[c] * logits[c] (written only together with dlogits).  Every output pointer is optional.
+ *   One wave per row, no atomics: two launches are bitwise equal.
+ *   CCLIP_ERR_ARG (nothing launched): null logits, row_class or col_class; R <= 0 or C <= 0; ld < C; dlogits with ldd < C. */
+int cclip_xent_rows_classes(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* row_class,
+                            const int32_t* col_class, float grad_scale, float* loss_row, int32_t* pred, float* hit,
+                            float* dlogits, int64_t ldd, float* rowdot, hipStream_t stream);
 /* out (+)= alpha * (mul_dev ? *mul_dev : 1) * sum_i a[i] * (b ? b[i] : 1)   (single block, deterministic) */
 int cclip_reduce_dot(const float* a, const float* b, int64_t n, float alpha, const float* mul_dev, float* out,
                      int32_t accumulate, hipStream_t stream);

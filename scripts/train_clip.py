@@ -7,7 +7,12 @@ linear warm-up, per-epoch evaluation, periodic state_dict checkpoints in the Ope
     python scripts/train_clip.py --synthetic --model test-small --epochs 1 --max-steps 3        # offline smoke run
 
 Differences from the reference script, on purpose: constants became flags; TensorBoard (not installed) became one JSON line per
-step on stdout; `--fused-loss` uses clip.contrastive_loss (fused logits + CE, the data-parallel form under torchrun)."""
+step on stdout; `--fused-loss` uses clip.contrastive_loss (fused logits + CE, the data-parallel form under torchrun).
+
+`--class-aware` (implies the fused loss) is where `--batch-size G > 1` becomes meaningful: G groups of the same K labels hold
+every text G times, and the pairwise loss pushes each image away from the G-1 copies of its own text.  With the flag the batch's
+distinct texts are encoded once (clip.unique_texts), every text of an image's class is its positive (clip.contrastive_loss with
+labels= / text_labels=), and the logged accuracy counts an arg-max on the image's class as a hit."""
 from __future__ import annotations
 
 import argparse
@@ -38,6 +43,8 @@ def build_args():
     ap.add_argument("--name", default="clip_balance")
     ap.add_argument("--max-steps", type=int, default=0, help="stop after this many optimiser steps (0: run all epochs)")
     ap.add_argument("--fused-loss", action="store_true")
+    ap.add_argument("--class-aware", action="store_true",
+                    help="same-text pairs are positives: encode each distinct text once, class-aware fused loss (for --batch-size > 1)")
     ap.add_argument("--synthetic", action="store_true", help="generated images + labels, seeded weights, byte tokenizer")
     ap.add_argument("--seed", type=int, default=567)
     return ap
@@ -89,7 +96,13 @@ def main(argv=None):
             image, text = image.to(device).flatten(0, 1), text.to(device).flatten(0, 1)     # [G, K, ...] -> [G*K, ...]
             opt.zero_grad()
             label = torch.arange(image.shape[0], device=device)
-            if args.fused_loss:
+            if args.class_aware:
+                text_u, inverse = clip.unique_texts(text)                                   # [U, 77], text == text_u[inverse]
+                fi, ft = model.encode_image_text(image, text_u)                             # the text tower sees U rows, not G*K
+                loss, stats = clip.contrastive_loss(fi, ft, model.logit_scale, None, labels=inverse,
+                                                    text_labels=torch.arange(text_u.shape[0], device=device))
+                acc = float(stats[1]) / image.shape[0]
+            elif args.fused_loss:
                 fi, ft = model.encode_image_text(image, text)
                 loss, stats = clip.contrastive_loss(fi, ft, model.logit_scale, None)
                 acc = float(stats[1]) / image.shape[0] if len(stats) > 1 else float("nan")
