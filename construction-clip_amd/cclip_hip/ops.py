@@ -937,6 +937,22 @@ class BeamState:
         self.x = None
 
 
+def _beam_step_desc(s, x, rows, blocks_arr, n_layer, kcache, vcache, pos, scratch16, max_len, *, heads, hidden, act, linear_layout,
+                    lnf_w, lnf_b, wte16, wte_f32, wpe_f32) -> None:
+    """The checks and the `step` fields that gpt2_beam_search and gpt2_beam_search_batch share (`rows` sequences in x / the cache)."""
+    D = wte16.shape[1]
+    assert kcache.dim() == 4 and kcache.shape[1] == rows and kcache.stride(3) == 1 and kcache.stride(2) == D and kcache.stride() == vcache.stride()
+    assert kcache.shape[2] == max_len and scratch16.numel() >= rows * (5 * D + hidden) and scratch16.dtype == kcache.dtype
+    assert n_layer <= BEAM_MAX_LAYERS and wte_f32.dtype == torch.float32 and wpe_f32.dtype == torch.float32
+    assert wte_f32.is_contiguous() and wpe_f32.is_contiguous() and wte16.is_contiguous() and wpe_f32.shape[0] >= max_len
+    s.n_layer, s.n_seq, s.width, s.heads, s.hidden, s.act, s.linear_layout, s.pos = n_layer, rows, D, heads, hidden, act, int(linear_layout), pos
+    s.blocks = blocks_arr
+    s.x, s.kcache, s.vcache = x.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
+    s.ld_layer, s.ld_seq = kcache.stride(0), kcache.stride(1)
+    s.scratch16 = scratch16.data_ptr()
+    s.lnf_w, s.lnf_b, s.wte16, s.vocab = lnf_w.data_ptr(), lnf_b.data_ptr(), wte16.data_ptr(), wte16.shape[0]
+
+
 def gpt2_beam_search(blocks_arr, n_layer, st: BeamState, kcache, vcache, pos, scratch16, n_steps, *, heads, hidden, act, lnf_w, lnf_b,
                      wte16, wte_f32, wpe_f32, temperature, stop_token, first_logits=None, logits=None, grid_cap: int = 0) -> None:
     """`n_steps` KV-cached decode steps + beam selections in ONE persistent launch (cclip_gpt2_beam_search; Conv1D layout).
@@ -947,18 +963,10 @@ def gpt2_beam_search(blocks_arr, n_layer, st: BeamState, kcache, vcache, pos, sc
     D = wte16.shape[1]
     if st.x is None:
         st.x = torch.empty(nb, D, device=kcache.device, dtype=torch.float32)
-    assert kcache.dim() == 4 and kcache.shape[1] == nb and kcache.stride(3) == 1 and kcache.stride(2) == D and kcache.stride() == vcache.stride()
-    assert kcache.shape[2] == st.max_len and scratch16.numel() >= nb * (5 * D + hidden) and scratch16.dtype == kcache.dtype
-    assert n_layer <= BEAM_MAX_LAYERS and wte_f32.dtype == torch.float32 and wpe_f32.dtype == torch.float32
-    assert wte_f32.is_contiguous() and wpe_f32.is_contiguous() and wte16.is_contiguous() and wpe_f32.shape[0] >= st.max_len
     d = BeamDesc()
     s = d.step
-    s.n_layer, s.n_seq, s.width, s.heads, s.hidden, s.act, s.linear_layout, s.pos = n_layer, nb, D, heads, hidden, act, 0, pos
-    s.blocks = blocks_arr
-    s.x, s.kcache, s.vcache = st.x.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
-    s.ld_layer, s.ld_seq = kcache.stride(0), kcache.stride(1)
-    s.scratch16 = scratch16.data_ptr()
-    s.lnf_w, s.lnf_b, s.wte16, s.vocab = lnf_w.data_ptr(), lnf_b.data_ptr(), wte16.data_ptr(), wte16.shape[0]
+    _beam_step_desc(s, st.x, nb, blocks_arr, n_layer, kcache, vcache, pos, scratch16, st.max_len, heads=heads, hidden=hidden, act=act,
+                    linear_layout=False, lnf_w=lnf_w, lnf_b=lnf_b, wte16=wte16, wte_f32=wte_f32, wpe_f32=wpe_f32)
     if logits is not None:
         _req(logits, torch.float32, "logits")
         s.logits, s.ld_logits = logits.data_ptr(), logits.stride(0)
@@ -1020,21 +1028,12 @@ def gpt2_beam_search_batch(blocks_arr, n_layer, st: BeamBatchState, kcache, vcac
     D = wte16.shape[1]
     if st.x.shape[1] != D:
         st.x = torch.empty(R, D, device=kcache.device, dtype=torch.float32)
-    assert kcache.dim() == 4 and kcache.shape[1] == R and kcache.stride(3) == 1 and kcache.stride(2) == D and kcache.stride() == vcache.stride()
-    assert kcache.shape[2] == st.max_len and scratch16.numel() >= R * (5 * D + hidden) and scratch16.dtype == kcache.dtype
-    assert n_layer <= BEAM_MAX_LAYERS and wte_f32.dtype == torch.float32 and wpe_f32.dtype == torch.float32
-    assert wte_f32.is_contiguous() and wpe_f32.is_contiguous() and wte16.is_contiguous() and wpe_f32.shape[0] >= st.max_len
     _req(first_logits, torch.float32, "first_logits")
     assert first_logits.is_contiguous() and first_logits.shape == (nc, wte16.shape[0])
     assert st.tokens.shape[1] >= n_steps + 1
     d = BeamBatchDesc()
-    s = d.step
-    s.n_layer, s.n_seq, s.width, s.heads, s.hidden, s.act, s.linear_layout, s.pos = n_layer, R, D, heads, hidden, act, int(linear_layout), pos
-    s.blocks = blocks_arr
-    s.x, s.kcache, s.vcache = st.x.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
-    s.ld_layer, s.ld_seq = kcache.stride(0), kcache.stride(1)
-    s.scratch16 = scratch16.data_ptr()
-    s.lnf_w, s.lnf_b, s.wte16, s.vocab = lnf_w.data_ptr(), lnf_b.data_ptr(), wte16.data_ptr(), wte16.shape[0]
+    _beam_step_desc(d.step, st.x, R, blocks_arr, n_layer, kcache, vcache, pos, scratch16, st.max_len, heads=heads, hidden=hidden, act=act,
+                    linear_layout=linear_layout, lnf_w=lnf_w, lnf_b=lnf_b, wte16=wte16, wte_f32=wte_f32, wpe_f32=wpe_f32)
     d.n_cap, d.beams, d.n_steps, d.stop_token = nc, nb, n_steps, stop_token
     d.ld_tokens, d.max_len, d.grid_cap, d.temperature = st.tokens.stride(0), st.max_len, grid_cap, temperature
     d.first_logits, d.wte_f32, d.wpe_f32 = first_logits.data_ptr(), wte_f32.data_ptr(), wpe_f32.data_ptr()

@@ -10,22 +10,18 @@
 //     type as skinny_block does) are staged in LDS as 16-bit values.  Wave w owns the 32-wide K steps w, w+4, ... and the four
 //     waves' partial sums are added in wave order, so an output element's summation order depends neither on the number of
 //     rows nor on the row's position: a caption's results do not depend on the batch it is decoded in.
-//   - attention: one wave per (row, head), as attn_task, against the caption's own slot table slot_of[cap][t][beam] (caption c
+//   - attention: one wave per (row, head), attn_task against the caption's own slot table slot_of[cap][t][beam] (caption c
 //     owns cache slots c*beams .. c*beams+beams-1, its prefix in slot c*beams);
 //   - lm_head: each workgroup's vocabulary slice x all rows on MFMA (the slice is read once), then per-(workgroup, row)
-//     (max, sum-exp, top-k) partials as select_partials leaves them;
-//   - selection: caption c is merged by workgroup c mod G with select_merge's arithmetic (restated below unchanged); a caption
+//     (max, sum-exp, top-k) partials (select_partials);
+//   - selection: caption c is merged by workgroup c mod G with the one-caption kernel's select_merge; a caption
 //     that has stopped is not merged again, so its tokens / lengths / scores are those of the one-caption loop's break.
 // Hand-overs, bounded spins, the error flag that drains the grid, one workgroup per CU and the re-initialised state words are
-// those of decode_persist.hip.
-#include "gemm_skinny_impl.h"
+// those of decode_persist.hip; what the two kernels share is in decode_persist_impl.h.
+#include "decode_persist_impl.h"
 
 namespace CCLIP_NS {
-namespace beam_batch {
 
-#define BB_MAXL 24
-#define BB_PS 20            // floats per (caption, workgroup, beam) selection partial: max, sum, 8 x (value, index) + pad
-#define BB_MAXR 256         // vocabulary rows per workgroup slice
 #define BB_MAXROWS 64       // captions x beams per launch
 #define BB_KC 768           // K chunk of a projection block
 #define BB_LDA (BB_KC + 8)  // LDS row stride of the staged rows / transposed weights (16-bit elements)
@@ -33,7 +29,7 @@ namespace beam_batch {
 struct BatchArgs {
   int n_layer, nb, n_cap, rows, D, H, Hd, act, V, pos0, n_steps, stop_token, ld_tokens, max_len, rows_per_wg;
   float temperature;
-  cclip_block_ptrs blocks[BB_MAXL];
+  cclip_block_ptrs blocks[DECODE_MAXL];
   float* x;
   bf16* kc; bf16* vc; long ld_layer, ld_seq;
   bf16* scratch;
@@ -44,38 +40,7 @@ struct BatchArgs {
   int* tokens; float* scores; float* seq_len; int* stopped;   // rows c * nb + b
   int* state;                 // [0] hand-over counter, [1] error, [2] captions stopped
   int* cap_state;             // [n_cap][8]: [2] stopped, [3] selections made by then, [4] token columns
-  float* part;                // [n_cap][G][8][BB_PS]
-};
-
-// the fields of one caption that the selection reads and writes (select_merge below is decode_persist.hip's, over this view)
-struct CapView {
-  int nb, V, D, pos0, max_len, ld_tokens, stop_token;
-  const float* wte32; const float* wpe32;
-  float* x; int* slot_of; int* tokens; float* scores; float* seq_len; int* stopped; int* state; float* part;
-};
-
-// ---- phase hand-over (decode_persist.hip's PhaseSync) -------------------------------------------------------------------
-struct PhaseSync {
-  int* counter; int* err; int target; bool dead;
-  __device__ __forceinline__ void arrive(int nprod, bool worked) {
-    __syncthreads();
-    target += nprod;
-    if (worked && !dead && threadIdx.x == 0) __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __device__ __forceinline__ void wait() {
-    if (!dead && threadIdx.x == 0) {
-      int spins = 0;
-      while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > (1 << 23) || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-          __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      }
-    }
-    __syncthreads();
-    if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) dead = true;
-  }
+  float* part;                // [n_cap][G][8][DECODE_PS]
 };
 
 // ---- one 32-column block of a projection for all M rows, on MFMA ------------------------------------------------------------
@@ -107,17 +72,8 @@ __device__ __forceinline__ void mma_block(const GemmArgs& p, const int n0, float
   if (p.ln_x) {                                      // LayerNorm statistics (K <= 1024: one read of the row), as skinny_block
     for (int m = wave; m < M; m += 4) {
       const float* xr = p.ln_x + (long)m * p.ln_ldx;
-      float xv[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) { const int k = lane + 64 * u; xv[u] = ld_coh<true>(xr + (k < K ? k : 0)); }
-      float s1 = 0.f;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) if (lane + 64 * u < K) s1 += xv[u];
-      const float mean = wave_sum(s1) / (float)K;
-      float s2 = 0.f;
-#pragma unroll
-      for (int u = 0; u < 16; ++u) if (lane + 64 * u < K) { const float d = xv[u] - mean; s2 += d * d; }
-      const float rstd = rsqrtf(wave_sum(s2) / (float)K + 1e-5f);
+      float xv[16], mean, rstd;
+      ln_row_stats<true>(xr, K, xv, mean, rstd);
       if (lane == 0) { stt[m] = mean; stt[64 + m] = rstd; }
     }
   }
@@ -236,99 +192,7 @@ __device__ __forceinline__ void proj_phase(const GemmArgs& p, int nblk, int G, f
   for (int cb = blockIdx.x; cb < nblk; cb += G) mma_block<ACT>(p, cb * 32, lds, ps);
 }
 
-// ---- decode attention for one (row, head) by one wave: attn_task of decode_persist.hip against caption c's slot table ------
-__device__ __forceinline__ void attn_task(const BatchArgs& a, const int* slot, int sbase, const bf16* q, long ldq, const bf16* kc,
-                                          const bf16* vc, bf16* out, long ldo, int row, int b, int h, int S, bool valid, float* p_l,
-                                          int* ro_l, float* q_l) {
-  const int lane = threadIdx.x & 63;
-  const int nb = a.nb;
-  for (int k0 = 0; k0 < S; k0 += 256) {
-    int sl[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { const int key = k0 + lane + 64 * u; sl[u] = ld_coh<true>(slot + (long)(key < S ? key : S - 1) * 8 + b); }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int key = k0 + lane + 64 * u;
-      const int v = sl[u] < 0 ? 0 : (sl[u] >= nb ? nb - 1 : sl[u]);
-      if (key < S) ro_l[key] = (int)((long)(sbase + v) * a.ld_seq + (long)key * a.D + h * 64);
-    }
-  }
-  q_l[lane] = (float)ld_coh<true>(q + (long)row * ldq + h * 64 + lane);
-  __syncthreads();
-  const int c = lane & 7, kg = lane >> 3;
-  float m = -__builtin_inff(), l = 0.f;
-  float o[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = 0.f;
-  for (int c0 = 0; c0 < S; c0 += 128) {
-    bf16x8 kv[2][8], vv[4][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int key = c0 + lane + 64 * t;
-      const bf16* kr = kc + ro_l[key < S ? key : S - 1];
-#pragma unroll
-      for (int cc = 0; cc < 8; ++cc) kv[t][cc] = ld_coh<true>((const bf16x8*)(kr + 8 * cc));
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int key = c0 + 32 * t + 8 * u + kg;
-        vv[t][u] = ld_coh<true>((const bf16x8*)(vc + ro_l[key < S ? key : S - 1] + 8 * c));
-      }
-    float sc[2], cm = -__builtin_inff();
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int key = c0 + lane + 64 * t;
-      float acc = 0.f;
-#pragma unroll
-      for (int cc = 0; cc < 8; ++cc)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc += q_l[8 * cc + j] * (float)kv[t][cc][j];
-      sc[t] = key < S ? acc * 0.125f : -__builtin_inff();
-      cm = fmaxf(cm, sc[t]);
-    }
-    cm = wave_max(cm);
-    const float mn = fmaxf(m, cm);
-    const float resc = __expf(m - mn);
-    float cl = 0.f;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int key = c0 + lane + 64 * t;
-      const float e = key < S ? __expf(sc[t] - mn) : 0.f;
-      p_l[lane + 64 * t] = e;
-      cl += e;
-    }
-    l = l * resc + wave_sum(cl);
-    m = mn;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] *= resc;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float w = p_l[32 * t + 8 * u + kg];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] += w * (float)vv[t][u][j];
-      }
-    __syncthreads();
-  }
-  const float inv = 1.0f / l;
-  bf16x8 ov;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float t = o[j];
-    t += __shfl_xor(t, 8, 64);
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    ov[j] = (bf16)(t * inv);
-  }
-  if (valid && kg == 0) st_coh<true>((bf16x8*)(out + (long)row * ldo + h * 64 + 8 * c), ov);
-  __syncthreads();
-}
-
-// ---- LN_f + tied lm_head over the slice [r0, r0 + nr) for every row, on MFMA; logits to sl = lds as [rows][BB_MAXR] --------
+// ---- LN_f + tied lm_head over the slice [r0, r0 + nr) for every row, on MFMA; logits to sl = lds as [rows][DECODE_MAXR] --------
 // xs: LN_f(x) rounded to the operand type, 16-bit [RT*16][D+8] (rows past `rows` zero).  Wave w owns vocabulary tiles w, w+4,
 // .. (<= 4) for every row tile: the slice's wte rows are read once, whatever the number of rows.
 __device__ __forceinline__ void head_phase(const BatchArgs& a, float* lds, int r0, int nr) {
@@ -337,17 +201,8 @@ __device__ __forceinline__ void head_phase(const BatchArgs& a, float* lds, int r
   bf16* xs = (bf16*)lds;
   for (int m = wave; m < R; m += 4) {
     const float* xr = a.x + (long)m * D;
-    float xv[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) { const int kk = lane + 64 * u; xv[u] = ld_coh<true>(xr + (kk < D ? kk : 0)); }
-    float s1 = 0.f;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) if (lane + 64 * u < D) s1 += xv[u];
-    const float mean = wave_sum(s1) / (float)D;
-    float s2 = 0.f;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) if (lane + 64 * u < D) { const float dd = xv[u] - mean; s2 += dd * dd; }
-    const float rstd = rsqrtf(wave_sum(s2) / (float)D + 1e-5f);
+    float xv[16], mean, rstd;
+    ln_row_stats<true>(xr, D, xv, mean, rstd);
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
       const int kk = lane + 64 * u;
@@ -399,266 +254,8 @@ __device__ __forceinline__ void head_phase(const BatchArgs& a, float* lds, int r
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 16 * rt + 4 * g + r, v = 16 * (wave + 4 * j) + li;
-        if (rt < RT && row < R && v < nr) sl[row * BB_MAXR + v] = acc[j][rt][r];
+        if (rt < RT && row < R && v < nr) sl[row * DECODE_MAXR + v] = acc[j][rt][r];
       }
-  __syncthreads();
-}
-
-// ---- per-row partials of one vocabulary slice (select_partials of decode_persist.hip); row m is caption m / nb, beam m % nb,
-// or, in the first selection (one row per caption), caption m, beam 0 --------------------------------------------------------
-__device__ __forceinline__ void select_partials(const BatchArgs& a, const float* sl, int n_in, bool first, int r0, int nr, float T, int G) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int m = wave; m < n_in; m += 4) {
-    float z[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int j = lane + 64 * i;
-      z[i] = j < nr ? sl[m * BB_MAXR + j] / T : -__builtin_inff();
-    }
-    float mx = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-    mx = wave_max(mx);
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s += (lane + 64 * i < nr) ? expf(z[i] - mx) : 0.f;
-    s = wave_sum(s);
-    const int c = first ? m : m / a.nb, b = first ? 0 : m % a.nb;
-    float* pp = a.part + (((long)c * G + blockIdx.x) * 8 + b) * BB_PS;
-    if (lane == 0) { st_coh<true>(pp, nr > 0 ? mx : -__builtin_inff()); st_coh<true>(pp + 1, nr > 0 ? s : 0.f); }
-    for (int r = 0; r < a.nb; ++r) {
-      float bv = z[0]; int bi = lane;
-#pragma unroll
-      for (int i = 1; i < 4; ++i) if (z[i] > bv) { bv = z[i]; bi = lane + 64 * i; }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-      }
-      if (lane == 0) { st_coh<true>(pp + 2 + 2 * r, bv); st_coh<true>((int*)pp + 3 + 2 * r, r0 + bi); }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (lane + 64 * i == bi) z[i] = -__builtin_inff();
-    }
-  }
-}
-
-// ---- the selection proper (select_merge of decode_persist.hip, unchanged), by the caption's workgroup; lds: 64 + 512 + 4096 + 2 * n_in*G*k floats -------------------------------
-template <int MCAP>
-__device__ __forceinline__ void select_merge(const CapView& a, int n_in, bool first, int it, int cur_pos, int G, int ntok, float* lds) {
-  const int tid = threadIdx.x;
-  const int nb = a.nb, k = a.nb;
-  float* bM = lds;            // [8] global max per beam
-  float* bS = lds + 8;        // [8] global sum per beam
-  float* o_sc = lds + 16;     // [8] scores, [8] current lengths, [8] stopped (old beams)
-  float* o_len = lds + 24;
-  int* o_st = (int*)(lds + 32);
-  float* w_avg = lds + 40;    // [8] winners
-  int* w_flat = (int*)(lds + 48);
-  float* red_v = lds + 64;    // [256] reduction scratch
-  int* red_i = (int*)(lds + 64 + 256);
-  float* stat = lds + 64 + 512;          // [8][256 max | 256 sum] slice statistics
-  float* cav = stat + 4096;              // candidate averages [n_in * G * k]
-  int* cfl = (int*)(cav + n_in * G * k); // candidate flat indices
-  // per-beam softmax statistics from the workgroups' slice partials: thread g fetches slice g's (max, sum) of every beam (all
-  // loads in flight), the reduction runs out of LDS in slice order (deterministic).  A serial loop over the slices is one
-  // memory round trip per slice: 2 x 256 of them were 0.8 ms of a 1.4 ms step.
-  {
-    float pm[8], ps[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const float* pp = a.part + ((long)(tid < G ? tid : 0) * 8 + (m < n_in ? m : 0)) * BB_PS;
-      pm[m] = ld_coh<true>(pp); ps[m] = ld_coh<true>(pp + 1);
-    }
-#pragma unroll
-    for (int m = 0; m < 8; ++m) { stat[m * 512 + tid] = tid < G ? pm[m] : -__builtin_inff(); stat[m * 512 + 256 + tid] = tid < G ? ps[m] : 0.f; }
-  }
-  __syncthreads();
-  {
-    // block max / sum by wave shuffles + the four waves' results through LDS (fixed order: reproducible)
-    const int lane = tid & 63, wave = tid >> 6;
-    float wm[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) wm[m] = wave_max(stat[m * 512 + tid]);
-    if (lane == 0) {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) red_v[wave * 8 + m] = wm[m];
-    }
-    __syncthreads();
-    if (tid < 8) bM[tid] = fmaxf(fmaxf(red_v[tid], red_v[8 + tid]), fmaxf(red_v[16 + tid], red_v[24 + tid]));
-    __syncthreads();
-    float ws[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const float sg = stat[m * 512 + 256 + tid];
-      ws[m] = wave_sum(sg > 0.f ? sg * expf(stat[m * 512 + tid] - bM[m]) : 0.f);
-    }
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) red_v[wave * 8 + m] = ws[m];
-    }
-    __syncthreads();
-  }
-  if (tid < 8) {
-    const int m = tid;
-    if (m < n_in) {
-      bS[m] = ((red_v[m] + red_v[8 + m]) + red_v[16 + m]) + red_v[24 + m];
-      const bool st = first ? false : a.stopped[m] != 0;
-      o_st[m] = st ? 1 : 0;
-      o_sc[m] = first ? 0.f : a.scores[m];
-      o_len[m] = first ? 1.f : a.seq_len[m] + (st ? 0.f : 1.f);    // seq_lengths[~is_stopped] += 1 (not in the first selection)
-    }
-  }
-  __syncthreads();
-  const int C = n_in * G * k;
-  for (int c0 = tid; c0 < C; c0 += 2304) {                          // candidates: nine per thread in flight
-    float zz[9]; int tk[9];
-#pragma unroll
-    for (int u = 0; u < 9; ++u) {
-      const int c = c0 + 256 * u < C ? c0 + 256 * u : C - 1;
-      const int r = c % k, g = (c / k) % G, m = c / (k * G);
-      const float* pp = a.part + ((long)g * 8 + m) * BB_PS;
-      zz[u] = ld_coh<true>(pp + 2 + 2 * r);
-      tk[u] = ld_coh<true>((const int*)pp + 3 + 2 * r);
-    }
-#pragma unroll
-    for (int u = 0; u < 9; ++u) {
-      const int c = c0 + 256 * u;
-      if (c >= C) continue;
-      const int r = c % k, g = (c / k) % G, m = c / (k * G);
-      const float z = zz[u];
-      const int tok = tk[u];
-      float avg = -__builtin_inff();
-      int flat = 0x7fffffff;
-      if (o_st[m]) {                                                // logits[is_stopped] = -inf; logits[is_stopped, 0] = 0
-        if (g == 0 && r == 0) { avg = (o_sc[m] + 0.f) / o_len[m]; flat = m * a.V; }
-      } else if (z > -__builtin_inff() && tok >= 0 && tok < a.V) {
-        const float pr = expf(z - bM[m]) / bS[m];                   // softmax(-1) ...
-        const float lp = logf(pr);                                  // ... .log()
-        avg = (o_sc[m] + lp) / o_len[m];
-        flat = m * a.V + tok;
-      }
-      cav[c] = avg; cfl[c] = flat;
-    }
-  }
-  __syncthreads();
-  for (int r = 0; r < k; ++r) {                                     // top-k of the flattened [beams x V] averages, best first
-    float bv = -__builtin_inff(); int bc = -1, bf = 0x7fffffff;
-    for (int c = tid; c < C; c += 256) {
-      const float v = cav[c]; const int f = cfl[c];
-      if (f != 0x7fffffff && (bc < 0 || v > bv || (v == bv && f < bf))) { bv = v; bc = c; bf = f; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {                              // wave arg-max: larger average, then the lower flat index
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oc = __shfl_xor(bc, o, 64), of = __shfl_xor(bf, o, 64);
-      if (oc >= 0 && (bc < 0 || ov > bv || (ov == bv && of < bf))) { bv = ov; bc = oc; bf = of; }
-    }
-    if ((tid & 63) == 0) { red_v[tid >> 6] = bv; red_i[tid >> 6] = bc; red_i[4 + (tid >> 6)] = bf; }
-    __syncthreads();
-    if (tid == 0) {
-      float v0 = -__builtin_inff(); int c0 = -1, f0 = 0x7fffffff;
-      for (int t = 0; t < 4; ++t) {
-        const int cc = red_i[t];
-        if (cc < 0) continue;
-        const float v = red_v[t]; const int f = red_i[4 + t];
-        if (c0 < 0 || v > v0 || (v == v0 && f < f0)) { v0 = v; c0 = cc; f0 = f; }
-      }
-      w_avg[r] = v0; w_flat[r] = c0 >= 0 ? f0 : 0;
-      if (c0 >= 0) cfl[c0] = 0x7fffffff;
-    }
-    __syncthreads();
-  }
-  // bookkeeping: everything below reads the OLD beam state from LDS / registers before it writes the new one
-  int src[8], tok[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int f = i < k ? w_flat[i] : 0;
-    src[i] = f / a.V; tok[i] = f % a.V;
-    if (src[i] >= n_in) src[i] = n_in - 1;
-  }
-  // every load of the bookkeeping goes out first (token rows, slot-table rows, embedding rows: unconditional, clamped
-  // addresses), then the stores: issued phase by phase this was ~8 dependent memory round trips
-  const int next_pos = first ? a.pos0 : cur_pos + 1;
-  const bool has_next = next_pos < a.max_len;
-  int told[MCAP], sold[MCAP];
-  float e[MCAP][4], pe[4];
-  {
-    const int j = tid < ntok ? tid : 0;
-#pragma unroll
-    for (int m = 0; m < MCAP; ++m) told[m] = a.tokens[(long)(m < n_in ? m : 0) * a.ld_tokens + j];
-    const int t = tid <= cur_pos ? tid : 0;
-#pragma unroll
-    for (int m = 0; m < MCAP; ++m) sold[m] = ld_coh<true>(a.slot_of + (long)(t < 0 ? 0 : t) * 8 + m);
-    const int np = has_next ? next_pos : 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int d = tid + 256 * u < a.D ? tid + 256 * u : 0;
-      pe[u] = a.wpe32[(long)np * a.D + d];
-#pragma unroll
-      for (int i = 0; i < MCAP; ++i) e[i][u] = a.wte32[(long)tok[i < nb ? i : 0] * a.D + d];
-    }
-  }
-  if (tid < ntok) {                                                 // tokens = cat(tokens[next_tokens_source], next_tokens)
-#pragma unroll
-    for (int i = 0; i < MCAP; ++i) {
-      int v = told[0];
-#pragma unroll
-      for (int m = 1; m < MCAP; ++m) v = src[i] == m ? told[m] : v;          // (select chain: no dynamically indexed register array)
-      if (i < nb) a.tokens[(long)i * a.ld_tokens + tid] = v;
-    }
-  }
-  if (!first && tid <= cur_pos) {                                   // cache reorder = permute the slot table
-#pragma unroll
-    for (int i = 0; i < MCAP; ++i) {
-      int v = sold[0];
-#pragma unroll
-      for (int m = 1; m < MCAP; ++m) v = src[i] == m ? sold[m] : v;
-      if (i < nb) st_coh<true>(a.slot_of + (long)tid * 8 + i, v);
-    }
-  }
-  if (has_next) {
-    if (tid < nb) st_coh<true>(a.slot_of + (long)next_pos * 8 + tid, tid);        // the next step appends beam b's row to slot b
-#pragma unroll
-    for (int i = 0; i < MCAP; ++i)                                  // next input: wte[token] + wpe[position] (D <= 1024: 4 per thread)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) if (i < nb && tid + 256 * u < a.D) st_coh<true>(a.x + (long)i * a.D + tid + 256 * u, e[i][u] + pe[u]);
-  }
-  for (int j = tid + 256; j < ntok; j += 256) {                     // (prompts longer than 256 tokens)
-    int old[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) old[m] = m < n_in ? a.tokens[(long)m * a.ld_tokens + j] : 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) if (i < nb) a.tokens[(long)i * a.ld_tokens + j] = old[src[i]];
-  }
-  if (!first) {
-    for (int t = tid + 256; t <= cur_pos; t += 256) {               // (positions past 256)
-      int old[8];
-#pragma unroll
-      for (int m = 0; m < 8; ++m) old[m] = ld_coh<true>(a.slot_of + (long)t * 8 + m);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        int v = old[0];
-#pragma unroll
-        for (int m = 1; m < 8; ++m) v = src[i] == m ? old[m] : v;
-        if (i < nb) st_coh<true>(a.slot_of + (long)t * 8 + i, v);
-      }
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    bool all = true;
-    for (int i = 0; i < nb; ++i) {
-      const float len = o_len[src[i]];
-      const int st = (o_st[src[i]] != 0) || tok[i] == a.stop_token;
-      if (ntok < a.ld_tokens) a.tokens[(long)i * a.ld_tokens + ntok] = tok[i];
-      a.seq_len[i] = len;
-      a.scores[i] = w_avg[i] * len;                                 // scores = scores_sum_average * seq_lengths
-      a.stopped[i] = st;
-      all = all && st;
-    }
-    a.state[4] = ntok + 1;
-    if (all && !a.state[2]) { a.state[3] = it + 1; __hip_atomic_store(a.state + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-  }
   __syncthreads();
 }
 
@@ -689,7 +286,7 @@ __global__ __launch_bounds__(256) void gpt2_beam_batch_persist_kernel(const Batc
         v.wte32 = a.wte32; v.wpe32 = a.wpe32;
         v.x = a.x + (long)c * nb * D; v.slot_of = a.slot_of + (long)c * a.max_len * 8; v.tokens = a.tokens + (long)c * nb * a.ld_tokens;
         v.scores = a.scores + c * nb; v.seq_len = a.seq_len + c * nb; v.stopped = a.stopped + c * nb; v.state = cs;
-        v.part = a.part + (long)c * G * 8 * BB_PS;
+        v.part = a.part + (long)c * G * 8 * DECODE_PS;
         select_merge<MCAP>(v, n_in, first, it, cur_pos, G, it, lds);
         if (tid == 0 && __hip_atomic_load(cs + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
           __hip_atomic_fetch_add(a.state + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -702,10 +299,10 @@ __global__ __launch_bounds__(256) void gpt2_beam_batch_persist_kernel(const Batc
     // the prefill's last-position logits of every caption: selections with one input beam (test.py:396-405)
     for (int i = tid; i < a.n_cap * VR; i += 256) {
       const int c = i / VR, j = i - c * VR;
-      if (j < nr) lds[c * BB_MAXR + j] = a.first_logits[(long)c * a.V + r0 + j];
+      if (j < nr) lds[c * DECODE_MAXR + j] = a.first_logits[(long)c * a.V + r0 + j];
     }
     __syncthreads();
-    select_partials(a, lds, a.n_cap, true, r0, nr, T, G);
+    select_partials(a.part, nb, lds, a.n_cap, true, r0, nr, T, G);
     ps.arrive(G, true);
     select_all(1, true, it, a.pos0 - 1);
     ++it;
@@ -740,8 +337,8 @@ __global__ __launch_bounds__(256) void gpt2_beam_batch_persist_kernel(const Batc
         const int tt = valid ? t : ntask - 1;
         const int row = tt / a.H, c = row / nb;
         float* wl = lds + wave * (128 + a.max_len + 64);
-        attn_task(a, a.slot_of + (long)c * a.max_len * 8, c * nb, qkv, ldrow, kc, vc, att, ldrow, row, row - c * nb, tt % a.H, pos + 1,
-                  valid, wl, (int*)(wl + 128), wl + 128 + a.max_len);
+        attn_task(a.slot_of + (long)c * a.max_len * 8, c * nb, nb, a.ld_seq, D, qkv, ldrow, kc, vc, att, ldrow, row, row - c * nb, tt % a.H,
+                  pos + 1, valid, wl, (int*)(wl + 128), wl + 128 + a.max_len);
       }
       ps.arrive(nprod(ntask4), blockIdx.x < ntask4);
       // P3: out-proj + residual (x += ...)
@@ -776,51 +373,36 @@ __global__ __launch_bounds__(256) void gpt2_beam_batch_persist_kernel(const Batc
     // LN_f + tied lm_head over this workgroup's vocabulary slice, the slice's partials, then the selections
     ps.wait();
     head_phase(a, lds, r0, nr);
-    select_partials(a, lds, R, false, r0, nr, T, G);
+    select_partials(a.part, nb, lds, R, false, r0, nr, T, G);
     ps.arrive(G, true);
     select_all(nb, false, it, pos);
   }
 }
 
-}  // namespace beam_batch
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
 
 extern "C" int CCLIP_FN(cclip_gpt2_beam_search_batch)(const cclip_beam_batch_desc* d, hipStream_t stream) {
-  using namespace CCLIP_NS::beam_batch;
-  if (!d || !d->step.blocks || !d->step.x || !d->step.kcache || !d->step.vcache || !d->step.scratch16) return CCLIP_ERR_ARG;
+  if (!d || !persist_desc_ok(d->step)) return CCLIP_ERR_ARG;
   const cclip_decode_desc& s = d->step;
   if (d->n_cap <= 0 || d->beams <= 0 || d->beams > 8 || (long)d->n_cap * d->beams > BB_MAXROWS || s.n_seq != d->n_cap * d->beams)
     return CCLIP_ERR_ARG;
-  if (s.n_layer <= 0 || s.n_layer > BB_MAXL || s.linear_layout) return CCLIP_ERR_ARG;
-  if (s.width <= 0 || (s.width & 63) || s.width > 1024 || s.width != s.heads * 64 || s.hidden <= 0 || (s.hidden & 31) || s.pos < 0) return CCLIP_ERR_ARG;
-  if (s.act != CCLIP_ACT_NONE && s.act != CCLIP_ACT_GELU_NEW) return CCLIP_ERR_ARG;
-  if (!s.lnf_w || !s.lnf_b || !s.wte16 || s.vocab <= 0 || (s.ld_seq & 7) || (s.ld_layer & 7)) return CCLIP_ERR_ARG;
   if (!d->first_logits || !d->wte_f32 || !d->wpe_f32 || !d->slot_of || !d->tokens || !d->scores || !d->seq_lengths || !d->is_stopped ||
       !d->state || !d->cap_state || !d->select_ws)
     return CCLIP_ERR_ARG;
   if (d->n_steps < 0 || d->max_len <= s.pos || d->max_len > 2048 || d->ld_tokens < d->n_steps + 1 || s.ld_seq < (long)d->max_len * s.width)
     return CCLIP_ERR_ARG;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0; hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return CCLIP_ERR_LAUNCH;
-    n_cu = prop.multiProcessorCount;
-  }
-  // the grid of cclip_gpt2_beam_search: at most one workgroup per CU (every workgroup resident), independent of the batch
-  int G = (s.vocab + 223) / 224; if (G < 96) G = 96;
-  if (G > 256) G = 256;
-  if (G > n_cu) G = n_cu;
-  if (d->grid_cap > 0 && d->grid_cap < G) G = d->grid_cap;
-  int VR = (s.vocab + G - 1) / G; VR = (VR + 31) / 32 * 32;
-  if (VR > BB_MAXR) return CCLIP_ERR_ARG;
+  const int n_cu = persist_cu_count();
+  if (n_cu == 0) return CCLIP_ERR_LAUNCH;
+  int G, VR;
+  if (!persist_grid(s.vocab, d->grid_cap, n_cu, &G, &VR)) return CCLIP_ERR_ARG;
   const int rows = s.n_seq, nb = d->beams;
   const int mcap = nb <= 4 ? 4 : 8;
   // LDS: projection block (rows + transposed weights + statistics), attention rows, lm_head rows / slice logits, selection
   size_t by = (size_t)(BB_MAXROWS + 32) * BB_LDA * 2 + 128 * 4;
   const size_t att = (size_t)4 * (128 + d->max_len + 64) * 4; if (att > by) by = att;
   const size_t head = (size_t)((rows + 15) / 16 * 16) * (s.width + 8) * 2; if (head > by) by = head;
-  const size_t slc = (size_t)(rows > d->n_cap ? rows : d->n_cap) * BB_MAXR * 4; if (slc > by) by = slc;
+  const size_t slc = (size_t)(rows > d->n_cap ? rows : d->n_cap) * DECODE_MAXR * 4; if (slc > by) by = slc;
   const size_t sel = (64 + 512 + 4096 + 2 * (size_t)nb * G * nb) * 4; if (sel > by) by = sel;
   if (by > 150 * 1024) return CCLIP_ERR_ARG;
   BatchArgs a;
@@ -835,18 +417,6 @@ extern "C" int CCLIP_FN(cclip_gpt2_beam_search_batch)(const cclip_beam_batch_des
   a.state = d->state; a.cap_state = d->cap_state; a.part = d->select_ws;
   if (hipMemsetAsync(d->state, 0, 8 * sizeof(int), stream) != hipSuccess) return CCLIP_ERR_LAUNCH;
   if (hipMemsetAsync(d->cap_state, 0, (size_t)8 * d->n_cap * sizeof(int), stream) != hipSuccess) return CCLIP_ERR_LAUNCH;
-  const size_t lds = by;
-#define BEAM_BATCH_LAUNCH(MC)                                                                                                   \
-  do {                                                                                                                          \
-    static size_t attr = 0;                                                                                                     \
-    if (lds > attr) {                                                                                                           \
-      if (hipFuncSetAttribute((const void*)gpt2_beam_batch_persist_kernel<MC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-        return CCLIP_ERR_LAUNCH;                                                                                                \
-      attr = lds;                                                                                                               \
-    }                                                                                                                           \
-    hipLaunchKernelGGL((gpt2_beam_batch_persist_kernel<MC>), dim3(G), dim3(256), lds, stream, a);                               \
-  } while (0)
-  if (mcap == 4) BEAM_BATCH_LAUNCH(4); else BEAM_BATCH_LAUNCH(8);
-#undef BEAM_BATCH_LAUNCH
-  return cclip_launch_status();
+  return mcap == 4 ? launch_persist<gpt2_beam_batch_persist_kernel<4>>(G, by, stream, a)
+                   : launch_persist<gpt2_beam_batch_persist_kernel<8>>(G, by, stream, a);
 }

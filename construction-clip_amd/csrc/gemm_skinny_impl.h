@@ -1,5 +1,6 @@
 // The 32-column block of the skinny (M <= 8) K-strided GEMV, shared by the stand-alone kernel (gemm_bf16_skinny.hip) and the
-// persistent decode kernel (decode_persist.hip).
+// one-caption persistent decode kernel (decode_persist.hip), with the coherent accesses and the single-read LayerNorm row that
+// both persistent decode kernels use (decode_persist_impl.h includes this file).
 #pragma once
 #include "gemm_bf16_impl.h"
 
@@ -41,6 +42,24 @@ __device__ __forceinline__ void st_coh(T* p, T v) {
   }
 }
 
+// LayerNorm statistics of one row of K <= 1024 columns by one wave (eps 1e-5, fp32): the row is read ONCE, 16 values per lane
+// left in xv (column lane + 64 u; loads unconditional on clamped addresses, so all are in flight together, sums masked) - three
+// dependent passes over the row were three memory round trips.  The caller writes the normalised row out in its own form.
+template <bool COH>
+__device__ __forceinline__ void ln_row_stats(const float* xr, const int K, float (&xv)[16], float& mean, float& rstd) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) { const int k = lane + 64 * u; xv[u] = ld_coh<COH>(xr + (k < K ? k : 0)); }
+  float s1 = 0.f;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) if (lane + 64 * u < K) s1 += xv[u];
+  mean = wave_sum(s1) / (float)K;
+  float s2 = 0.f;
+#pragma unroll
+  for (int u = 0; u < 16; ++u) if (lane + 64 * u < K) { const float d = xv[u] - mean; s2 += d * d; }
+  rstd = rsqrtf(wave_sum(s2) / (float)K + 1e-5f);
+}
+
 // One 32-column block (columns n0..n0+31) of the skinny GEMM, executed by a 256-thread workgroup; sk_lds: A as fp32 [M][K],
 // reused for the reduction (max(M*K, 256*MCAP*8) floats).  U: weight rows in flight per lane (K = 768: 12 = all of them).
 // Every thread of the workgroup must call it (three workgroup barriers inside).  COH: activations in / out through ld_coh / st_coh.
@@ -80,22 +99,12 @@ __device__ __forceinline__ void skinny_block(const GemmArgs& p, const int n0, fl
   }
   if (p.ln_x) {
     // A = LayerNorm(x) (eps 1e-5, fp32 statistics), rounded to the 16-bit operand type exactly as the stand-alone
-    // LayerNorm kernel's output would be; wave w normalises rows w, w+4.  Rows of up to 1024 columns are read ONCE (16
-    // values per lane, all loads in flight together): three dependent passes over the row were three memory round trips.
+    // LayerNorm kernel's output would be; wave w normalises rows w, w+4.  Rows of up to 1024 columns are read once.
     for (int m = wave; m < M; m += 4) {
       const float* xr = p.ln_x + (long)m * p.ln_ldx;
       if (K <= 1024) {
-        float xv[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) { const int k = lane + 64 * u; xv[u] = ld_coh<COH>(xr + (k < K ? k : 0)); }   // unconditional: all in flight
-        float s1 = 0.f;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) if (lane + 64 * u < K) s1 += xv[u];
-        const float mean = wave_sum(s1) / (float)K;
-        float s2 = 0.f;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) if (lane + 64 * u < K) { const float d = xv[u] - mean; s2 += d * d; }
-        const float rstd = rsqrtf(wave_sum(s2) / (float)K + 1e-5f);
+        float xv[16], mean, rstd;
+        ln_row_stats<COH>(xr, K, xv, mean, rstd);
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
           const int k = lane + 64 * u;
@@ -222,6 +231,5 @@ __device__ __forceinline__ void skinny_block(const GemmArgs& p, const int n0, fl
     }
   }
 }
-
 
 }  // namespace CCLIP_NS
