@@ -716,6 +716,66 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
     return out_scores, out_index
 
 
+LM_HEAD_SCORE_MAX_D = 1024
+
+
+def lm_head_score_workspace(R: int, V: int) -> int:
+    """bytes of per-split partials cclip_lm_head_score needs (R * ceil(V / 1024) * 24)"""
+    fn = lib.cclip_lm_head_score_workspace
+    fn.restype = c_long
+    return int(fn(c_int(R), c_int(V)))
+
+
+def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, lse=None, pred=None, pred_logit=None):
+    """Scores of the lm_head rows z = x16 @ w16^T without the logits: x16 [R, D] and w16 [V, D] 16-bit (same dtype), inner
+    stride 1, row strides multiples of 8 elements, 16-byte aligned; labels_i32 int32 [R].  Returns (logp, lse, pred,
+    pred_logit), each [R]: logp = z[label] - lse (exactly 0 where label == ignore_index, NaN for any other label outside
+    [0, V)), lse = logsumexp(z), pred = argmax (equal logits: the lower column; NaN below every number) and its logit.
+    D % 32 == 0, 32 <= D <= 1024.  A row's outputs do not depend on R.  Enqueues two launches; no host read."""
+    for t, n in ((x16, "x16"), (w16, "w16"), (labels_i32, "labels_i32")):
+        if not t.is_cuda:
+            raise TypeError(f"lm_head_score: {n}: expected a cuda tensor, got {t.device} (no CPU path)")
+    for t, n in ((x16, "x16"), (w16, "w16")):
+        if t.dtype not in HALF_TYPES or t.dtype != x16.dtype:
+            raise ValueError(f"lm_head_score: {n} must be bfloat16 or float16, both alike, got {x16.dtype} / {t.dtype}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"lm_head_score: {n} must be a 2-D view with inner stride 1, got {tuple(t.shape)} / {t.stride()}")
+    if labels_i32.dtype != torch.int32:
+        raise ValueError(f"lm_head_score: labels must be int32, got {labels_i32.dtype}")
+    R, D = x16.shape
+    V = w16.shape[0]
+    if w16.shape[1] != D:
+        raise ValueError(f"lm_head_score: x16 has {D} columns, w16 has {w16.shape[1]}")
+    if R < 1 or V < 1:
+        raise ValueError(f"lm_head_score: empty operand (R = {R}, V = {V})")
+    if V >= 2 ** 31:
+        raise ValueError(f"lm_head_score: V = {V}; column indices are int32")
+    if labels_i32.dim() != 1 or labels_i32.numel() != R or not labels_i32.is_contiguous():
+        raise ValueError(f"lm_head_score: labels must be a contiguous [{R}] vector, got {tuple(labels_i32.shape)}")
+    if D % 32 or not 32 <= D <= LM_HEAD_SCORE_MAX_D:
+        raise NotImplementedError(f"lm_head_score: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {LM_HEAD_SCORE_MAX_D}")
+    for t, n in ((x16, "x16"), (w16, "w16")):
+        if (t.shape[0] > 1 and t.stride(0) % 8) or t.data_ptr() % 16:
+            raise ValueError(f"lm_head_score: {n} must be 16-byte aligned with a row stride that is a multiple of 8 elements "
+                             f"(stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16})")
+    fn = _fn("cclip_lm_head_score", x16, w16)
+    dev = x16.device
+    outs = []
+    for t, n, dt in ((logp, "logp", torch.float32), (lse, "lse", torch.float32), (pred, "pred", torch.int32),
+                     (pred_logit, "pred_logit", torch.float32)):
+        if t is None:
+            t = torch.empty(R, device=dev, dtype=dt)
+        if t.dtype != dt or t.device != dev or tuple(t.shape) != (R,) or not t.is_contiguous():
+            raise ValueError(f"lm_head_score: {n} must be a contiguous {dt} [{R}] vector on {dev}, got {t.dtype} {tuple(t.shape)}")
+        outs.append(t)
+    ws = torch.empty(lm_head_score_workspace(R, V) // 8, device=dev, dtype=torch.int64)
+    ldx = x16.stride(0) if R > 1 else max(D, x16.stride(0) // 8 * 8)
+    ldw = w16.stride(0) if V > 1 else max(D, w16.stride(0) // 8 * 8)
+    check(fn(_p(x16), c_long(ldx), c_int(R), c_int(D), _p(w16), c_long(ldw), c_int(V), _p(labels_i32), c_int(ignore_index),
+             _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(ws), _stream()), "cclip_lm_head_score")
+    return tuple(outs)
+
+
 def attention_small_fwd(q, k, v, o, *, B: int, T: int, H: int, head_dim: int, lse=None, scale=None) -> None:
     """Generic-head_dim unmasked attention (TransformerMapper): same tensor conventions as attention_fwd."""
     d = _attn_desc(q, k, v, o, lse, B, T, H, False, None, scale, head_dim)

@@ -18,11 +18,12 @@ causal & key-padding attention).  fp32 masters in a flat arena, bf16 MFMA operan
 """
 from __future__ import annotations
 
+import math
 import os
 import warnings
 from enum import Enum
 from types import SimpleNamespace
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -939,6 +940,51 @@ class ClipCaptionModel(nn.Module):
         self._ensure_runtime()
         return _CaptionLoss.apply(self, tokens, prefix, attribute, mask, *self._arena.params.values())
 
+    @torch.no_grad()
+    def score(self, tokens, prefix, attribute, mask=None) -> "CaptionScores":
+        """Teacher-forced evaluation of train.py:354-357 without logits: per target the log-probability and the argmax, from
+        one fused lm_head scoring launch pair (ops.lm_head_score) on the rows that predict a target.  The embedding and
+        stack pass is caption_loss's inference pass (packed rows, nothing saved for backward); inference only, whatever
+        mode the model is in, and it touches no gradient.  Nothing is read on the host beyond the row count the packed
+        pass itself sizes its buffers with."""
+        if not tokens.is_cuda:
+            raise RuntimeError("ClipCaptionModel: HIP path only (no CPU fallback)")
+        xo, c = self._embed_and_run(tokens, prefix, attribute, mask, False, pack=True)
+        B, S, Lc = c["B"], c["S"], tokens.shape[1]
+        dev = tokens.device
+        first = S - Lc - 1                                                    # = P + A - 1 (train.py:356)
+        flat = tokens.reshape(-1)
+        tsel = c["tsel"] if c["cu"] is not None else None
+        if tsel is not None:                                                  # packed: the targets up to each caption's last non-zero token
+            rows = (c["cu"][:-1].long()[tsel // Lc] + first + tsel % Lc).to(torch.int32).contiguous()
+            labels = flat[tsel].to(torch.int32).contiguous()
+        else:
+            rows = (torch.arange(B, device=dev)[:, None] * S + first + torch.arange(Lc, device=dev)[None, :]).reshape(-1).to(torch.int32)
+            labels = flat.to(torch.int32).contiguous()
+        if c["compact"]:
+            rows = None                                                       # xo holds exactly these rows, in this order
+        ar = self._arena
+        p = ar.params
+        R, D = labels.numel(), self.model_embedding_size
+        keep = tokens != 0
+        if R:
+            xf = torch.empty(R, D, device=dev, dtype=self.compute_dtype)
+            ops.layernorm_fwd(xo, p["model.transformer.ln_f.weight"].data, p["model.transformer.ln_f.bias"].data, rows=R,
+                              row_index=rows, out_bf16=xf)
+            logp, _, pred, _ = ops.lm_head_score(xf, ar.b["model.transformer.wte.weight"], labels, ignore_index=0)
+        if tsel is not None:                                                  # compact rows back to [B, Lc]
+            token_logp = torch.zeros(B * Lc, device=dev, dtype=torch.float32)
+            token_pred = torch.full((B * Lc,), -1, device=dev, dtype=torch.int32)
+            if R:
+                token_logp[tsel] = logp
+                token_pred[tsel] = pred
+        else:
+            token_logp, token_pred = logp, pred
+        token_logp = token_logp.view(B, Lc)
+        token_pred = torch.where(keep, token_pred.view(B, Lc), torch.full_like(token_pred.view(B, Lc), -1))
+        return CaptionScores(token_logp=token_logp, token_pred=token_pred, token_correct=keep & (token_pred == tokens),
+                             n_tokens=keep.sum(1).to(torch.int32), nll=-token_logp.sum(1))
+
     # ---- backward shared by both autograd nodes ----
     def _backward_from_dlogits(self, c: dict, dlog_b: torch.Tensor, rows: torch.Tensor, lm):
         """dlog_b: bf16 [R, V] gradient of the selected logits rows."""
@@ -1008,6 +1054,48 @@ class ClipCaptionModel(nn.Module):
             self._mlp_mapper_backward(c["msave"], dxb.view(B, S * D)[:, :P * D], S * D, A)
         ar.scale_grads(trainable_names, 1.0 / LS)
         ar.publish_grads(trainable_names)
+
+
+class CaptionScores(NamedTuple):
+    """What ClipCaptionModel.score returns: device tensors, nothing read on the host.
+      token_logp     fp32 [B, Lc]   log p(tokens[b, j] | everything before it); 0 where tokens[b, j] == 0 (ignored, train.py:357)
+      token_pred     int32 [B, Lc]  the teacher-forced argmax at that position; -1 at ignored positions
+      token_correct  bool [B, Lc]   token_pred == tokens, False at ignored positions
+      n_tokens       int32 [B]      scored (non-zero) targets of the caption
+      nll            fp32 [B]       -token_logp.sum(1)"""
+    token_logp: torch.Tensor
+    token_pred: torch.Tensor
+    token_correct: torch.Tensor
+    n_tokens: torch.Tensor
+    nll: torch.Tensor
+
+    @property
+    def loss(self) -> torch.Tensor:
+        """nll.sum() / n_tokens.sum(): what caption_loss returns for the same batch (0-d fp32; 0 for a batch without targets)"""
+        return self.nll.sum() / self.n_tokens.sum().clamp(min=1).to(torch.float32)
+
+
+def evaluate_captions(model: "ClipCaptionModel", batches) -> dict:
+    """Held-out evaluation: `batches` yields (tokens, mask, prefix, attribute) as ClipCocoDataset / synthetic_caption_batch
+    do.  Sums are kept on the device (float64 for the log-likelihood) and read back once at the end.
+    Returns loss (mean negative log-likelihood per scored token, = caption_loss over the whole set), perplexity = exp(loss),
+    token_accuracy (teacher-forced argmax == target), caption_exact (share of captions with every scored token right),
+    n_captions and n_tokens."""
+    dev = next(model.parameters()).device
+    acc_f = torch.zeros(1, device=dev, dtype=torch.float64)                 # sum of nll
+    acc_i = torch.zeros(4, device=dev, dtype=torch.int64)                   # tokens, correct tokens, captions, exact captions
+    for tokens, mask, prefix, attribute in batches:
+        tokens, attribute = tokens.to(dev), attribute.to(dev)
+        sc = model.score(tokens, prefix.to(dev, dtype=torch.float32), attribute, None if mask is None else mask.to(dev))
+        right = sc.token_correct.sum(1)
+        acc_f += sc.nll.double().sum()
+        acc_i += torch.stack((sc.n_tokens.sum(), right.sum(), torch.full_like(right[0], tokens.shape[0]),
+                              (right == sc.n_tokens).sum())).to(torch.int64)
+    nll = float(acc_f.cpu())                                                # the one host read (with the next line's)
+    n_tok, n_right, n_cap, n_exact = (int(v) for v in acc_i.cpu())
+    loss = nll / max(n_tok, 1)
+    return dict(loss=loss, perplexity=math.exp(loss), token_accuracy=n_right / max(n_tok, 1),
+                caption_exact=n_exact / max(n_cap, 1), n_captions=n_cap, n_tokens=n_tok)
 
 
 class ClipCaptionPrefix(ClipCaptionModel):

@@ -297,6 +297,27 @@ int cclip_similarity_topk(const void* q, int64_t ldq, int32_t Q, const void* g, 
                           int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
                           hipStream_t stream);
 
+/* ---- lm_head scoring without the logits (csrc/lm_score.hip) ----------------------------------------------------
+ * For hidden rows x [R, D] (the ln_f output) and the vocabulary matrix w [V, D] (the tied wte), both bf16 (fp16 in the twin)
+ * with row strides ldx / ldw in elements and inner stride 1, with z[r, j] = sum_d x[r, d] w[j, d] accumulated in fp32 on the MFMA:
+ *   lse[r]        = log sum_j exp z[r, j]
+ *   logp[r]       = z[r, labels[r]] - lse[r]; exactly 0.0f where labels[r] == ignore_index (checked first); NaN where the
+ *                   label lies outside [0, V) (nothing is read out of range)
+ *   pred[r]       = argmax_j z[r, j]: equal fp32 logits (-0 == +0) go to the LOWER column, a NaN logit ranks below every number
+ *   pred_logit[r] = that maximum
+ * all [R] contiguous; lse, pred and pred_logit may be NULL.  The R x V logits are never written.  Every logit is one
+ * accumulator chain over d, the vocabulary is split by a rule that depends on V alone and partials are combined in a fixed
+ * order without atomics: two launches are bitwise equal, and a row's outputs do not depend on R or on the row's position.
+ * Two launches on `stream`: per-split partials into `workspace`, then the merge.  workspace: at least
+ * cclip_lm_head_score_workspace(R, V) bytes (0 for arguments the call would refuse; 24 bytes per row and 1024 columns),
+ * 8-byte aligned device memory the caller owns; its contents before and after are meaningless.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): null x, w, labels, logp or workspace; R <= 0; V <= 0; D < 32, D % 32 or D > 1024; ldx or
+ * ldw below D or not a multiple of 8; x or w not 16-byte aligned; a misaligned output or workspace. */
+int64_t cclip_lm_head_score_workspace(int32_t R, int32_t V);
+int cclip_lm_head_score(const void* x, int64_t ldx, int32_t R, int32_t D, const void* w, int64_t ldw, int32_t V,
+                        const int32_t* labels, int32_t ignore_index, float* logp, float* lse, int32_t* pred,
+                        float* pred_logit, void* workspace, hipStream_t stream);
+
 /* ---- loss side (fp32) ------------------------------------------------------------------------
  * cclip_l2norm_fwd/bwd: y = x / ||x||_2 per row (image_features / image_features.norm(dim=1)).
  * cclip_xent_rows: per row r with label labels[r]: loss_row = logsumexp(row) - row[label]
@@ -538,6 +559,9 @@ int cclip_cast_f32_to_f16(const float* in, void* out, int64_t n, hipStream_t str
 int cclip_similarity_topk_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
                               int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
                               hipStream_t stream);
+int cclip_lm_head_score_f16(const void* x, int64_t ldx, int32_t R, int32_t D, const void* w, int64_t ldw, int32_t V,
+                            const int32_t* labels, int32_t ignore_index, float* logp, float* lse, int32_t* pred,
+                            float* pred_logit, void* workspace, hipStream_t stream);
 
 #ifdef __cplusplus
 }

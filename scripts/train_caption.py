@@ -53,11 +53,15 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=0)
     ap.add_argument("--no-fused-loss", dest="fused", action="store_false")
     ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--val-data", default=None, help="embedding pickle of a held-out set: log val_loss / val_perplexity / "
+                    "val_token_accuracy after every epoch")
+    ap.add_argument("--val-fraction", type=float, default=0.0, help="hold this share of --data out (seeded permutation) for the same")
+    ap.add_argument("--val-seed", type=int, default=567)
     args = ap.parse_args(argv)
 
     from clip import optim as coptim
-    from clip_caption import (ClipCaptionModel, ClipCaptionPrefix, GPT2_MODELS, MappingType, init_caption_state_dict,
-                              init_transformer_mapper_state_dict)
+    from clip_caption import (ClipCaptionModel, ClipCaptionPrefix, GPT2_MODELS, MappingType, evaluate_captions,
+                              init_caption_state_dict, init_transformer_mapper_state_dict)
     from clip_caption.data import ClipCocoDataset
     device = torch.device("cuda:0")
     geo = GPT2_MODELS[args.gpt2 or args.tokenizer]
@@ -72,6 +76,16 @@ def main(argv=None):
         args.out_dir = os.path.join(tmp.name, "checkpoints")
     dataset = ClipCocoDataset(args.data, P, A, gpt2_type=args.tokenizer, normalize_prefix=args.normalize_prefix,
                               tokenizer=tokenizer)                                        # train.py:406
+    val_sets = []
+    if args.val_fraction > 0:                                                             # seeded split of --data
+        perm = torch.randperm(len(dataset), generator=torch.Generator().manual_seed(args.val_seed)).tolist()
+        n_val = min(len(dataset) - 1, max(1, int(round(args.val_fraction * len(dataset)))))
+        val_sets.append(torch.utils.data.Subset(dataset, sorted(perm[:n_val])))
+        dataset = torch.utils.data.Subset(dataset, sorted(perm[n_val:]))
+    if args.val_data:
+        val_sets.append(ClipCocoDataset(args.val_data, P, A, gpt2_type=args.tokenizer, normalize_prefix=args.normalize_prefix,
+                                        tokenizer=tokenizer))
+    val_set = torch.utils.data.ConcatDataset(val_sets) if val_sets else None
     mt = {"mlp": MappingType.MLP, "transformer": MappingType.Transformer}[args.mapping_type]
     cls = ClipCaptionPrefix if args.only_prefix else ClipCaptionModel                     # train.py:409-416
     model = cls(P, clip_length=args.prefix_length_clip, prefix_size=geo.prefix_size, num_layers=args.num_layers,
@@ -109,6 +123,10 @@ def main(argv=None):
             C.log_line(epoch=epoch, step=step, loss=round(float(loss.detach()), 6))
             if args.max_steps and step >= args.max_steps:
                 break
+        if val_set is not None:                                                           # held-out loss: no logits, no gradient touched
+            ev = evaluate_captions(model, DataLoader(val_set, batch_size=max(args.bs, 16), shuffle=False))
+            C.log_line(epoch=epoch, val_loss=round(ev["loss"], 6), val_perplexity=round(ev["perplexity"], 4),
+                       val_token_accuracy=round(ev["token_accuracy"], 6), val_captions=ev["n_captions"])
         if epoch % args.save_every == 0 or epoch == args.epochs - 1:                      # train.py:377-381
             path = os.path.join(args.out_dir, f"{args.prefix}-{epoch:03d}.pt")
             torch.save(model.state_dict(), path)
