@@ -74,24 +74,25 @@ def transformer_mapper(sd: SD, prefix: Tensor, clip_length: int, num_heads: int 
 
 
 def gpt2_forward(sd: SD, inputs_embeds: Tensor, attention_mask: Optional[Tensor], n_head: int,
-                 p: str = "model.") -> Tensor:
+                 p: str = "model.", dtype: torch.dtype = torch.float32) -> Tensor:
     """GPT2LMHeadModel(inputs_embeds=..., attention_mask=...).logits (call: train.py:268).
     pre-LN blocks, Conv1D weights stored [in, out] (HF:pytorch_utils.py:95-117), packed c_attn,
-    causal + additive key-padding mask (HF:modeling_gpt2.py:103-107), gelu_new, tied lm_head."""
-    x = inputs_embeds.float()
+    causal + additive key-padding mask (HF:modeling_gpt2.py:103-107), gelu_new, tied lm_head.
+    dtype: the arithmetic's type (float64: the reference of the float64 kernel tests)."""
+    x = inputs_embeds.to(dtype)
     b, s, d = x.shape
     dh = d // n_head
-    x = x + sd[p + "transformer.wpe.weight"].float()[:s]
-    causal = torch.full((s, s), float("-inf")).triu_(1)
+    x = x + sd[p + "transformer.wpe.weight"].to(dtype)[:s]
+    causal = torch.full((s, s), float("-inf"), dtype=dtype).triu_(1)
     if attention_mask is not None:
-        pad = (1.0 - attention_mask.float())[:, None, None, :] * torch.finfo(torch.float32).min
+        pad = (1.0 - attention_mask.to(dtype))[:, None, None, :] * torch.finfo(torch.float32).min
     else:
         pad = None
     n_layer = len({k.split(".")[3] for k in sd if k.startswith(p + "transformer.h.")})
     for i in range(n_layer):
         q = f"{p}transformer.h.{i}."
-        h = F.layer_norm(x, (d,), sd[q + "ln_1.weight"].float(), sd[q + "ln_1.bias"].float(), 1e-5)
-        qkv = h @ sd[q + "attn.c_attn.weight"].float() + sd[q + "attn.c_attn.bias"].float()
+        h = F.layer_norm(x, (d,), sd[q + "ln_1.weight"].to(dtype), sd[q + "ln_1.bias"].to(dtype), 1e-5)
+        qkv = h @ sd[q + "attn.c_attn.weight"].to(dtype) + sd[q + "attn.c_attn.bias"].to(dtype)
         qq, kk, vv = qkv.split(d, dim=-1)
         qq = qq.view(b, s, n_head, dh).transpose(1, 2)
         kk = kk.view(b, s, n_head, dh).transpose(1, 2)
@@ -100,12 +101,12 @@ def gpt2_forward(sd: SD, inputs_embeds: Tensor, attention_mask: Optional[Tensor]
         if pad is not None:
             sc = sc + pad
         a = (torch.softmax(sc, dim=-1) @ vv).transpose(1, 2).reshape(b, s, d)
-        x = x + a @ sd[q + "attn.c_proj.weight"].float() + sd[q + "attn.c_proj.bias"].float()
-        h = F.layer_norm(x, (d,), sd[q + "ln_2.weight"].float(), sd[q + "ln_2.bias"].float(), 1e-5)
-        h = gelu_new(h @ sd[q + "mlp.c_fc.weight"].float() + sd[q + "mlp.c_fc.bias"].float())
-        x = x + h @ sd[q + "mlp.c_proj.weight"].float() + sd[q + "mlp.c_proj.bias"].float()
-    x = F.layer_norm(x, (d,), sd[p + "transformer.ln_f.weight"].float(), sd[p + "transformer.ln_f.bias"].float(), 1e-5)
-    return x @ sd[p + "transformer.wte.weight"].float().t()
+        x = x + a @ sd[q + "attn.c_proj.weight"].to(dtype) + sd[q + "attn.c_proj.bias"].to(dtype)
+        h = F.layer_norm(x, (d,), sd[q + "ln_2.weight"].to(dtype), sd[q + "ln_2.bias"].to(dtype), 1e-5)
+        h = gelu_new(h @ sd[q + "mlp.c_fc.weight"].to(dtype) + sd[q + "mlp.c_fc.bias"].to(dtype))
+        x = x + h @ sd[q + "mlp.c_proj.weight"].to(dtype) + sd[q + "mlp.c_proj.bias"].to(dtype)
+    x = F.layer_norm(x, (d,), sd[p + "transformer.ln_f.weight"].to(dtype), sd[p + "transformer.ln_f.bias"].to(dtype), 1e-5)
+    return x @ sd[p + "transformer.wte.weight"].to(dtype).t()
 
 
 def caption_forward(sd: SD, tokens: Tensor, prefix: Tensor, attribute: Tensor, mask: Optional[Tensor],
