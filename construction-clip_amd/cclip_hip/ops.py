@@ -1284,6 +1284,39 @@ def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pr
           "cclip_xent_rows_classes")
 
 
+def sigmoid_rows(logits, row_class_i32, col_class_i32, bias, *, loss_row=None, pred=None, hit=None, dlogits=None,
+                 grad_scale: float = 1.0, rowdot=None, rowsum=None) -> None:
+    """Pairwise sigmoid (SigLIP) row loss (include/cclip_hip.h, cclip_sigmoid_rows): cell (r, c) is a positive when column c
+    carries row r's class, a negative otherwise; a negative class id is 'unlabelled'.  `bias` is a one-element fp32 device
+    tensor (never read on the host).  fp32 only; dlogits may be `logits` itself; rowdot / rowsum come only with dlogits."""
+    _req(logits, torch.float32, "logits"); _req(row_class_i32, torch.int32, "row_class"); _req(col_class_i32, torch.int32, "col_class")
+    _req(bias, torch.float32, "bias")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError(f"logits: expected [R, C] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
+    if bias.numel() != 1:
+        raise ValueError(f"bias: expected one element, got {tuple(bias.shape)}")
+    R, C = logits.shape
+    for t, n, name in ((row_class_i32, R, "row_class"), (col_class_i32, C, "col_class")):
+        if t.shape != (n,) or not t.is_contiguous():
+            raise ValueError(f"{name}: expected contiguous [{n}], got {tuple(t.shape)}")
+    for t, dt, name in ((loss_row, torch.float32, "loss_row"), (pred, torch.int32, "pred"), (hit, torch.float32, "hit"),
+                        (rowdot, torch.float32, "rowdot"), (rowsum, torch.float32, "rowsum")):
+        if t is not None:
+            _req(t, dt, name)
+            if t.shape != (R,) or not t.is_contiguous():
+                raise ValueError(f"{name}: expected contiguous [{R}], got {tuple(t.shape)}")
+    if dlogits is not None:
+        _req(dlogits, torch.float32, "dlogits")
+        if dlogits.shape != (R, C) or dlogits.stride(1) != 1:
+            raise ValueError(f"dlogits: expected [{R}, {C}] with unit column stride, got {tuple(dlogits.shape)}")
+    elif rowdot is not None or rowsum is not None:
+        raise ValueError("rowdot / rowsum are written only together with dlogits")
+    check(lib.cclip_sigmoid_rows(_p(logits), c_long(logits.stride(0)), c_int(R), c_int(C), _p(row_class_i32), _p(col_class_i32),
+                                 _p(bias), c_float(grad_scale), _p(loss_row), _p(pred), _p(hit), _p(dlogits),
+                                 c_long(0 if dlogits is None else dlogits.stride(0)), _p(rowdot), _p(rowsum), _stream()),
+          "cclip_sigmoid_rows")
+
+
 def reduce_dot(a, b, out, *, alpha: float = 1.0, mul_dev=None, accumulate: bool = False) -> None:
     check(lib.cclip_reduce_dot(_p(a), _p(b), c_long(a.numel()), c_float(alpha), _p(mul_dev), _p(out),
                                c_int(int(accumulate)), _stream()), "cclip_reduce_dot")

@@ -4,6 +4,7 @@ from .clip import available_models, load, tokenize, _transform  # noqa: F401
 from . import simple_tokenizer  # noqa: F401  (attention.py:114 uses clip.simple_tokenizer.SimpleTokenizer)
 from .model import CLIP, build_model  # noqa: F401
 from .loss import contrastive_loss, ContrastiveLoss, class_ids, unique_texts  # noqa: F401
+from .loss import sigmoid_loss, SigmoidLoss  # noqa: F401  (SigLIP's pairwise sigmoid objective on the same head)
 from .preprocess_device import DevicePreprocess  # noqa: F401
 from .explain import interpret, image_relevance_map, text_token_scores  # noqa: F401  (attention.py:14, 88-92, 115-117)
 from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)

@@ -347,6 +347,21 @@ int cclip_xent_rows(const float* logits, int64_t ld, int32_t R, int32_t C, const
 int cclip_xent_rows_classes(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* row_class,
                             const int32_t* col_class, float grad_scale, float* loss_row, int32_t* pred, float* hit,
                             float* dlogits, int64_t ldd, float* rowdot, hipStream_t stream);
+/* cclip_sigmoid_rows: the pairwise sigmoid (SigLIP) row loss (fp32 only), classes as for cclip_xent_rows_classes.  With
+ *   b = *bias_dev (a device scalar: nothing is read on the host), u = row[c] + b and y = +1 when row_class[r] >= 0 and
+ *   col_class[c] == row_class[r], else -1 (a column with a negative id is a negative for every labelled row):
+ *   loss_row = sum_c softplus(-y u), dlogits = -y sigmoid(-y u) * grad_scale (fp32, may alias logits),
+ *   rowdot = sum_c dlogits[c] * logits[c] (logits, not u: the d/d(logit_scale) term of the row), rowsum = sum_c dlogits[c]
+ *   (the d/d(bias) term of the row); rowdot and rowsum are written only together with dlogits.  A row with row_class[r] < 0
+ *   is unlabelled: loss_row, rowdot and rowsum are 0 and its dlogits row is all zeros.  For every row pred = argmax(row)
+ *   (first max) and hit = 1.0f when row_class[r] >= 0 and col_class[pred] == row_class[r], else 0.0f.  Every output pointer
+ *   is optional.  softplus and sigmoid are formed from exp(-|u|), so |u| = 100 gives finite losses and |dlogits| <=
+ *   grad_scale.  One wave per row, one sweep, no atomics: two launches are bitwise equal.
+ *   CCLIP_ERR_ARG (nothing launched): null logits, row_class, col_class or bias_dev; R <= 0 or C <= 0; ld < C; dlogits with
+ *   ldd < C. */
+int cclip_sigmoid_rows(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* row_class,
+                       const int32_t* col_class, const float* bias_dev, float grad_scale, float* loss_row, int32_t* pred,
+                       float* hit, float* dlogits, int64_t ldd, float* rowdot, float* rowsum, hipStream_t stream);
 /* out (+)= alpha * (mul_dev ? *mul_dev : 1) * sum_i a[i] * (b ? b[i] : 1)   (single block, deterministic) */
 int cclip_reduce_dot(const float* a, const float* b, int64_t n, float alpha, const float* mul_dev, float* out,
                      int32_t accumulate, hipStream_t stream);

@@ -12,7 +12,13 @@ step on stdout; `--fused-loss` uses clip.contrastive_loss (fused logits + CE, th
 `--class-aware` (implies the fused loss) is where `--batch-size G > 1` becomes meaningful: G groups of the same K labels hold
 every text G times, and the pairwise loss pushes each image away from the G-1 copies of its own text.  With the flag the batch's
 distinct texts are encoded once (clip.unique_texts), every text of an image's class is its positive (clip.contrastive_loss with
-labels= / text_labels=), and the logged accuracy counts an arg-max on the image's class as a hit."""
+labels= / text_labels=), and the logged accuracy counts an arg-max on the image's class as a hit.
+
+`--loss sigmoid` (implies the fused path) swaps the objective for SigLIP's pairwise sigmoid loss (clip.SigmoidLoss): every
+(image, text) cell is scored on its own against a learnable `logit_bias` (`--logit-bias-init`, SigLIP's -10), which suits the
+small batches of this loop.  It composes with `--class-aware` (distinct texts once, every text of the class a positive).  The
+bias is not a CLIP weight: it has an AdamW of its own at `--lr` under the same warm-up, it is logged with the loss, and it is
+saved next to each checkpoint as `<checkpoint>_logit_bias.pt` - the checkpoint itself stays a pure OpenAI-layout state_dict."""
 from __future__ import annotations
 
 import argparse
@@ -45,6 +51,9 @@ def build_args():
     ap.add_argument("--fused-loss", action="store_true")
     ap.add_argument("--class-aware", action="store_true",
                     help="same-text pairs are positives: encode each distinct text once, class-aware fused loss (for --batch-size > 1)")
+    ap.add_argument("--loss", choices=("softmax", "sigmoid"), default="softmax",
+                    help="sigmoid: SigLIP's pairwise sigmoid loss with a learnable logit bias (implies the fused path)")
+    ap.add_argument("--logit-bias-init", type=float, default=-10.0, help="initial logit bias of --loss sigmoid")
     ap.add_argument("--synthetic", action="store_true", help="generated images + labels, seeded weights, byte tokenizer")
     ap.add_argument("--seed", type=int, default=567)
     return ap
@@ -89,18 +98,32 @@ def main(argv=None):
     opt = coptim.AdamW(model, lr=args.lr)                                                   # train.py:143
     sched = coptim.get_linear_schedule_with_warmup(opt, args.warmup_steps, args.epochs * len(train_dl))   # train.py:145-147
     ce = torch.nn.CrossEntropyLoss()
+    sig = bias_opt = bias_sched = None
+    if args.loss == "sigmoid":
+        sig = clip.SigmoidLoss(init_bias=args.logit_bias_init).to(device)
+        bias_opt = torch.optim.AdamW(sig.parameters(), lr=args.lr, weight_decay=0.0)
+        bias_sched = coptim.get_linear_schedule_with_warmup(bias_opt, args.warmup_steps, args.epochs * len(train_dl))
     os.makedirs(args.out_dir, exist_ok=True)
     step = 0
     for epoch in range(1, args.epochs + 1):
         for image, text in train_dl:                                                        # train.py:157
             image, text = image.to(device).flatten(0, 1), text.to(device).flatten(0, 1)     # [G, K, ...] -> [G*K, ...]
             opt.zero_grad()
+            if bias_opt is not None:
+                bias_opt.zero_grad()
             label = torch.arange(image.shape[0], device=device)
             if args.class_aware:
                 text_u, inverse = clip.unique_texts(text)                                   # [U, 77], text == text_u[inverse]
                 fi, ft = model.encode_image_text(image, text_u)                             # the text tower sees U rows, not G*K
-                loss, stats = clip.contrastive_loss(fi, ft, model.logit_scale, None, labels=inverse,
-                                                    text_labels=torch.arange(text_u.shape[0], device=device))
+                text_ids = torch.arange(text_u.shape[0], device=device)
+                if sig is not None:
+                    loss, stats = sig(fi, ft, model.logit_scale, labels=inverse, text_labels=text_ids)
+                else:
+                    loss, stats = clip.contrastive_loss(fi, ft, model.logit_scale, None, labels=inverse, text_labels=text_ids)
+                acc = float(stats[1]) / image.shape[0]
+            elif sig is not None:
+                fi, ft = model.encode_image_text(image, text)
+                loss, stats = sig(fi, ft, model.logit_scale)
                 acc = float(stats[1]) / image.shape[0]
             elif args.fused_loss:
                 fi, ft = model.encode_image_text(image, text)
@@ -113,8 +136,14 @@ def main(argv=None):
             loss.backward()
             opt.step()
             sched.step()
+            extra = {}
+            if sig is not None:
+                bias_opt.step()
+                bias_sched.step()
+                extra = dict(logit_bias=round(float(sig.logit_bias.detach()), 6))
             step += 1
-            C.log_line(epoch=epoch, step=step, loss=round(float(loss.detach()), 6), accuracy=round(acc, 4), lr=sched.get_last_lr()[0])
+            C.log_line(epoch=epoch, step=step, loss=round(float(loss.detach()), 6), accuracy=round(acc, 4), lr=sched.get_last_lr()[0],
+                       **extra)
             if args.max_steps and step >= args.max_steps:
                 break
         test_acc = evaluate(model, test_dl, device)
@@ -123,6 +152,10 @@ def main(argv=None):
             path = os.path.join(args.out_dir, f"{args.name}_comb{args.combination_num}_{epoch}.pt")
             torch.save(model.state_dict(), path)                                            # train.py:211-217
             C.log_line(saved=path)
+            if sig is not None:
+                side = path[:-3] + "_logit_bias.pt"
+                torch.save(sig.logit_bias.detach().cpu(), side)
+                C.log_line(saved=side)
         if args.max_steps and step >= args.max_steps:
             break
     if tmp is not None:
