@@ -776,6 +776,53 @@ def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, 
     return tuple(outs)
 
 
+SAMPLE_ROWS_MAX_V = 65536
+
+
+def sample_rows(logits, u, done_i32, *, inv_temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, stop_token: int = -1,
+                token=None, logprob=None, n_kept=None, kept_mass=None):
+    """One sampled token per row (include/cclip_hip.h, cclip_sample_rows): logits fp32 [n, V] with inner stride 1, u fp32 [n]
+    uniforms in [0, 1), done_i32 int32 [n] (read, and set to 1 on the rows that draw stop_token; a row entered as done gets
+    token 0 at logprob 0).  The logits are multiplied by inv_temperature; top_k = 0 and top_p = 1 switch the filters off.  Returns (token int32, logprob fp32, n_kept int32,
+    kept_mass fp32), each [n].  V <= 65536.  One launch; no host read; two calls are bitwise equal."""
+    if not 0.0 < inv_temperature < float("inf"):
+        raise ValueError(f"sample_rows: inv_temperature must be a positive finite number, got {inv_temperature}")
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f"sample_rows: top_k must be an integer >= 0 (0 = off), got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"sample_rows: top_p must lie in (0, 1] (1 = off), got {top_p}")
+    if logits.dtype != torch.float32 or u.dtype != torch.float32:
+        raise ValueError(f"sample_rows: logits and u must be float32, got {logits.dtype} / {u.dtype}")
+    if done_i32.dtype != torch.int32:
+        raise ValueError(f"sample_rows: done must be int32, got {done_i32.dtype}")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError(f"sample_rows: logits must be a 2-D view with inner stride 1, got {tuple(logits.shape)} / {logits.stride()}")
+    n, V = logits.shape
+    if n < 1 or not 1 <= V <= SAMPLE_ROWS_MAX_V:
+        raise ValueError(f"sample_rows: n = {n}, V = {V}; the kernel needs n >= 1 and 1 <= V <= {SAMPLE_ROWS_MAX_V}")
+    ld = logits.stride(0) if n > 1 else max(V, logits.stride(0))
+    if ld < V:
+        raise ValueError(f"sample_rows: row stride {ld} below V = {V}")
+    for t, name in ((u, "u"), (done_i32, "done")):
+        if tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != logits.device:
+            raise ValueError(f"sample_rows: {name} must be a contiguous [{n}] vector on {logits.device}, got {tuple(t.shape)} on {t.device}")
+    if not logits.is_cuda:
+        raise TypeError(f"sample_rows: expected cuda tensors, got {logits.device} (no CPU path)")
+    dev = logits.device
+    outs = []
+    for t, name, dt in ((token, "token", torch.int32), (logprob, "logprob", torch.float32), (n_kept, "n_kept", torch.int32),
+                        (kept_mass, "kept_mass", torch.float32)):
+        if t is None:
+            t = torch.empty(n, device=dev, dtype=dt)
+        if t.dtype != dt or t.device != dev or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"sample_rows: {name} must be a contiguous {dt} [{n}] vector on {dev}, got {t.dtype} {tuple(t.shape)}")
+        outs.append(t)
+    check(lib.cclip_sample_rows(_p(logits), c_long(ld), c_int(n), c_int(V), c_float(inv_temperature), c_int(min(int(top_k), 2 ** 31 - 1)),
+                                c_float(top_p), _p(u), c_int(stop_token), _p(done_i32), _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                                _p(outs[3]), _stream()), "cclip_sample_rows")
+    return tuple(outs)
+
+
 def attention_small_fwd(q, k, v, o, *, B: int, T: int, H: int, head_dim: int, lse=None, scale=None) -> None:
     """Generic-head_dim unmasked attention (TransformerMapper): same tensor conventions as attention_fwd."""
     d = _attn_desc(q, k, v, o, lse, B, T, H, False, None, scale, head_dim)

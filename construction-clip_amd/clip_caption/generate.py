@@ -304,3 +304,95 @@ def generate2_batch(model, tokenizer, embeds, entry_length: int = 67, top_p: flo
         return out
     att = [[a] for a in _replay_attention(model, [embeds[i] for i in range(N)], [r[0] for r in rows], attention_layer)]
     return (*out, att) if return_tokens else (out, att)
+
+
+def _sample_outputs(tokenizer, tokens, logprobs, stop_token: int, prompt_ids, return_tokens: bool, return_logprobs: bool):
+    """One image's K samples: texts best first by mean token log-probability; tokens / lengths / sums stay in draw order."""
+    K, steps = tokens.shape
+    at = torch.arange(1, steps + 1, device=tokens.device)
+    lengths = torch.where(tokens.eq(stop_token), at, at.new_tensor(steps)).amin(dim=1)     # up to and including the first stop token
+    total = logprobs.sum(dim=1)                                          # (a finished row adds exact zeros)
+    order = (total / lengths).argsort(descending=True, stable=True).tolist()
+    rows, lens = tokens.cpu().numpy(), lengths.tolist()
+    texts = [tokenizer.decode(prompt_ids + list(rows[i][:lens[i]])) for i in order]
+    if not return_tokens:
+        return texts
+    return (texts, tokens, lengths, total, logprobs) if return_logprobs else (texts, tokens, lengths, total)
+
+
+@torch.no_grad()
+def generate_sample_batch(model, tokenizer, embeds, num_samples: int = 1, entry_length: int = 67, top_p: float = 0.8,
+                          top_k: int = 0, temperature: float = 1.0, stop_token: int = 102, generator=None, uniforms=None,
+                          return_tokens: bool = False, return_logprobs: bool = False, _prompt_ids=None):
+    """num_samples captions DRAWN from the model's distribution for each of N prefixes (embeds [N, S, D]): at every position
+    the next token of each sample comes from softmax(logits / temperature) cut to the top_k most probable tokens (0 = off)
+    and to the nucleus top_p (the reference's filter, test.py:492-500; 1 = off) - one KV-cached decode step over all N x K
+    rows, one row-sampling launch (csrc/sample_rows.hip), one wte gather.  A sample ends with its first stop_token; from then on
+    it only appends token 0.  The randomness is one uniform per (position, row): torch.rand(entry_length, N * K,
+    generator=generator) drawn up front, or `uniforms` of that shape (row i * K + j = sample j of image i), so one seed gives
+    one set of captions.  Returns a list of N lists of K texts, each list best first by mean token log-probability; with
+    return_tokens a list of N tuples (texts, tokens int32 [K, steps], lengths [K], sum_logprob [K]) in draw order, with
+    return_logprobs also the per-position log-probabilities fp32 [K, steps] (log p of the full softmax; 0 past the end)."""
+    from cclip_hip import ops
+    _check_embeds(embeds)
+    if num_samples < 1:
+        raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+    if entry_length < 1:
+        raise ValueError(f"entry_length must be >= 1, got {entry_length}")
+    if not temperature > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    if not embeds.is_cuda:
+        raise TypeError(f"generate_sample: expected cuda embeddings, got {embeds.device} (sampling has no host path)")
+    model.eval()
+    dev = embeds.device
+    N, K = embeds.shape[0], int(num_samples)
+    n = N * K
+    if uniforms is None:
+        gdev = dev if generator is None else generator.device
+        uniforms = torch.rand(entry_length, n, generator=generator, device=gdev).to(dev)
+    else:
+        if tuple(uniforms.shape) != (entry_length, n):
+            raise ValueError(f"uniforms must be [{entry_length}, {n}] (entry_length, N * num_samples), got {tuple(uniforms.shape)}")
+        uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
+    logits, cache = _step_logits(model, embeds, None)                   # prefill: every prefix once
+    if K > 1:                                                           # each sample its own rows of the cache
+        rows = torch.arange(N, device=dev).repeat_interleave(K)
+        logits, cache = logits[rows], cache.reorder(rows)
+    done = torch.zeros(n, dtype=torch.int32, device=dev)
+    toks, lps = [], []
+    for step in range(entry_length):
+        if step:
+            step_in = model.gpt.transformer.wte(toks[-1].long()).view(n, 1, -1)
+            logits, cache = _step_logits(model, step_in, cache)
+        tok, lp, _, _ = ops.sample_rows(logits, uniforms[step], done, inv_temperature=1.0 / temperature, top_k=top_k, top_p=top_p,
+                                        stop_token=stop_token)
+        toks.append(tok)
+        lps.append(lp)
+        # `all done` is a device -> host sync: looked at every 4th step and on the last, as generate_beam's host loop does
+        if ((step & 3) == 3 or step == entry_length - 1) and bool(done.all()):
+            break
+    tokens, logprobs = torch.stack(toks, dim=1), torch.stack(lps, dim=1)
+    prompt_ids = [] if _prompt_ids is None else list(_prompt_ids)
+    return [_sample_outputs(tokenizer, tokens[i * K:(i + 1) * K], logprobs[i * K:(i + 1) * K], stop_token, prompt_ids, return_tokens,
+                            return_logprobs) for i in range(N)]
+
+
+@torch.no_grad()
+def generate_sample(model, tokenizer, embed=None, prompt=None, num_samples: int = 1, entry_length: int = 67, top_p: float = 0.8,
+                    top_k: int = 0, temperature: float = 1.0, stop_token: int = 102, generator=None, uniforms=None,
+                    return_tokens: bool = False, return_logprobs: bool = False):
+    """generate_sample_batch for one image (embed [1, S, D]) or one text prompt: the num_samples texts best first; with
+    return_tokens (texts, tokens [K, steps], lengths, sum_logprob) in draw order.  From a prompt the texts start with the
+    prompt, the token rows hold the drawn tokens only."""
+    prompt_ids = None
+    if embed is None:
+        if prompt is None:
+            raise ValueError("generate_sample needs embed= or prompt=")
+        prompt_ids = list(tokenizer.encode(prompt))
+        device = next(model.parameters()).device
+        embed = model.gpt.transformer.wte(torch.tensor(prompt_ids, device=device).unsqueeze(0))
+    if isinstance(embed, torch.Tensor) and embed.dim() == 3 and embed.shape[0] != 1:
+        raise ValueError(f"generate_sample takes one prefix [1, S, D], got {tuple(embed.shape)}; use generate_sample_batch")
+    return generate_sample_batch(model, tokenizer, embed, num_samples=num_samples, entry_length=entry_length, top_p=top_p, top_k=top_k,
+                                 temperature=temperature, stop_token=stop_token, generator=generator, uniforms=uniforms,
+                                 return_tokens=return_tokens, return_logprobs=return_logprobs, _prompt_ids=prompt_ids)[0]

@@ -318,6 +318,31 @@ int cclip_lm_head_score(const void* x, int64_t ldx, int32_t R, int32_t D, const 
                         const int32_t* labels, int32_t ignore_index, float* logp, float* lse, int32_t* pred,
                         float* pred_logit, void* workspace, hipStream_t stream);
 
+/* ---- row sampling: temperature, top-k, nucleus and the draw in one launch (csrc/sample_rows.hip, fp32 only) ----
+ * One token per row of logits [n, V] (row stride ld >= V elements), for every row r with done[r] == 0:
+ *   p        = softmax(row * inv_temperature)
+ *   order    : the tokens by (logit descending, id ascending), the fp32 logits compared as they are (-0 == +0)
+ *   top-k    : keeps the first top_k tokens of that order (0, or any value >= V: all)
+ *   top-p    : among those a token is kept if and only if the mass of the tokens strictly ahead of it is <= top_p (so the
+ *              first is always kept; 1 = off)
+ *   n_kept   = the size of the kept set, kept_mass = Z = its share of the row's mass
+ *   token    : walking the kept tokens in ascending id order, the first whose running kept mass exceeds u[r] * Z
+ *              (u[r] in [0, 1); values outside are clamped into [0, 1 - 2^-24])
+ *   logprob  = log p[token] (of the full softmax, not the renormalised one)
+ *   done[r]  becomes 1 when token == stop_token.
+ * A row with done[r] != 0 gets token 0, logprob 0, n_kept 0, kept_mass 0 and done[r] is left alone.  -inf logits are legal
+ * (p = 0, never drawn while the row has a finite logit); a row with a NaN, a +inf or no finite logit is undefined (some token in
+ * [0, V) comes out, nothing is accessed out of bounds).  token, logprob, n_kept, kept_mass, u and done are [n] contiguous.
+ * Masses are 64-bit integers (2^-40 of the row's largest term per unit; a term that is positive in fp32 weighs at least one
+ * unit), so every sum is exact and independent of the order it is taken in: no floating-point sum, no floating-point
+ * atomic, two launches are bitwise equal and a row's outputs do not depend on n.  One 256-thread work-group per row, six
+ * passes over the row, no workspace.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): a null pointer; n <= 0; V < 1 or V > 65536; ld < V; top_k < 0; top_p outside (0, 1];
+ * inv_temperature not a positive finite number. */
+int cclip_sample_rows(const float* logits, int64_t ld, int32_t n, int32_t V, float inv_temperature, int32_t top_k,
+                      float top_p, const float* u, int32_t stop_token, int32_t* done, int32_t* token, float* logprob,
+                      int32_t* n_kept, float* kept_mass, hipStream_t stream);
+
 /* ---- loss side (fp32) ------------------------------------------------------------------------
  * cclip_l2norm_fwd/bwd: y = x / ||x||_2 per row (image_features / image_features.norm(dim=1)).
  * cclip_xent_rows: per row r with label labels[r]: loss_row = logsumexp(row) - row[label]

@@ -41,6 +41,13 @@ def build_parser():
     ap.add_argument("--attention-out", default=None, metavar="FILE.npz",
                     help="also store, per image i, attention_<i> [H, n, S0+n-1] (the best beam's last-layer rows) and map_<i> "
                          "(clip_caption.caption_attention_map of them: the reference's attention_map, test.py:342-349)")
+    ap.add_argument("--sample", type=int, default=0, metavar="K",
+                    help="also draw K captions per image from the model's distribution (clip_caption.generate_sample_batch); "
+                         "each record gets \"samples\", best first by mean token log-probability")
+    ap.add_argument("--top-p", type=float, default=0.8, help="--sample: nucleus mass (1 = off)")
+    ap.add_argument("--top-k", type=int, default=0, help="--sample: keep the k most probable tokens (0 = off)")
+    ap.add_argument("--temperature", type=float, default=1.0, help="--sample: softmax temperature")
+    ap.add_argument("--seed", type=int, default=0, help="--sample: seed of the draws (one seed, one set of captions)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=9, help="--synthetic: images to describe")
     ap.add_argument("--clip_synthetic", default="test-tiny", help="--synthetic: CLIP geometry")
@@ -87,18 +94,34 @@ def setup(args):
     return cap, annotations, args.image_path, tmp
 
 
+@torch.no_grad()
+def sample_captions(cap, images, args, generator):
+    """--sample: K drawn captions per image, on the prefix Captioner.submit decodes from (projected features + attribute ids)"""
+    from clip_caption import generate_sample_batch
+    feat, _, ids = cap.embed(images)
+    model = cap.caption_model
+    proj = model.clip_project(feat).view(feat.shape[0], cap.prefix_length, -1)
+    emb = torch.cat((proj, model.gpt.transformer.wte(ids.long())), dim=1)
+    return generate_sample_batch(model, cap.tokenizer, emb, num_samples=args.sample, entry_length=args.entry_length or 67,
+                                 top_p=args.top_p, top_k=args.top_k, temperature=args.temperature, generator=generator)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.sample < 0:
+        raise SystemExit("--sample must be >= 0")
     from PIL import Image
     cap, annotations, image_path, tmp = setup(args)
     log = {"caption": []}
     arrays = {}
     entry_length = args.entry_length or (67 if args.greedy else 100)
+    generator = torch.Generator(device=cap.device).manual_seed(args.seed) if args.sample else None
     for i in range(0, len(annotations), args.bs):
         chunk = annotations[i:i + args.bs]
         images = [Image.open(os.path.join(image_path, a["file_name"])) for a in chunk]
         records = cap.describe(images, beam_size=args.beam_size, entry_length=entry_length, greedy=args.greedy,
                                return_attention=args.attention_out is not None)
+        samples = sample_captions(cap, images, args, generator) if args.sample else None
         for j, (a, r) in enumerate(zip(chunk, records)):
             if args.attention_out is not None:
                 from clip_caption import caption_attention_map
@@ -111,6 +134,8 @@ def main(argv=None):
                 "caption": a.get("caption", "") or a.get("violation_list", ""),           # test.py:622-623
                 "file_name": a.get("file_name", ""),
             })
+            if samples is not None:
+                log["caption"][-1]["samples"] = samples[j]
         C.log_line(done=min(i + args.bs, len(annotations)), of=len(annotations))
     if tmp is not None:
         tmp.cleanup()
