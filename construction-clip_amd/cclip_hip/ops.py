@@ -626,6 +626,25 @@ def attention_relevance(q, k, v, lse, da, R, *, B: int, T: int, H: int, causal: 
           "cclip_attention_relevance")
 
 
+def attention_relevance_row(q, k, v, lse, da, r_in, r_out, *, B: int, T: int, H: int, causal: bool = False, scale=None, cu=None,
+                            grad_scale: float = 1.0) -> None:
+    """One row of attention_relevance's update at any T <= 8192: r_out[b, :T_b] = r_in[b, :T_b] + r_in[b, :T_b] C with the same
+    C (never formed), r_out[b, T_b:] = r_in[b, T_b:].  q/k/v/lse/da as for attention_relevance; r_in, r_out fp32 [B, T]
+    contiguous and different buffers (the library refuses r_in is r_out)."""
+    _req16(da, "da")
+    assert da.stride(-1) == 1
+    _req(lse, torch.float32, "lse")
+    for r, n in ((r_in, "r_in"), (r_out, "r_out")):
+        _req(r, torch.float32, n)
+        assert r.is_contiguous() and tuple(r.shape) == (B, T), f"{n}: expected contiguous [{B}, {T}], got {tuple(r.shape)}"
+    assert lse.is_contiguous() and lse.numel() >= B * H * T
+    d = _attn_desc(q, k, v, da, lse, B, T, H, causal, None, scale)     # (o is not read: da stands in as the dtype witness)
+    _attn_cu(d, cu, B)
+    d.dout, d.lddo = da.data_ptr(), da.stride(-2)
+    check(_fn("cclip_attention_relevance_row", q, k, v, da)(ctypes.byref(d), c_float(grad_scale), _p(r_in), _p(r_out), _stream()),
+          "cclip_attention_relevance_row")
+
+
 ATTENTION_PROBS_MAX_T = 256
 
 

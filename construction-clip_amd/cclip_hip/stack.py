@@ -396,9 +396,11 @@ class BlockStack:
 
         param_grads=False: the dgrad chain only - every block is treated as frozen (no weight / bias gradient, no side stream,
         no grad_hook).  relevance=(R, stop_layer, grad_scale): at every layer l >= stop_layer the attention relevance of that
-        layer (ops.attention_relevance: R <- R + R C_l, R fp32 [B, T, T]) runs on the layer's attention-output gradient before
-        its attention backward; the walk ends at stop_layer, whose input gradient is not formed (dx / the return value are
-        then meaningless).  grad_scale: the loss scale dx was multiplied by."""
+        layer (ops.attention_relevance: R <- R + R C_l, R fp32 [B, T, T], T <= 128) runs on the layer's attention-output gradient
+        before its attention backward; the walk ends at stop_layer, whose input gradient is not formed (dx / the return value are
+        then meaningless).  grad_scale: the loss scale dx was multiplied by.  R fp32 [B, T] (2-D) is one row per sequence instead:
+        ops.attention_relevance_row (r <- r + r C_l, any T) runs per layer, ping-ponging between R and one scratch buffer, and the
+        final row ends in the caller's R."""
         import os
         geo = self.geo
         D, H = geo.width, geo.heads
@@ -434,6 +436,8 @@ class BlockStack:
             if Mp != M:
                 tmp8[M:].zero_()
         ln_ws = self.scratch  # partial sums live in scratch; sized per call
+        # relevance with a 2-D R: [current row, scratch], swapped after every layer (the row kernel cannot update in place)
+        rel_row = [relevance[0], torch.empty_like(relevance[0])] if relevance is not None and relevance[0].dim() == 2 else None
 
         def leaf(fn):
             """run a parameter-gradient launch group where it belongs: after what the main stream has produced so far"""
@@ -535,7 +539,14 @@ class BlockStack:
                         self._wgrad(dxb, a, gr["w_o"], M, A("w_o", gr), sc, gr["b_o"], A("b_o", gr), pad=True)
                     leaf(f3)
                 ops.gemm_bf16(dxb, wd("w_o")[0], b_kcontig=wd("w_o")[1], out_bf16=dsm, M=M)
-            if relevance is not None:
+            if rel_row is not None:
+                assert geo.head_dim == 64, "attention relevance: head_dim 64"
+                ops.attention_relevance_row(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], lse[l], dsm, rel_row[0], rel_row[1],
+                                            B=B, T=T, H=H, causal=geo.causal, cu=saved.get("cu"), grad_scale=relevance[2])
+                rel_row.reverse()
+                if l <= relevance[1]:
+                    break
+            elif relevance is not None:
                 assert geo.head_dim == 64 and T <= 128, "attention relevance: head_dim 64, T <= 128"
                 ops.attention_relevance(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], lse[l], dsm, relevance[0], B=B, T=T,
                                         H=H, causal=geo.causal, cu=saved.get("cu"), grad_scale=relevance[2])
@@ -564,6 +575,8 @@ class BlockStack:
                 # this layer's last gradient kernels are enqueued (weights on the side stream, LayerNorm affines on the main
                 # one): a data-parallel reducer may start this layer's all-reduce now, under the remaining layers' backward
                 hook([t for t in gr.values() if t is not None], [s_ for s_ in (cur, side) if s_ is not None])
+        if rel_row is not None and rel_row[0] is not relevance[0]:
+            relevance[0].copy_(rel_row[0])       # the walk ended on the scratch side
         saved["dx_in"] = dx              # (with a compact tail the full-width fp32 gradient is a new tensor, not the argument)
         if side is not None:
             cur.wait_stream(side)        # every parameter gradient is complete before anyone downstream looks at it

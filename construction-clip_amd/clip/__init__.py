@@ -7,4 +7,5 @@ from .loss import contrastive_loss, ContrastiveLoss, class_ids, unique_texts  # 
 from .loss import sigmoid_loss, SigmoidLoss  # noqa: F401  (SigLIP's pairwise sigmoid objective on the same head)
 from .preprocess_device import DevicePreprocess  # noqa: F401
 from .explain import interpret, image_relevance_map, text_token_scores  # noqa: F401  (attention.py:14, 88-92, 115-117)
+from .explain import interpret_rows, text_row_scores  # noqa: F401  (the same rows for towers of more than 128 tokens)
 from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)

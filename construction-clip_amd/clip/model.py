@@ -643,9 +643,40 @@ class CLIP(nn.Module):
             raise NotImplementedError(
                 f"relevance maps: the fused relevance kernel handles sequences of at most 128 tokens with 64-wide heads; this "
                 f"model has {geo.vision_tokens} image tokens and {geo.context_length} text tokens (ViT-B/16, ViT-L/14 are out of range)")
+        r_img, r_txt = self._relevance_pass(image, text, start_layer, start_layer_text, rows=False, what="relevance")
+        N, C = image.shape[0], geo.context_length
+        if r_txt.shape[1] < C:                  # trim_text_padding ran the tower on fewer positions: the rest stays identity
+            full = torch.eye(C, device=r_txt.device, dtype=torch.float32).repeat(N, 1, 1)
+            full[:, :r_txt.shape[1], :r_txt.shape[1]] = r_txt
+            r_txt = full
+        return r_img, r_txt
+
+    def relevance_rows(self, image: torch.Tensor, text: torch.Tensor, start_layer: int = -1,
+                       start_layer_text: int = -1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The rows of relevance()'s matrices that the reference's callers read, at any sequence length (ViT-B/16, ViT-L/14):
+        (r_img fp32 [N, T_img] = row 0 (class token) of R_image, r_txt fp32 [N, context_length] = the EOT row of R_text, zero at
+        the positions a trimmed or packed text tower did not run - what the full matrix holds there).
+
+        The same forward and dgrad-only backward as relevance(); per block the row kernel (ops.attention_relevance_row) advances
+        r <- r + r C_l from the one-hot of the pooled position instead of the T x T matrix.  Heads must be 64 wide; there is no
+        token limit.  The arena's gradient slots and every .grad stay as they are."""
+        _require_cuda(image, "relevance_rows")
+        _require_cuda(text, "relevance_rows")
+        geo = self.geo
+        if geo.vision_width % 64 or geo.transformer_width % 64:
+            raise NotImplementedError(f"relevance rows: the row relevance kernel needs 64-wide heads (widths {geo.vision_width} / "
+                                      f"{geo.transformer_width})")
+        r_img, r_txt = self._relevance_pass(image, text, start_layer, start_layer_text, rows=True, what="relevance_rows")
+        C = geo.context_length
+        if r_txt.shape[1] < C:                  # trim_text_padding ran the tower on fewer positions: zero there
+            r_txt = torch.nn.functional.pad(r_txt, (0, C - r_txt.shape[1]))
+        return r_img, r_txt
+
+    def _relevance_pass(self, image, text, start_layer: int, start_layer_text: int, *, rows: bool, what: str):
+        """relevance() / relevance_rows(): the forward of both towers, _Logits.backward with dlogits = I, and each tower's walk."""
         N = image.shape[0]
         if N == 0 or text.shape[0] != N:
-            raise ValueError(f"relevance: need N >= 1 image / text pairs, got {N} images and {text.shape[0]} texts")
+            raise ValueError(f"{what}: need N >= 1 image / text pairs, got {N} images and {text.shape[0]} texts")
         with torch.no_grad():
             fi, ci = self._image_forward(image, train=True)
             ft, ct = self._text_forward(text, train=True)
@@ -659,17 +690,16 @@ class CLIP(nn.Module):
             dfi, dft = torch.empty_like(i_n), torch.empty_like(t_n)
             ops.l2norm_bwd(d_in, i_n, inv_i, dfi)
             ops.l2norm_bwd(d_tn, t_n, inv_t, dft)
-            r_img = self._tower_relevance("vis", ci, dfi, start_layer)
-            r_txt = self._tower_relevance("txt", ct, dft, start_layer_text)
-        C = geo.context_length
-        if r_txt.shape[1] < C:                  # trim_text_padding ran the tower on fewer positions: the rest stays identity
-            full = torch.eye(C, device=r_txt.device, dtype=torch.float32).repeat(N, 1, 1)
-            full[:, :r_txt.shape[1], :r_txt.shape[1]] = r_txt
-            r_txt = full
+            # the pooled position of each sequence: the class token; the caption's EOT (its last row when the tower ran packed)
+            pos_i = torch.zeros(N, device=fi.device, dtype=torch.long) if rows else None
+            pos_t = (ct["rows_dense"].long() - torch.arange(N, device=fi.device) * ct["L"]) if rows else None
+            r_img = self._tower_relevance("vis", ci, dfi, start_layer, pos_i)
+            r_txt = self._tower_relevance("txt", ct, dft, start_layer_text, pos_t)
         return r_img, r_txt
 
-    def _tower_relevance(self, tower: str, c: dict, dfeat: torch.Tensor, start: int) -> torch.Tensor:
-        """Pooled LayerNorm backward of one tower, then BlockStack.backward(param_grads=False, relevance=...) from R = I."""
+    def _tower_relevance(self, tower: str, c: dict, dfeat: torch.Tensor, start: int, pos=None) -> torch.Tensor:
+        """Pooled LayerNorm backward of one tower, then BlockStack.backward(param_grads=False, relevance=...) from R = I
+        [B, T, T] - or, with pos (int64 [B]), from the one-hot rows e_pos [B, T]."""
         ar, st = self._arena, self._rt[tower]
         p = ar.params
         vis = tower == "vis"
@@ -677,7 +707,10 @@ class CLIP(nn.Module):
         B, saved = c["B"], c["saved"]
         T, L = saved["T"], len(st.blocks)
         dev = dfeat.device
-        R = torch.eye(T, device=dev, dtype=torch.float32).repeat(B, 1, 1)
+        if pos is None:
+            R = torch.eye(T, device=dev, dtype=torch.float32).repeat(B, 1, 1)
+        else:
+            R = torch.zeros(B, T, device=dev, dtype=torch.float32).scatter_(1, pos[:, None], 1.0)
         s = L - 1 if start == -1 else start     # (the reference: only -1 means "last block"; any other value keeps blocks i >= it)
         if s >= L:
             return R

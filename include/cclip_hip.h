@@ -180,6 +180,15 @@ int cclip_attention_bwd(const cclip_attn_desc* d, hipStream_t stream);
  * as for the backward).  R: fp32 [B, T, T], updated in place.  grad_scale > 0: the loss scale the dgrad chain runs under.
  * Neither P nor dP is written anywhere. */
 int cclip_attention_relevance(const cclip_attn_desc* d, float grad_scale, float* R, hipStream_t stream);
+/* One row of the same step, 1 <= T <= 8192 (the long towers: ViT-B/16 197, ViT-L/14 257, ViT-L/14@336px 577 tokens): the row
+ * vector r of R obeys r <- r + r C, so per sequence b of length T_b (T, or cu[b+1] - cu[b] clamped to T; lse keeps row stride T)
+ *   r_out[b, j] = r_in[b, j] + 1 / (H grad_scale) sum_{i < T_b} r_in[b, i] sum_h max(P_h[i, j] dP_h[i, j], 0)     (j < T_b)
+ *   r_out[b, j] = r_in[b, j]                                                                                      (T_b <= j < T)
+ * with P_h, dP_h and the fields read from d as for cclip_attention_relevance.  r_in, r_out: fp32 [B, T] contiguous and DIFFERENT
+ * buffers (a workgroup reads all of r_in[b] while others write r_out[b]).  Neither P, dP nor C is written to memory; no atomics:
+ * two launches agree bit for bit.  CCLIP_ERR_ARG, with no launch, for null pointers, r_in == r_out, head_dim != 64,
+ * grad_scale <= 0, a leading dimension that is no multiple of 8, or q / k / v / dout not 16-byte aligned. */
+int cclip_attention_relevance_row(const cclip_attn_desc* d, float grad_scale, const float* r_in, float* r_out, hipStream_t stream);
 /* Attention probabilities of one layer, T <= 256 (what HF's `output_attentions=True` returns; the reference's generate_beam
  * logs them, CLIP_prefix_caption/test.py:381-390): P[b, h, i, 0:T] = softmax_j(scale q_t k_j + mask) in fp32 for the query
  * position t = q_rows[i] (q_rows: optional int32 DEVICE array of n_q positions shared by all sequences, values clamped to
@@ -567,6 +576,8 @@ int cclip_layernorm_bwd_f16(const void* dy, int32_t dy_is_f16, int64_t lddy, con
 int cclip_attention_fwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_bwd_f16(const cclip_attn_desc* d, hipStream_t stream);
 int cclip_attention_relevance_f16(const cclip_attn_desc* d, float grad_scale, float* R, hipStream_t stream);
+int cclip_attention_relevance_row_f16(const cclip_attn_desc* d, float grad_scale, const float* r_in, float* r_out,
+                                      hipStream_t stream);
 int cclip_attention_probs_f16(const cclip_attn_desc* d, const int32_t* q_rows, int32_t n_q, float* P, int64_t ld_p_b,
                               int64_t ld_p_h, int64_t ld_p_q, hipStream_t stream);
 int cclip_attention_small_fwd_f16(const cclip_attn_desc* d, hipStream_t stream);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Relevance maps - attention.py:153 (`main`) on the MI355X `clip` package: load the model (+ a fine-tuned
-state_dict), preprocess one image, tokenize the captions, `clip.interpret`, then the patch map upsampled to 224 x 224 and
+state_dict), preprocess one image, tokenize the captions, `clip.interpret` (`clip.interpret_rows` for a tower of more than 128
+image tokens), then the patch map upsampled to 224 x 224 and
 min-max normalised (attention.py:88-92) and each caption's per-token scores (attention.py:115-117).  Written to an .npz
 (image_map [224, 224], token_scores of the first caption, and per caption token_scores_<i>, text_relevance, image_relevance)
 plus an overlay PNG next to it (PIL; the reference's cv2 / matplotlib figure is not reproduced).
@@ -66,10 +67,13 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.checkpoint, map_location="cpu", weights_only=True))
     img = preprocess(Image.open(args.image)).unsqueeze(0).to(device)                     # attention.py:161
     text = C.get_tokenize(model)(args.captions).to(device)                                # attention.py:165
-    r_text, r_image = clip.interpret(img, text, model, device=device, start_layer=args.start_layer,
-                                     start_layer_text=args.start_layer_text)
+    # more than 128 image tokens (ViT-B/16, ViT-L/14): the full T x T matrices are not offered; their rows are (text_relevance is
+    # then [N, T], each caption's EOT row)
+    long_tower = model.geo.vision_tokens > 128
+    r_text, r_image = (clip.interpret_rows if long_tower else clip.interpret)(
+        img, text, model, device=device, start_layer=args.start_layer, start_layer_text=args.start_layer_text)
     maps = clip.image_relevance_map(r_image, args.size).cpu().numpy()
-    scores = [s.cpu().numpy() for s in clip.text_token_scores(r_text, text)]
+    scores = [s.cpu().numpy() for s in (clip.text_row_scores if long_tower else clip.text_token_scores)(r_text, text)]
     out = dict(image_map=maps[0], token_scores=scores[0], text_relevance=r_text.cpu().numpy(),
                image_relevance=r_image.cpu().numpy(), tokens=text.cpu().numpy())
     for i, s in enumerate(scores):
