@@ -890,6 +890,50 @@ def resample_v_norm(tmp: torch.Tensor, row0: int, bounds: torch.Tensor, kk: torc
                                     m3, s3, _p(out), _stream()), "cclip_resample_v_norm")
 
 
+# region preprocess: K boxes in three launches, tables built on the device (csrc/preprocess_rois.hip).  `desc_host` / `desc`:
+# the same int64 [K, ROI_DESC_FIELDS] records (cclip_roi_desc) on the host, where the launcher checks them, and on the device.
+ROI_DESC_FIELDS = 11
+ROI_MAX_KSIZE = 257
+
+
+def _roi_args(desc_host: torch.Tensor, desc: torch.Tensor, n: int, ksize_max: int, bounds: torch.Tensor, kk: torch.Tensor) -> int:
+    if desc_host.is_cuda or desc_host.dtype != torch.int64:
+        raise TypeError(f"desc_host: expected cpu torch.int64, got {desc_host.device} {desc_host.dtype}")
+    _req(desc, torch.int64, "desc"); _req(bounds, torch.int32, "bounds"); _req(kk, torch.int32, "kk")
+    K = desc_host.shape[0]
+    assert desc_host.shape == (K, ROI_DESC_FIELDS) and desc.shape == (K, ROI_DESC_FIELDS) and desc_host.is_contiguous() and desc.is_contiguous()
+    assert bounds.shape == (K, 2, n, 2) and kk.shape == (K, 2, n, ksize_max) and bounds.is_contiguous() and kk.is_contiguous()
+    return K
+
+
+def roi_coeffs(desc_host: torch.Tensor, desc: torch.Tensor, n: int, ksize_max: int, bounds: torch.Tensor, kk: torch.Tensor) -> None:
+    """Fills bounds int32 [K, 2, n, 2] and kk int32 [K, 2, n, ksize_max] with PIL's windows and coefficients of every box."""
+    K = _roi_args(desc_host, desc, n, ksize_max, bounds, kk)
+    check(lib.cclip_roi_coeffs(_p(desc_host), _p(desc), c_int(K), c_int(n), c_int(ksize_max), _p(bounds), _p(kk), _stream()),
+          "cclip_roi_coeffs")
+
+
+def roi_resample_h(src: torch.Tensor, desc_host: torch.Tensor, desc: torch.Tensor, n: int, ksize_max: int, bounds: torch.Tensor,
+                   kk: torch.Tensor, tmp: torch.Tensor) -> None:
+    """src uint8 (flat, every photo of the call) -> tmp uint8 (flat): the horizontal pass of every box over the rows it needs."""
+    _req(src, torch.uint8, "src"); _req(tmp, torch.uint8, "tmp")
+    K = _roi_args(desc_host, desc, n, ksize_max, bounds, kk)
+    assert src.is_contiguous() and tmp.is_contiguous()
+    check(lib.cclip_roi_resample_h(_p(src), c_long(src.numel()), _p(desc_host), _p(desc), c_int(K), c_int(n), c_int(ksize_max), _p(bounds),
+                                   _p(kk), _p(tmp), c_long(tmp.numel()), _stream()), "cclip_roi_resample_h")
+
+
+def roi_resample_v_norm(tmp: torch.Tensor, desc_host: torch.Tensor, desc: torch.Tensor, n: int, ksize_max: int, bounds: torch.Tensor,
+                        kk: torch.Tensor, mean, std, out: torch.Tensor) -> None:
+    """tmp uint8 (flat) -> out fp32 [K, 3, n, n] = ((u8 / 255) - mean) / std of the vertical pass, cropped."""
+    _req(tmp, torch.uint8, "tmp"); _req(out, torch.float32, "out")
+    K = _roi_args(desc_host, desc, n, ksize_max, bounds, kk)
+    assert tmp.is_contiguous() and out.is_contiguous() and out.shape == (K, 3, n, n)
+    m3, s3 = (c_float * 3)(*mean), (c_float * 3)(*std)
+    check(lib.cclip_roi_resample_v_norm(_p(tmp), c_long(tmp.numel()), _p(desc_host), _p(desc), c_int(K), c_int(n), c_int(ksize_max),
+                                        _p(bounds), _p(kk), m3, s3, _p(out), _stream()), "cclip_roi_resample_v_norm")
+
+
 # --------------------------------------------------------------------------------------------
 # fp8 (e4m3) inference projections
 # --------------------------------------------------------------------------------------------

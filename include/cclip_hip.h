@@ -434,6 +434,36 @@ int cclip_resample_h_u8(const uint8_t* in, int64_t in_ld, int32_t rows, const in
 int cclip_resample_v_norm(const uint8_t* tmp, int64_t tmp_ld, int32_t row0, const int32_t* bounds, const int32_t* kk,
                           int32_t ksize, int32_t n, const float* mean3, const float* std3, float* out, hipStream_t stream);
 
+/* Region preprocess: K boxes of decoded photos -> out fp32 [K, 3, n, n], every box bit-identical to _transform(n) of the
+ * cropped box, in three launches whatever K is; the windows and coefficients are computed on the device.
+ * One descriptor per box, filled on the host (clip/preprocess_device.py:roi_descriptors) and passed twice: `desc_host` is a
+ * HOST copy that the launcher checks before it launches anything (it is not kept), `desc` the same records in device memory.
+ * The kernels read `desc` only, and a launcher cannot compare the two without a read-back: the bounds guarantee below holds
+ * only if the caller passes two identical copies (clip.DevicePreprocess uploads `desc` from `desc_host` and edits neither).
+ *   src_off, src_ld  byte offset of the box's top-left pixel in `src` and the row stride in bytes of its photo (HWC uint8
+ *                    RGB; several photos of different sizes may be packed into one buffer);
+ *   tmp_off          byte offset of the box's rows in the 8-bit intermediate (rows * n * 3 bytes, box after box);
+ *   w, h             box size; nw, nh: its size after Resize(n) on the shorter side; left, top: the centre crop;
+ *   row0, rows       the input rows (relative to the box) that the n surviving output rows read.
+ * Tables: bounds int32 [K, 2, n, 2] = (first index, count), kk int32 [K, 2, n, ksize_max]; axis 0 horizontal, 1 vertical;
+ * indices are relative to the box; only the first `count` coefficients of a row are written.  ksize_max: at least the largest
+ * ksize = 2 * ceil(2 * max(in / out, 1)) + 1 of any box and axis, at most 257 (a downscale factor of 64).
+ * CCLIP_ERR_ARG (nothing launched): a null pointer; K, n, ksize_max, src_bytes or tmp_bytes <= 0; ksize_max above 257 or
+ * below what a box needs; a descriptor whose nw / nh / left / top / row0 / rows do not fit n and its w, h, or whose source or
+ * intermediate extent leaves [0, src_bytes) / [0, tmp_bytes); src_ld above 2^36.  mean3 / std3 are HOST pointers to 3 floats. */
+typedef struct cclip_roi_desc {
+  int64_t src_off, src_ld, tmp_off;
+  int64_t w, h, nw, nh, left, top, row0, rows;
+} cclip_roi_desc;
+int cclip_roi_coeffs(const cclip_roi_desc* desc_host, const cclip_roi_desc* desc, int32_t K, int32_t n, int32_t ksize_max,
+                     int32_t* bounds_out, int32_t* kk_out, hipStream_t stream);
+int cclip_roi_resample_h(const uint8_t* src, int64_t src_bytes, const cclip_roi_desc* desc_host, const cclip_roi_desc* desc,
+                         int32_t K, int32_t n, int32_t ksize_max, const int32_t* bounds, const int32_t* kk, uint8_t* tmp,
+                         int64_t tmp_bytes, hipStream_t stream);
+int cclip_roi_resample_v_norm(const uint8_t* tmp, int64_t tmp_bytes, const cclip_roi_desc* desc_host, const cclip_roi_desc* desc,
+                              int32_t K, int32_t n, int32_t ksize_max, const int32_t* bounds, const int32_t* kk,
+                              const float* mean3, const float* std3, float* out, hipStream_t stream);
+
 /* ---- fp8 (OCP e4m3) inference projections --------------------------------------------------------
  * BASELINE.json configs[4] (ViT-L/14@336px encode_image, fp8 MFMA path).  No reference behaviour exists for fp8
  * (the reference runs fp16 / fp32): parity of this path is unpinned and bounded against the fp32 oracle by test.
