@@ -934,6 +934,52 @@ def roi_resample_v_norm(tmp: torch.Tensor, desc_host: torch.Tensor, desc: torch.
                                         _p(bounds), _p(kk), m3, s3, _p(out), _stream()), "cclip_roi_resample_v_norm")
 
 
+OVERLAY_MAX_SIDE = 16384
+
+
+def relevance_overlay(rel: torch.Tensor, images: torch.Tensor, lut: torch.Tensor, size: int, out: torch.Tensor,
+                      map_out: Optional[torch.Tensor] = None) -> None:
+    """N relevance overlays in one launch (include/cclip_hip.h, cclip_relevance_overlay): rel fp32 [N, g*g], images fp32
+    [N, 3, R, R] or [1, 3, R, R] (one image under all N maps), lut fp32 [256, 3] -> out uint8 [>= N, size, size, 3] (the first N
+    overlays are written) and, when given, map_out fp32 [N, size, size] (the min-max normalised upsampled map).  All contiguous
+    cuda tensors on one device; no CPU path.  Two calls give equal bytes."""
+    tensors = [(rel, "rel", torch.float32), (images, "images", torch.float32), (lut, "lut", torch.float32), (out, "out", torch.uint8)]
+    if map_out is not None:
+        tensors.append((map_out, "map_out", torch.float32))
+    for t, name, dt in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"relevance_overlay: {name} must be a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != dt:
+            raise ValueError(f"relevance_overlay: {name} must be {dt}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"relevance_overlay: {name} must be contiguous, got shape {tuple(t.shape)} strides {t.stride()}")
+        if t.device != rel.device:
+            raise ValueError(f"relevance_overlay: {name} is on {t.device}, rel on {rel.device}")
+    if rel.dim() != 2 or rel.shape[0] < 1:
+        raise ValueError(f"relevance_overlay: rel must be [N, g*g] with N >= 1, got {tuple(rel.shape)}")
+    N, P = rel.shape
+    g = int(round(P ** 0.5))
+    if g < 1 or g * g != P:
+        raise ValueError(f"relevance_overlay: {P} patches do not form a square grid")
+    if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] != images.shape[3] or images.shape[2] < 1:
+        raise ValueError(f"relevance_overlay: images must be [N, 3, R, R], got {tuple(images.shape)}")
+    if images.shape[0] not in (1, N):
+        raise ValueError(f"relevance_overlay: {images.shape[0]} images for {N} maps (give one image, or one per map)")
+    R = images.shape[2]
+    if int(size) != size or not 1 <= size <= OVERLAY_MAX_SIDE or max(g, R) > OVERLAY_MAX_SIDE:
+        raise ValueError(f"relevance_overlay: size {size}, grid {g}, resolution {R}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    size = int(size)
+    if tuple(lut.shape) != (256, 3):
+        raise ValueError(f"relevance_overlay: lut must be [256, 3], got {tuple(lut.shape)}")
+    if out.dim() != 4 or out.shape[0] < N or tuple(out.shape[1:]) != (size, size, 3):
+        raise ValueError(f"relevance_overlay: out must be [>= {N}, {size}, {size}, 3], got {tuple(out.shape)}")
+    if map_out is not None and tuple(map_out.shape) != (N, size, size):
+        raise ValueError(f"relevance_overlay: map_out must be [{N}, {size}, {size}], got {tuple(map_out.shape)}")
+    stride = 0 if images.shape[0] == 1 else 3 * R * R
+    check(lib.cclip_relevance_overlay(_p(rel), c_int(N), c_int(g), _p(images), c_long(stride), c_int(R), _p(lut), c_int(size), _p(out),
+                                      _p(map_out), _stream()), "cclip_relevance_overlay")
+
+
 # --------------------------------------------------------------------------------------------
 # fp8 (e4m3) inference projections
 # --------------------------------------------------------------------------------------------

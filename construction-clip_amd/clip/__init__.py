@@ -8,5 +8,6 @@ from .loss import sigmoid_loss, SigmoidLoss  # noqa: F401  (SigLIP's pairwise si
 from .preprocess_device import DevicePreprocess  # noqa: F401
 from .explain import interpret, image_relevance_map, text_token_scores  # noqa: F401  (attention.py:14, 88-92, 115-117)
 from .explain import interpret_rows, text_row_scores  # noqa: F401  (the same rows for towers of more than 128 tokens)
+from .explain import jet_table, relevance_overlay, text_heat_html  # noqa: F401  (attention.py:77-96, 113-143: the overlay picture)
 from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)

@@ -10,13 +10,20 @@ is no autograd through them.
 interpret() forms the whole T x T matrices and so ends at 128 tokens (ViT-B/32).  interpret_rows() returns exactly the rows the
 reference's callers read - the class-token row of the image tower and each caption's EOT row - through a streaming row kernel
 (csrc/attention_relevance_row.hip) at any sequence length: ViT-B/16, ViT-L/14, ViT-L/14@336px.
+
+relevance_overlay() is show_image_relevance's picture (attention.py:77-96): the upsampled, normalised map through a colour
+table, added to the min-max normalised image and rescaled to 8 bits, for N maps in one launch (csrc/relevance_overlay.hip).
+text_heat_html() is a dependency-free stand-in for show_heatmap_on_text's captum record (attention.py:113-143).
 """
 from __future__ import annotations
 
-from typing import List, Tuple, Union
+import html
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn.functional as F
+
+from cclip_hip import ops
 
 
 def interpret(image: torch.Tensor, texts: torch.Tensor, model, device=None, start_layer: int = -1,
@@ -89,3 +96,80 @@ def text_row_scores(text_relevance_row: torch.Tensor, tokens: torch.Tensor) -> U
     eot = int(tokens.argmax(dim=-1))
     r = text_relevance_row[1:eot].float()
     return r / r.sum()
+
+
+def jet_table() -> torch.Tensor:
+    """The default colour table of relevance_overlay: fp32 [256, 3], row k = the blue-cyan-yellow-red ramp at t = k / 255,
+    r = clip(1.5 - |4t - 3|, 0, 1), g = clip(1.5 - |4t - 2|, 0, 1), b = clip(1.5 - |4t - 1|, 0, 1), channel order RGB (row 0 is
+    blue, row 255 red).  It stands in for cv2.COLORMAP_JET: cv2 is not a dependency of this package.  cv2's own table - or any
+    other [256, 3] table with values in [0, 1] - can be passed as `lut=`; reverse its last axis first, cv2 tables are BGR.  The
+    reference adds the BGR heat map to the RGB image and swaps the sum once more (attention.py:78-80, 97), so its hot patches
+    come out blue; that accident is not reproduced: hot is red here."""
+    t = torch.arange(256, dtype=torch.float64) / 255
+    return torch.stack([(1.5 - (4 * t - c).abs()).clamp(0, 1) for c in (3, 2, 1)], dim=1).float()
+
+
+_JET = {}
+
+
+def relevance_overlay(image_relevance: torch.Tensor, image: torch.Tensor, size: int = 224, lut: Optional[torch.Tensor] = None,
+                      return_map: bool = False):
+    """attention.py:77-96 (show_image_relevance without the matplotlib figure) on the device: image_relevance fp32 [N, grid*grid]
+    as a grid, bilinearly upsampled to size x size and min-max normalised (image_relevance_map), looked up in the colour table
+    (row min(floor(255 m), 255)), added to the image - fp32 [N, 3, R, R], or [1, 3, R, R] under all N maps - resampled to
+    size x size and min-max normalised, and the sum scaled by its maximum to 8 bits.  Returns uint8 [N, size, size, 3] (HWC, RGB:
+    `Image.fromarray(overlay[i].cpu().numpy())`) on the device of the inputs; with return_map also the fp32 [N, size, size]
+    normalised maps.  image_relevance [grid*grid] with image [3, R, R] gives one [size, size, 3] (and [size, size]).
+    lut: fp32 [256, 3] with values in [0, 1]; default jet_table().  One launch for all N; the map, the normalised image and the
+    blend are never stored.  The inputs must be contiguous float32 cuda tensors."""
+    single = image_relevance.dim() == 1
+    rel = image_relevance.detach()
+    img = image.detach()
+    if single:
+        rel = rel.unsqueeze(0)
+    if img.dim() == 3:
+        img = img.unsqueeze(0)
+    if rel.dim() != 2 or rel.shape[0] < 1:
+        raise ValueError(f"relevance_overlay: image_relevance must be [grid*grid] or [N, grid*grid], got {tuple(image_relevance.shape)}")
+    N, P = rel.shape
+    dim = int(round(P ** 0.5))
+    if dim < 1 or dim * dim != P:
+        raise ValueError(f"relevance_overlay: {P} patches do not form a square grid")
+    if img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"relevance_overlay: image must be [3, R, R] or [N, 3, R, R], got {tuple(image.shape)}")
+    if img.shape[0] not in (1, N):
+        raise ValueError(f"relevance_overlay: {img.shape[0]} images for {N} maps (give one image, or one per map)")
+    if lut is not None and tuple(lut.shape) != (256, 3):
+        raise ValueError(f"relevance_overlay: lut must be [256, 3], got {tuple(lut.shape)}")
+    dev = rel.device
+    if lut is None:
+        if dev not in _JET:
+            _JET[dev] = jet_table().to(dev)
+        lut = _JET[dev]
+    else:
+        lut = lut.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if not rel.is_cuda:
+        raise ValueError(f"relevance_overlay: expected cuda tensors, got {dev} (no CPU path)")
+    out = torch.empty(N, size, size, 3, device=dev, dtype=torch.uint8)
+    m = torch.empty(N, size, size, device=dev, dtype=torch.float32) if return_map else None
+    ops.relevance_overlay(rel, img, lut, size, out, m)
+    if single:
+        out, m = out[0], (m[0] if return_map else None)
+    return (out, m) if return_map else out
+
+
+def text_heat_html(pieces: Sequence[str], scores) -> str:
+    """Host-only stand-in for show_heatmap_on_text's captum record (attention.py:113-143): one <span> per piece of the caption on a
+    red background whose alpha is the piece's score over the largest score (scores <= 0 stay transparent), the text HTML-escaped.
+    pieces: the caption's tokens (or characters); scores: as many numbers (a tensor, an array or a list) - text_row_scores of the
+    caption, or its sums per piece."""
+    vals = [float(s) for s in (scores.tolist() if hasattr(scores, "tolist") else scores)]
+    pieces = list(pieces)
+    if len(vals) != len(pieces):
+        raise ValueError(f"text_heat_html: {len(pieces)} pieces, {len(vals)} scores")
+    top = max(vals, default=0.0)
+    spans = []
+    for piece, v in zip(pieces, vals):
+        alpha = min(max(v / top, 0.0), 1.0) if top > 0 and v == v else 0.0
+        spans.append(f'<span style="background-color: rgba(255, 0, 0, {alpha:.3f})" title="{v:.4f}">{html.escape(str(piece))}</span>')
+    return '<div class="text-heat" style="font-family: sans-serif; line-height: 1.8">' + "".join(spans) + "</div>"

@@ -116,6 +116,7 @@ class Captioner:
         caption_types = dict(CAPTION_TYPES if caption_types is None else caption_types)
         violation_types = list(VIOLATION_TYPES if violation_types is None else violation_types)
         self.clip_model, self.caption_model, self.tokenizer = clip_model, caption_model, tokenizer
+        self.clip_tokenize = clip_tokenize                                 # explain() tokenises the generated captions with it
         self.prefix_length, self.attribute_length = prefix_length, attribute_length
         self.caption_labels, self.violation_labels = list(caption_types.values()), violation_types
         self.attributes = attribute_strings(self.caption_labels, self.violation_labels)
@@ -238,3 +239,36 @@ class Captioner:
             return records
         return records, {"ids": torch.cat([e["ids"] for e in extras]), "index": torch.cat([e["index"] for e in extras]),
                          "tokens": [t for e in extras for t in e["tokens"]]}
+
+    def _caption_tokens(self, texts: List[str]) -> torch.Tensor:
+        """CLIP token rows of generated captions; an over-long caption is cut where clip_tokenize can do that (`truncate`)"""
+        import inspect
+        try:
+            cut = "truncate" in inspect.signature(self.clip_tokenize).parameters
+        except (TypeError, ValueError):
+            cut = False
+        return (self.clip_tokenize(texts, truncate=True) if cut else self.clip_tokenize(texts)).to(self.device)
+
+    def explain(self, images, size: int = 224, relevance_model=None, start_layer: int = -1, start_layer_text: int = -1, lut=None,
+                **describe_kwargs):
+        """Caption plus why, for a batch (the reference's root predict.py:57-86 per photo): `describe(images)`, the N predictions
+        tokenised with clip_tokenize, `clip.interpret_rows` of every (image, own caption) pair on relevance_model (default: the
+        Captioner's CLIP model; the reference loads a second checkpoint for this, predict.py:46,50), then `clip.relevance_overlay`
+        and `clip.text_row_scores`.  Returns describe's records, each extended with "overlay" (uint8 [size, size, 3] numpy, RGB),
+        "image_relevance" (fp32 [patches]), "token_scores" (fp32 over the caption's tokens 1 .. EOT-1, summing to 1) and
+        "clip_tokens" (the caption's CLIP token row), the last three on the device.  The overlays of the whole batch come back
+        in one copy.  size / lut: as for clip.relevance_overlay; describe_kwargs go to describe (with return_tokens=True the
+        result is (records, extras), as there)."""
+        import clip
+        images = self._images(images)
+        res = self.describe(images, **describe_kwargs)
+        records = res[0] if describe_kwargs.get("return_tokens") else res
+        tokens = self._caption_tokens([r["prediction"] for r in records])
+        model = self.clip_model if relevance_model is None else relevance_model
+        r_text, r_image = clip.interpret_rows(images, tokens, model, device=self.device, start_layer=start_layer,
+                                              start_layer_text=start_layer_text)
+        overlays = clip.relevance_overlay(r_image.contiguous(), images.float().contiguous(), size=size, lut=lut).cpu().numpy()
+        scores = clip.text_row_scores(r_text, tokens)
+        for i, rec in enumerate(records):
+            rec.update(overlay=overlays[i], image_relevance=r_image[i], token_scores=scores[i], clip_tokens=tokens[i])
+        return res

@@ -590,6 +590,23 @@ typedef struct cclip_beam_batch_desc {
 } cclip_beam_batch_desc;
 int cclip_gpt2_beam_search_batch(const cclip_beam_batch_desc* d, hipStream_t stream);
 
+/* ---- relevance overlays --------------------------------------------------------------------------
+ * N patch-relevance vectors and their images -> N finished 8-bit RGB overlays in one launch (csrc/relevance_overlay.hip; the
+ * reference's show_image_relevance, attention.py:77-96).  For output pixel (y, x) of overlay n, everything in fp32:
+ *   bil(src, L, i): F.interpolate(mode="bilinear", align_corners=False) - s = max((i + 0.5) L / S - 0.5, 0), i0 = floor(s),
+ *                   i1 = min(i0 + 1, L - 1), weight s - i0, separable in y and x;
+ *   u = bil of the g x g grid, m = (u - min u) / (max u - min u) over the S x S pixels (0 when the range is 0);
+ *   v_c = bil of image channel c, xn_c = (v_c - min v) / (max v - min v) over all 3 S S values (0 when the range is 0);
+ *   k = min(floor(255 m), 255), cam_c = lut[k][c] + xn_c, M = max cam over all 3 S S values;
+ *   out[n][y][x][c] = floor(255 (cam_c / M)), 0 when M == 0 (values outside [0, 255] - a negative table entry - saturate).
+ * rel: fp32 [N][g*g].  images: fp32 [3][R][R] per overlay, overlay n's at images + n * image_stride floats; image_stride 0 =
+ *   one image shared by all N maps, otherwise >= 3 R R.  lut: fp32 [256][3].  out: uint8 [N][S][S][3], any alignment.
+ * map_out: NULL, or fp32 [N][S][S] that receives m.  1 <= g, R, S <= CCLIP_OVERLAY_MAX_SIDE.
+ * One work-group per overlay, no atomics: two calls give the same bytes. */
+#define CCLIP_OVERLAY_MAX_SIDE 16384
+int cclip_relevance_overlay(const float* rel, int32_t N, int32_t g, const float* images, int64_t image_stride, int32_t R,
+                            const float* lut, int32_t S, uint8_t* out, float* map_out, hipStream_t stream);
+
 /* ---- IEEE fp16 twins ---------------------------------------------------------------------------
  * Every entry point above whose 16-bit buffers are bf16 has a twin with the identical signature that
  * treats them as IEEE fp16 (same MFMA rate on gfx950; 3 more mantissa bits - the reference's own CUDA
