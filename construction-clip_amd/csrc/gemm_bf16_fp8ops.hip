@@ -22,7 +22,7 @@ namespace CCLIP_NS {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 
-// ---- per-row quantisation: x16 [rows, cols] -> e4m3 [rows, cols] + scale[rows] (scale = amax / 448; 1 for an all-zero row)
+// ---- per-row quantisation: x16 [rows, cols] -> e4m3 [rows, cols] + scale[rows] (scale = amax / 448, at least 2^-126; 1 for an all-zero row)
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16* __restrict__ x, long ldx, int rows, int cols,
                                                                 unsigned char* __restrict__ out, long ldo, float* __restrict__ scale) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -35,7 +35,8 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16* __re
       for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf((float)v[j]));
     }
     amax = wave_max(amax);
-    const float s = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    // (the floor keeps 1 / s finite: below amax = 448 / FLT_MAX the quotient is an fp32 subnormal, 1 / s = inf and 0 * inf = NaN went out as -448)
+    const float s = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), 0x1p-126f) : 1.0f;
     const float inv = 1.0f / s;
     for (int c = lane * 8; c < cols; c += 512) {
       const bf16x8 v = *(const bf16x8*)(xr + c);
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16* __re
 }
 
 // LayerNorm whose output goes straight to e4m3 + per-row scale: the quantisation of the LN-fed projections' A operand costs
-// no extra pass (the row is in registers anyway).  Same statistics as ln_fwd_kernel (layernorm.hip).
+// no extra pass (the row is in registers anyway).  Statistics as ln_fwd_kernel (layernorm.hip), plus a correction of the mean.
 template <int NV>
 __global__ __launch_bounds__(256) void ln_fwd_fp8_kernel(const float* __restrict__ x, long ldx, int rows, int D,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -72,31 +73,37 @@ __global__ __launch_bounds__(256) void ln_fwd_fp8_kernel(const float* __restrict
       s += v[c].x + v[c].y + v[c].z + v[c].w;
     }
     const float mean = wave_sum(s) * inv_d;
-    float q = 0.f;
+    // The fp32 mean is off by up to half an ulp of itself plus the sum's rounding - for a row whose mean is far above its spread
+    // (1000 +- 1: 5e-5, the size of the whole LayerNorm tolerance) that error went into every output.  x - mean is exact there, so
+    // the mean of the centred values measures what the mean missed: dm, taken off again below (same pass as the squares: the two
+    // reductions are independent).  Ordinary rows: dm is a few 1e-8 and moves nothing but last bits.
+    float q = 0.f, e = 0.f;
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       const int col = c * 256 + lane * 4;
       if (col < D) {
-        const float a = v[c].x - mean, b = v[c].y - mean, cc = v[c].z - mean, d = v[c].w - mean;
-        q += a * a + b * b + cc * cc + d * d;
+        v[c].x -= mean; v[c].y -= mean; v[c].z -= mean; v[c].w -= mean;
+        e += v[c].x + v[c].y + v[c].z + v[c].w;
+        q += v[c].x * v[c].x + v[c].y * v[c].y + v[c].z * v[c].z + v[c].w * v[c].w;
       }
     }
-    const float rstd = rsqrtf(wave_sum(q) * inv_d + eps);
+    const float dm = wave_sum(e) * inv_d;
+    const float rstd = rsqrtf(fmaxf(wave_sum(q) * inv_d - dm * dm, 0.f) + eps);    // sum (d - dm)^2 = sum d^2 - D dm^2
     float amax = 0.f;
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       const int col = c * 256 + lane * 4;
       if (col < D) {
         const float4 g = *(const float4*)(gamma + col), b = *(const float4*)(beta + col);
-        v[c].x = (v[c].x - mean) * rstd * g.x + b.x;
-        v[c].y = (v[c].y - mean) * rstd * g.y + b.y;
-        v[c].z = (v[c].z - mean) * rstd * g.z + b.z;
-        v[c].w = (v[c].w - mean) * rstd * g.w + b.w;
+        v[c].x = (v[c].x - dm) * rstd * g.x + b.x;
+        v[c].y = (v[c].y - dm) * rstd * g.y + b.y;
+        v[c].z = (v[c].z - dm) * rstd * g.z + b.z;
+        v[c].w = (v[c].w - dm) * rstd * g.w + b.w;
         amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[c].x), fabsf(v[c].y))), fmaxf(fabsf(v[c].z), fabsf(v[c].w)));
       }
     }
     amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
+    const float sc = amax > 0.f ? fmaxf(amax * (1.0f / 448.0f), 0x1p-126f) : 1.0f;   // (floored as in quantize_rows_fp8_kernel)
     const float inv = 1.0f / sc;
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
