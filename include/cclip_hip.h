@@ -219,7 +219,9 @@ int cclip_attention_decode(const void* q, int64_t ldq, const void* kcache, const
  * C[m*ldc+n] = alpha' * sum_k A[m*sam + k*sak] * B[n*sbn + k*sbk] + beta * C[m*ldc+n], with
  * alpha' = alpha * (alpha_log_dev ? exp(*alpha_log_dev) : 1)  (logit_scale.exp() without a host sync).
  * Replaces `x @ visual.proj`, `x @ text_projection`, `logit_scale.exp() * I @ T.t()` of
- * CLIP.forward/encode_* and their backward products (tiny, accuracy critical). */
+ * CLIP.forward/encode_* and their backward products (tiny, accuracy critical).
+ * beta == 0: C is an output only - it is not read, so NaN or uninitialised memory in it does not reach the result.
+ * alpha' == 0 does not skip the product: a NaN or inf in A or B still reaches C. */
 int cclip_gemm_f32(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbn, int64_t sbk,
                    int32_t M, int32_t N, int32_t K, float alpha, const float* alpha_log_dev, float beta,
                    float* C, int64_t ldc, hipStream_t stream);
@@ -233,6 +235,11 @@ int cclip_gemm_f32(const float* A, int64_t sam, int64_t sak, const float* B, int
  * cclip_vit_embed_ln: x0 = patch_out + positional_embedding[t] (+ class_embedding at t = 0),
  *   x = ln_pre(x0); optional saves x0, mean, rstd.  All fp32 [rows = B*T, D].
  * cclip_text_embed: x[r] = token_embedding[text[r]] + positional_embedding[r % L] (pos may be NULL).
+ *   Token ids outside [0, V) are clamped to the nearest end of the table by the kernels of cclip_text_embed, cclip_caption_embed
+ *   and cclip_embed_scatter_add (never an out-of-bounds access; tests/test_kernels_f32_gpu.py pins it).  The deterministic
+ *   gradient does NOT clamp at this level: cclip_embed_tables / cclip_embed_segsum take tok_sorted as given and require ids in
+ *   [0, V] (V itself = a dropped row; a negative id would index demb out of bounds) - the host wrapper
+ *   (cclip_hip/ops.py embed_scatter_tables) clamps to [0, V - 1] before it sorts.
  * cclip_embed_scatter_add: ids are [n, L]; demb[text[r]] += dx[(r/L)*seq_stride + seq_off + r%L]  (fp32 atomics - hardware
  *   order, kept as the one-launch alternative; the default host path uses cclip_embed_segsum below;
  *   text tower: L = seq_stride = 77, seq_off = 0; caption model: the token part of a longer sequence).
@@ -354,10 +361,17 @@ int cclip_sample_rows(const float* logits, int64_t ld, int32_t n, int32_t V, flo
 
 /* ---- loss side (fp32) ------------------------------------------------------------------------
  * cclip_l2norm_fwd/bwd: y = x / ||x||_2 per row (image_features / image_features.norm(dim=1)).
+ *   No epsilon, as in the reference: a row of zeros gives y = 0 * rsqrt(0) = NaN in every column and inv_norm = +inf - what
+ *   x / x.norm() gives in torch; other rows are unaffected.
  * cclip_xent_rows: per row r with label labels[r]: loss_row = logsumexp(row) - row[label]
  *   (0 when label == ignore_index), pred = argmax(row) (first max), and, if dlogits != NULL,
  *   dlogits = (softmax(row) - onehot) * grad_scale (fp32, may alias logits; or bf16, must not);
  *   rowdot (optional) = sum_c dlogits[c] * logits[c]  (the d/d(logit_scale) contribution of the row);
+ *   a row is ignored (loss 0, a gradient row of exact zeros, rowdot 0) when label == ignore_index, label < 0 or label >= C.
+ *   FINITE LOGITS ONLY: both callers (clip/loss.py, clip_caption/model.py) pass GEMM outputs and nothing masks a logit.  A -inf
+ *   that is the first element a lane reads (any of the first 64 columns) turns the row's loss and gradient into NaN (the running
+ *   maximum forms exp(-inf - -inf)); a -inf in a later column gets probability 0 and leaves loss, gradient and pred those of
+ *   the finite columns, but rowdot (0 * -inf) is NaN; a NaN or +inf logit is undefined.
  *   l2norm_bwd's mul_dev (optional) is a device scalar the result is multiplied by (upstream dloss).
  *   Replaces torch.nn.CrossEntropyLoss + torch.argmax of CLIP/train.py:162-173 and
  *   nnf.cross_entropy(ignore_index=0) of CLIP_prefix_caption/train.py:357. */
