@@ -580,6 +580,24 @@ def _attn_cu(d, cu, B):
         d.cu_seqlens = cu.data_ptr()
 
 
+def _attn_grads(d, dout, dq, dk, dv):
+    d.dout, d.lddo = dout.data_ptr(), dout.stride(-2)
+    d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    d.lddq, d.lddk, d.lddv = dq.stride(-2), dk.stride(-2), dv.stride(-2)
+
+
+def _relevance_desc(q, k, v, lse, da, B, T, H, causal, scale, cu):
+    """the descriptor both relevance kernels read: da (the gradient at the attention output) travels in the dout fields"""
+    _req16(da, "da")
+    assert da.stride(-1) == 1
+    _req(lse, torch.float32, "lse")
+    assert lse.is_contiguous() and lse.numel() >= B * H * T
+    d = _attn_desc(q, k, v, da, lse, B, T, H, causal, None, scale)     # (o is not read: da stands in as the dtype witness)
+    _attn_cu(d, cu, B)
+    d.dout, d.lddo = da.data_ptr(), da.stride(-2)
+    return d
+
+
 def attention_fwd(q, k, v, o, *, B: int, T: int, H: int, causal: bool = False, key_keep=None, lse=None, scale=None, out_mx=None,
                   cu=None) -> None:
     """q/k/v/o: bf16 2-D views [B*T, >= H*64] (any row stride, inner stride 1); head h at columns h*64..
@@ -601,9 +619,7 @@ def attention_bwd(q, k, v, o, lse, dout, dq, dk, dv, *, B: int, T: int, H: int, 
                   scale=None, cu=None) -> None:
     d = _attn_desc(q, k, v, o, lse, B, T, H, causal, key_keep, scale)
     _attn_cu(d, cu, B)
-    d.dout, d.lddo = dout.data_ptr(), dout.stride(-2)
-    d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-    d.lddq, d.lddk, d.lddv = dq.stride(-2), dk.stride(-2), dv.stride(-2)
+    _attn_grads(d, dout, dq, dk, dv)
     check(_fn("cclip_attention_bwd", q, k, v, o, dout, dq, dk, dv)(ctypes.byref(d), _stream()), "cclip_attention_bwd")
 
 
@@ -613,15 +629,9 @@ def attention_relevance(q, k, v, lse, da, R, *, B: int, T: int, H: int, causal: 
     P = softmax(scale q k^T) (rebuilt from the forward's lse) and dP = da v^T, then R[b, :T_b, :T_b] += R[b, :T_b, :T_b] C.
     q/k/v/da as for attention_bwd (da = the gradient at the attention output); lse fp32 [B, H, T]; R fp32 [B, T, T] contiguous,
     updated in place (rows / columns >= T_b of a packed sequence are left as they are)."""
-    _req16(da, "da")
-    assert da.stride(-1) == 1
-    _req(lse, torch.float32, "lse")
+    d = _relevance_desc(q, k, v, lse, da, B, T, H, causal, scale, cu)
     _req(R, torch.float32, "R")
     assert R.is_contiguous() and tuple(R.shape) == (B, T, T), f"R: expected contiguous [{B}, {T}, {T}], got {tuple(R.shape)}"
-    assert lse.is_contiguous() and lse.numel() >= B * H * T
-    d = _attn_desc(q, k, v, da, lse, B, T, H, causal, None, scale)     # (o is not read: da stands in as the dtype witness)
-    _attn_cu(d, cu, B)
-    d.dout, d.lddo = da.data_ptr(), da.stride(-2)
     check(_fn("cclip_attention_relevance", q, k, v, da)(ctypes.byref(d), c_float(grad_scale), _p(R), _stream()),
           "cclip_attention_relevance")
 
@@ -631,16 +641,10 @@ def attention_relevance_row(q, k, v, lse, da, r_in, r_out, *, B: int, T: int, H:
     """One row of attention_relevance's update at any T <= 8192: r_out[b, :T_b] = r_in[b, :T_b] + r_in[b, :T_b] C with the same
     C (never formed), r_out[b, T_b:] = r_in[b, T_b:].  q/k/v/lse/da as for attention_relevance; r_in, r_out fp32 [B, T]
     contiguous and different buffers (the library refuses r_in is r_out)."""
-    _req16(da, "da")
-    assert da.stride(-1) == 1
-    _req(lse, torch.float32, "lse")
+    d = _relevance_desc(q, k, v, lse, da, B, T, H, causal, scale, cu)
     for r, n in ((r_in, "r_in"), (r_out, "r_out")):
         _req(r, torch.float32, n)
         assert r.is_contiguous() and tuple(r.shape) == (B, T), f"{n}: expected contiguous [{B}, {T}], got {tuple(r.shape)}"
-    assert lse.is_contiguous() and lse.numel() >= B * H * T
-    d = _attn_desc(q, k, v, da, lse, B, T, H, causal, None, scale)     # (o is not read: da stands in as the dtype witness)
-    _attn_cu(d, cu, B)
-    d.dout, d.lddo = da.data_ptr(), da.stride(-2)
     check(_fn("cclip_attention_relevance_row", q, k, v, da)(ctypes.byref(d), c_float(grad_scale), _p(r_in), _p(r_out), _stream()),
           "cclip_attention_relevance_row")
 
@@ -850,9 +854,7 @@ def attention_small_fwd(q, k, v, o, *, B: int, T: int, H: int, head_dim: int, ls
 
 def attention_small_bwd(q, k, v, o, lse, dout, dq, dk, dv, *, B: int, T: int, H: int, head_dim: int, scale=None) -> None:
     d = _attn_desc(q, k, v, o, lse, B, T, H, False, None, scale, head_dim)
-    d.dout, d.lddo = dout.data_ptr(), dout.stride(-2)
-    d.dq, d.dk, d.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-    d.lddq, d.lddk, d.lddv = dq.stride(-2), dk.stride(-2), dv.stride(-2)
+    _attn_grads(d, dout, dq, dk, dv)
     check(_fn("cclip_attention_small_bwd", q, k, v, o, dout, dq, dk, dv)(ctypes.byref(d), _stream()), "cclip_attention_small_bwd")
 
 

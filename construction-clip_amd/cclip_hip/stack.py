@@ -539,17 +539,16 @@ class BlockStack:
                         self._wgrad(dxb, a, gr["w_o"], M, A("w_o", gr), sc, gr["b_o"], A("b_o", gr), pad=True)
                     leaf(f3)
                 ops.gemm_bf16(dxb, wd("w_o")[0], b_kcontig=wd("w_o")[1], out_bf16=dsm, M=M)
-            if rel_row is not None:
-                assert geo.head_dim == 64, "attention relevance: head_dim 64"
-                ops.attention_relevance_row(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], lse[l], dsm, rel_row[0], rel_row[1],
-                                            B=B, T=T, H=H, causal=geo.causal, cu=saved.get("cu"), grad_scale=relevance[2])
-                rel_row.reverse()
-                if l <= relevance[1]:
-                    break
-            elif relevance is not None:
-                assert geo.head_dim == 64 and T <= 128, "attention relevance: head_dim 64, T <= 128"
-                ops.attention_relevance(qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], lse[l], dsm, relevance[0], B=B, T=T,
-                                        H=H, causal=geo.causal, cu=saved.get("cu"), grad_scale=relevance[2])
+            if relevance is not None:
+                rel_in = (qkv[:, 0:D], qkv[:, D:2 * D], qkv[:, 2 * D:3 * D], lse[l], dsm)
+                rel_kw = dict(B=B, T=T, H=H, causal=geo.causal, cu=saved.get("cu"), grad_scale=relevance[2])
+                if rel_row is not None:
+                    assert geo.head_dim == 64, "attention relevance: head_dim 64"
+                    ops.attention_relevance_row(*rel_in, rel_row[0], rel_row[1], **rel_kw)
+                    rel_row.reverse()
+                else:
+                    assert geo.head_dim == 64 and T <= 128, "attention relevance: head_dim 64, T <= 128"
+                    ops.attention_relevance(*rel_in, relevance[0], **rel_kw)
                 if l <= relevance[1]:
                     break
             if geo.head_dim == 64:

@@ -16,9 +16,9 @@
 //   backward S = Q K^T, dP = dO V^T (query on accumulator rows): P and dS are the B operands of
 //            dV^T = dO^T P and dK^T = Q^T dS with no data movement; only dS crosses LDS once,
 //            for dQ^T = K^T dS^T.  Each wave owns key tiles, so dK/dV need no cross-wave sums.
-// LDS images are [row][64] bf16 with 128-byte rows, 16-byte chunk c of row r stored at
-// chunk c ^ (r & 7): conflict-free for both ds_read_b128 row reads and the transposed reads.
-#include "cclip_common.h"
+// LDS images are [row][64] bf16 in the swizzled layout of attention_tiles.h, which also holds the fragment reads and the
+// staging helpers (head_load / head_store for a whole slice, blk_load / blk_store for 64 rows of one).
+#include "attention_tiles.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
@@ -75,41 +75,6 @@ __device__ __forceinline__ void attn_store_mx(const AttnArgs& a, long row, int h
     *(int*)(op + 16 * dt) = w;
   }
   if (g == 0) *(unsigned short*)(a.omx + (long)(h >> 1) * a.ldomx + 4 * row + ((2 * h) & 3)) = (unsigned short)(e[0] | (e[1] << 8));
-}
-
-__device__ __forceinline__ int at_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
-// A-operand fragment of X^T (16 columns d0..d0+15 as MFMA rows) over 8 rows given as two 4-row blocks
-__device__ __forceinline__ bf16x8 frag_tr(const char* img, int rowblk0, int rowblk1, int dt, int lane) {
-  const int q = (lane >> 2) & 3, p = lane & 3;
-  const int chunk = 2 * dt + (p >> 1), sub = 8 * (p & 1);
-  const bf16x4 lo = lds_read_tr16(img + at_off(rowblk0 + q, chunk) + sub);
-  const bf16x4 hi = lds_read_tr16(img + at_off(rowblk1 + q, chunk) + sub);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ bf16x8 frag_row(const char* img, int row, int chunk) {
-  return *(const bf16x8*)(img + at_off(row, chunk));
-}
-
-// Staging of a [T][64] head slice into LDS in two halves: head_load issues every 16-byte global load of the slice (IT per
-// thread, rows clamped so that no load is predicated) and head_store writes them to the swizzled image, zeroing rows >= T.
-// All loads of all operands go out before the first wait: a predicated load -> wait -> ds_write loop costs one HBM round
-// trip per iteration (8-10 serial round trips were most of a T=50 workgroup's life, rocprofv3 + ISA).
-template <int IT>
-__device__ __forceinline__ void head_load(const bf16* g, long ld, long row0, int T, uint4 (&r)[IT], int tid) {
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int idx = tid + 256 * it, row = idx >> 3, c = idx & 7;
-    r[it] = *(const uint4*)(g + (row0 + (row < T ? row : T - 1)) * ld + c * 8);
-  }
-}
-template <int IT>
-__device__ __forceinline__ void head_store(char* img, int T, int rows_total, const uint4 (&r)[IT], int tid) {
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int idx = tid + 256 * it, row = idx >> 3, c = idx & 7;
-    if (row < rows_total) *(uint4*)(img + at_off(row, c)) = row < T ? r[it] : make_uint4(0, 0, 0, 0);
-  }
 }
 
 template <int NKT>
@@ -515,24 +480,7 @@ __global__ __launch_bounds__(256) void attn_long_fwd_kernel(const AttnArgs a, in
 // the query axis (dQ).  Both recompute S and dP from the saved log-sum-exp, as the short kernel does; delta = rowsum(dO*O)
 // is recomputed per staged query block.  Same operand roles as attn_bwd_kernel: query on accumulator rows, so P and dS
 // are B operands of dV^T = dO^T P and dK^T = Q^T dS without data movement; dS crosses LDS once for dQ^T = K^T dS^T.
-//
-// Staging of 64 rows [r0, r0+64) of a [T][64] head slice, split as in the short kernels: blk_load requests the thread's
-// two 16-byte chunks (rows clamped: no predicated load), blk_store writes them to the swizzled image (zero rows >= T).
-// Between the two a kernel keeps the NEXT block's chunks in registers while the current block is multiplied.
-__device__ __forceinline__ void blk_load(const bf16* g, long ld, long row0, int r0, int T, uint4 (&r)[2], int tid) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = r0 + (tid >> 3) + 32 * i;
-    r[i] = *(const uint4*)(g + (row0 + (row < T ? row : T - 1)) * ld + (tid & 7) * 8);
-  }
-}
-__device__ __forceinline__ void blk_store(char* img, int r0, int T, const uint4 (&r)[2], int tid) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = (tid >> 3) + 32 * i;
-    *(uint4*)(img + at_off(row, tid & 7)) = r0 + row < T ? r[i] : make_uint4(0, 0, 0, 0);
-  }
-}
+// Rows are staged 64 at a time with blk_load / blk_store (attention_tiles.h).
 // one query block's Q, dO, O chunks and log-sum-exp in registers
 struct QBlockRegs { uint4 q[2], d[2], o[2]; float lse; };
 __device__ __forceinline__ void qblk_load(const AttnArgs& a, long row0, int b, int h, int q0, QBlockRegs& r, int tid) {

@@ -10,12 +10,13 @@
 // registers.  The forward's lse is not read: the kernel needs nothing but q and k, and a row sums to 1 to fp32 rounding.
 //
 // One work-group (4 waves) per (b, h, block of 64 query rows); wave w owns rows 16w .. 16w+15 of the block.  K of the
-// (b, h) is staged once in LDS ([row][64] 16-bit, 16-byte chunk c of row r at chunk c ^ (r & 7): the layout of
-// attention_relevance.hip, conflict-free for the B-fragment reads); Q rows go straight from memory into the A fragments.
+// (b, h) is staged once in LDS in the swizzled [row][64] image of attention_tiles.h (at_off / frag_row, conflict-free for the
+// B-fragment reads) by a loop of its own: through head_load / head_store the kernel measured 4 % slower per launch at
+// B H = 36, T = 140, with everything after the barrier unchanged.  Q rows go straight from memory into the A fragments.
 // S = Q K^T is v_mfma_f32_16x16x32 with the query on the accumulator rows: lane (li, g) holds rows 4g .. 4g+3, column
 // (key) 16 kt + li of tile kt, so a row's reduction is over kt in registers and over the 16 lanes of a group by xor-shuffles.
 // Fixed order, no atomics: two launches are bitwise equal.
-#include "cclip_common.h"
+#include "attention_tiles.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
@@ -29,8 +30,6 @@ struct ProbsArgs {
   int B, T, H, n_q, causal;
   float scale;
 };
-
-__device__ __forceinline__ int rel_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
 __device__ __forceinline__ float group16_max(float v) {
 #pragma unroll
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsArgs a) {
   for (int it = 0; it < IT; ++it) {               // K of (b, h) -> LDS; rows >= T are zero (loads clamped, not predicated)
     const int idx = tid + 256 * it, row = idx >> 3, ch = idx & 7;
     const uint4 v = *(const uint4*)(a.k + (row0 + (row < T ? row : T - 1)) * a.ldk + h * 64 + ch * 8);
-    *(uint4*)(Ks + rel_off(row, ch)) = row < T ? v : make_uint4(0, 0, 0, 0);
+    *(uint4*)(Ks + at_off(row, ch)) = row < T ? v : make_uint4(0, 0, 0, 0);
   }
   __syncthreads();                                // the only barrier: waves without rows may leave after it
   const int i0 = 64 * qb + 16 * wave;
@@ -98,8 +97,8 @@ __global__ __launch_bounds__(256) void attn_probs_kernel(const ProbsArgs a) {
     s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (kt >= nkt || (a.causal && 16 * kt > pmax)) continue;     // (wave-uniform; every entry of such a tile is masked below)
     const int key = 16 * kt + li;
-    s[kt] = CCLIP_MFMA_16x16x32(qf0, *(const bf16x8*)(Ks + rel_off(key, g)), s[kt]);
-    s[kt] = CCLIP_MFMA_16x16x32(qf1, *(const bf16x8*)(Ks + rel_off(key, 4 + g)), s[kt]);
+    s[kt] = CCLIP_MFMA_16x16x32(qf0, frag_row(Ks, key, g), s[kt]);
+    s[kt] = CCLIP_MFMA_16x16x32(qf1, frag_row(Ks, key, 4 + g), s[kt]);
   }
 
   const float NEG = -__builtin_huge_valf();

@@ -9,31 +9,20 @@
 // (I + C_{L-1}) ... (I + C_s) without storing the L per-layer maps.
 //
 // One workgroup (4 waves) per sequence.  Heads are looped; each wave keeps the same query tiles for every head, so C sums
-// across heads in registers (fixed order: no atomics, bitwise reproducible).  Both products are v_mfma_f32_16x16x32 with the
-// query on the accumulator rows, exactly as in attn_bwd_kernel (attention.hip): S = Q K^T and dP = dA V^T, K and V of the
-// head staged in LDS ([row][64] 16-bit, 16-byte chunk c of row r at chunk c ^ (r & 7)), Q and dA rows read straight into
-// the A fragments.  After the head loop C goes to LDS as fp32 (reusing the head operands' space); each wave then forms rows
+// across heads in registers (fixed order: no atomics, bitwise reproducible).  K and V of the head are staged in LDS with
+// head_load / head_store (attention_tiles.h), the next head's loads in flight under this head's MFMAs; the tile itself -
+// S = Q K^T, dP = dA V^T, the mask and max(P dP, 0) - is rel_tile of attention_relevance_core.h, shared with the row kernel.
+// After the head loop C goes to LDS as fp32 (reusing the head operands' space); each wave then forms rows
 // of R C from R rows it holds in registers (one row's columns across the lanes, broadcast with readlane) and writes them back.
-#include "cclip_common.h"
-#include "../../include/cclip_hip.h"
+#include "attention_relevance_core.h"
 
 namespace CCLIP_NS {
 
-struct RelArgs {
-  const bf16* q; const bf16* k; const bf16* v;   // row (b*T + t) (or cu[b] + t), head h at column h*64
-  long ldq, ldk, ldv;
-  const bf16* da; long ldda;                      // gradient at the attention output, same layout
-  const float* lse;                               // [B, H, T]
-  const int* cu;                                  // packed batch: sequence b is rows [cu[b], cu[b+1]); null: row b*T + t
-  float* R;                                       // [B, T, T]
-  int B, T, H, causal;
-  float scale, cscale;                            // cscale = 1 / (H * grad_scale)
-};
+struct RelArgs : RelCommon { float* R; };         // R: [B, T, T]
 
-__device__ __forceinline__ int rel_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
+// (second bound = waves per SIMD: unbounded, <5> - T <= 80, the text tower's 77 - allocates 172 registers, which is two waves, not three)
 template <int NKT>
-__global__ __launch_bounds__(256) void attn_relevance_kernel(const RelArgs a) {
+__global__ __launch_bounds__(256, NKT <= 5 ? 3 : 2) void attn_relevance_kernel(const RelArgs a) {
   constexpr int TP = 16 * NKT;                    // padded tokens
   constexpr int NQW = (NKT + 3) / 4;              // query tiles per wave
   constexpr int CLD = TP + 4;                     // row stride of C in LDS (floats; even: 8-byte aligned column pairs)
@@ -46,10 +35,9 @@ __global__ __launch_bounds__(256) void attn_relevance_kernel(const RelArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
   const int b = blockIdx.x;
-  int T = a.cu ? a.cu[b + 1] - a.cu[b] : a.T;
-  T = T < a.T ? T : a.T;
+  long row0;
+  const int T = rel_seq(a, b, row0);
   if (T <= 0) return;                             // (workgroup-uniform)
-  const long row0 = a.cu ? (long)a.cu[b] : (long)b * a.T;
   const int nqt = (T + 15) >> 4;
 
   f32x4 c[NQW][NKT];
@@ -59,59 +47,26 @@ __global__ __launch_bounds__(256) void attn_relevance_kernel(const RelArgs a) {
     for (int kt = 0; kt < NKT; ++kt) c[i][kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   uint4 rk[IT], rv[IT];
-  auto head_load = [&](int h) {                   // every 16-byte load of head h's K and V, rows clamped (no predicated loads)
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int idx = tid + 256 * it, row = idx >> 3, ch = idx & 7;
-      const long gr = row0 + (row < T ? row : T - 1);
-      rk[it] = *(const uint4*)(a.k + gr * a.ldk + h * 64 + ch * 8);
-      rv[it] = *(const uint4*)(a.v + gr * a.ldv + h * 64 + ch * 8);
-    }
+  auto kv_load = [&](int h) {
+    head_load<IT>(a.k + h * 64, a.ldk, row0, T, rk, tid);
+    head_load<IT>(a.v + h * 64, a.ldv, row0, T, rv, tid);
   };
-  head_load(0);
+  kv_load(0);
   for (int h = 0; h < a.H; ++h) {
     __syncthreads();                              // everyone is done with the previous head's K / V
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-      const int idx = tid + 256 * it, row = idx >> 3, ch = idx & 7;
-      if (row < TP) {
-        *(uint4*)(Ks + rel_off(row, ch)) = row < T ? rk[it] : make_uint4(0, 0, 0, 0);
-        *(uint4*)(Vs + rel_off(row, ch)) = row < T ? rv[it] : make_uint4(0, 0, 0, 0);
-      }
-    }
-    if (h + 1 < a.H) head_load(h + 1);            // in flight under this head's MFMAs
+    head_store<IT>(Ks, T, TP, rk, tid);
+    head_store<IT>(Vs, T, TP, rv, tid);
+    if (h + 1 < a.H) kv_load(h + 1);              // in flight under this head's MFMAs
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NQW; ++i) {
       const int qt = wave + 4 * i;
       if (qt >= nqt) continue;                    // (wave-uniform)
-      const int qr = 16 * qt + li < T ? 16 * qt + li : T - 1;
-      const bf16* qp = a.q + (row0 + qr) * a.ldq + h * 64 + 8 * g;
-      const bf16* dp_ = a.da + (row0 + qr) * a.ldda + h * 64 + 8 * g;
-      const bf16x8 qf0 = *(const bf16x8*)qp, qf1 = *(const bf16x8*)(qp + 32);
-      const bf16x8 df0 = *(const bf16x8*)dp_, df1 = *(const bf16x8*)(dp_ + 32);
-      float lsv[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int qi = 16 * qt + 4 * g + r;
-        lsv[r] = qi < T ? a.lse[((long)b * a.H + h) * a.T + qi] : 0.f;
-      }
+      const RelQTile q = rel_qtile(a, row0, b, h, qt, T, lane);
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
         if (kt >= nqt || (a.causal && kt > qt)) continue;
-        const int key = 16 * kt + li;
-        f32x4 sv = (f32x4){0.f, 0.f, 0.f, 0.f}, dp = (f32x4){0.f, 0.f, 0.f, 0.f};
-        sv = CCLIP_MFMA_16x16x32(qf0, *(const bf16x8*)(Ks + rel_off(key, g)), sv);
-        sv = CCLIP_MFMA_16x16x32(qf1, *(const bf16x8*)(Ks + rel_off(key, 4 + g)), sv);
-        dp = CCLIP_MFMA_16x16x32(df0, *(const bf16x8*)(Vs + rel_off(key, g)), dp);
-        dp = CCLIP_MFMA_16x16x32(df1, *(const bf16x8*)(Vs + rel_off(key, 4 + g)), dp);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int qi = 16 * qt + 4 * g + r;
-          const bool ok = qi < T && key < T && (!a.causal || key <= qi);
-          const float pv = ok ? __expf(sv[r] * a.scale - lsv[r]) : 0.f;
-          c[i][kt][r] += ok ? fmaxf(pv * dp[r], 0.f) : 0.f;
-        }
+        c[i][kt] += rel_tile(a, q, Ks, Vs, qt, kt, 0, T, lane);
       }
     }
   }
@@ -168,18 +123,9 @@ __global__ __launch_bounds__(256) void attn_relevance_kernel(const RelArgs a) {
 using namespace CCLIP_NS;
 
 extern "C" int CCLIP_FN(cclip_attention_relevance)(const cclip_attn_desc* d, float grad_scale, float* R, hipStream_t stream) {
-  if (!d || !d->q || !d->k || !d->v || !d->lse || !d->dout || !R) return CCLIP_ERR_ARG;
-  if (d->B <= 0 || d->H <= 0 || d->T <= 0 || d->T > 128 || d->head_dim != 64 || !(grad_scale > 0.f)) return CCLIP_ERR_ARG;
-  if ((d->ldq & 7) || (d->ldk & 7) || (d->ldv & 7) || (d->lddo & 7)) return CCLIP_ERR_ARG;
-  if (((uintptr_t)d->q | (uintptr_t)d->k | (uintptr_t)d->v | (uintptr_t)d->dout) & 15) return CCLIP_ERR_ARG;
-  if (((uintptr_t)R & 3) || ((uintptr_t)d->lse & 3)) return CCLIP_ERR_ARG;
   RelArgs a;
-  a.q = (const bf16*)d->q; a.k = (const bf16*)d->k; a.v = (const bf16*)d->v;
-  a.ldq = d->ldq; a.ldk = d->ldk; a.ldv = d->ldv;
-  a.da = (const bf16*)d->dout; a.ldda = d->lddo;
-  a.lse = d->lse; a.cu = d->cu_seqlens; a.R = R;
-  a.B = d->B; a.T = d->T; a.H = d->H; a.causal = d->causal;
-  a.scale = d->scale; a.cscale = 1.0f / ((float)d->H * grad_scale);
+  if (rel_common_from_desc(d, grad_scale, 128, a) != CCLIP_OK || !R || ((uintptr_t)R & 3)) return CCLIP_ERR_ARG;
+  a.R = R;
   const int nkt = (d->T + 15) / 16;
   dim3 grid(d->B), block(256);
   if (nkt <= 2) hipLaunchKernelGGL((attn_relevance_kernel<2>), grid, block, 0, stream, a);

@@ -12,7 +12,7 @@
 //
 // Phase 1 (topk_partial_kernel): grid = query blocks x gallery splits.  A work-group (4 waves) owns 64 * MT query rows, wave w
 // the rows 16 MT w ..; their A fragments stay in registers.  The split's gallery rows stream through LDS in tiles of GT rows
-// ([row][D] 16-bit, 16-byte chunk c of row r at chunk c ^ (r & mask): the layout of attention_relevance.hip, conflict-free
+// ([row][D] 16-bit, 16-byte chunk c of row r at chunk c ^ (r & mask): the swizzle of attention_tiles.h at row length D, conflict-free
 // for the B-fragment reads); the next tile's 16-byte global loads are in flight while the current one is multiplied.
 // The query is on the accumulator rows: lane (li, g) holds query rows 4g .. 4g+3 against gallery row 16 st + li of sub-tile st.
 // Each lane keeps its rows' running k-th-best score; a sub-tile none of whose scores beats it costs four compares and one
