@@ -846,6 +846,102 @@ def sample_rows(logits, u, done_i32, *, inv_temperature: float = 1.0, top_k: int
     return tuple(outs)
 
 
+CAPTION_SELECT_MAX_K = 64
+CAPTION_SELECT_MAX_E = 1024
+
+
+def _ref_offsets(ref_off, N: int, Rtot: int) -> torch.Tensor:
+    """The CSR offsets of caption_select's references, validated on the host: int32 [N + 1] from 0, never decreasing, ending
+    inside the Rtot rows (the kernel reads them on the device and trusts them)."""
+    if isinstance(ref_off, torch.Tensor):
+        if ref_off.is_cuda:
+            raise TypeError("caption_select: ref_off must be a host tensor or a sequence (it is validated before the upload)")
+        if ref_off.is_floating_point() or ref_off.dim() != 1:
+            raise ValueError(f"caption_select: ref_off must be a 1-D integer vector, got {tuple(ref_off.shape)} {ref_off.dtype}")
+        off = [int(v) for v in ref_off.tolist()]
+    else:
+        off = [int(v) for v in ref_off]
+    if len(off) != N + 1:
+        raise ValueError(f"caption_select: ref_off needs N + 1 = {N + 1} entries, got {len(off)}")
+    if off[0] != 0 or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError(f"caption_select: ref_off must start at 0 and never decrease, got {off}")
+    if off[-1] > Rtot:
+        raise ValueError(f"caption_select: ref_off ends at {off[-1]}, ref has {Rtot} rows")
+    return torch.tensor(off, dtype=torch.int32)
+
+
+def caption_select(img, txt, K: int, *, lm_mean=None, ref=None, ref_off=None, w: float = 2.5, lm_weight: float = 0.0,
+                   cos=None, clip_score=None, ref_score=None, score=None, order=None, best=None):
+    """K candidate captions per image scored and ranked (include/cclip_hip.h, cclip_caption_select): img fp32 [N, E], txt fp32
+    [N * K, E] (row n * K + k = candidate k of image n), both raw tower outputs with inner stride 1, row strides multiples of
+    4 floats, 16-byte aligned.  lm_mean fp32 [N * K]: the candidates' mean token log-probability (None = 0).  ref fp32 [Rtot, E]
+    with ref_off, N + 1 CSR offsets ON THE HOST (a sequence or a CPU integer tensor; validated here, then uploaded): image n's
+    reference captions are rows ref_off[n] .. ref_off[n + 1] - 1, possibly none.  Returns (cos, clip_score, ref_score or None,
+    score, order, best): fp32 [N, K] x 4, int32 [N, K], int32 [N]; clip_score = w max(cos, 0), score = cos + lm_weight lm_mean,
+    order by (score descending, k ascending).  1 <= K <= 64, E % 4 == 0, E <= 1024.  One launch; no host read; two calls are
+    bitwise equal."""
+    for t, n in ((img, "img"), (txt, "txt")) + (((ref, "ref"),) if ref is not None else ()):
+        if t.dtype != torch.float32:
+            raise ValueError(f"caption_select: {n} must be float32, got {t.dtype}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"caption_select: {n} must be a 2-D view with inner stride 1, got {tuple(t.shape)} / {t.stride()}")
+    N, E = img.shape
+    if int(K) != K or K < 1:
+        raise ValueError(f"caption_select: K must be an integer >= 1, got {K}")
+    K = int(K)
+    if N < 1:
+        raise ValueError("caption_select: need at least one image")
+    if tuple(txt.shape) != (N * K, E):
+        raise ValueError(f"caption_select: txt must be [N * K, E] = [{N * K}, {E}], got {tuple(txt.shape)}")
+    if (ref is None) != (ref_off is None):
+        raise ValueError("caption_select: give both ref and ref_off, or neither")
+    if ref is not None and ref.shape[1] != E:
+        raise ValueError(f"caption_select: ref has {ref.shape[1]} columns, img has {E}")
+    if lm_mean is not None and (lm_mean.dtype != torch.float32 or tuple(lm_mean.shape) != (N * K,) or not lm_mean.is_contiguous()):
+        raise ValueError(f"caption_select: lm_mean must be a contiguous float32 [{N * K}] vector, got {lm_mean.dtype} {tuple(lm_mean.shape)}")
+    if K > CAPTION_SELECT_MAX_K:
+        raise NotImplementedError(f"caption_select: K = {K}; the kernel ranks at most {CAPTION_SELECT_MAX_K} candidates per image")
+    if E < 4 or E % 4 or E > CAPTION_SELECT_MAX_E:
+        raise NotImplementedError(f"caption_select: E = {E}; the kernel needs E % 4 == 0 and 4 <= E <= {CAPTION_SELECT_MAX_E}")
+    off = None if ref_off is None else _ref_offsets(ref_off, N, ref.shape[0])
+    if ref is not None and ref.shape[0] == 0:             # no reference anywhere: every rmax is 0, no row is read
+        ref = ref.new_zeros(1, E)
+    dev = img.device
+    lds = []
+    for t, n in ((img, "img"), (txt, "txt"), (ref, "ref")):
+        if t is None:
+            lds.append(E)
+            continue
+        if not t.is_cuda or t.device != dev:
+            raise TypeError(f"caption_select: {n}: expected a cuda tensor on {dev}, got {t.device} (no CPU path)")
+        ld = t.stride(0) if t.shape[0] > 1 else max(E, t.stride(0) // 4 * 4)
+        if ld < E or ld % 4 or t.data_ptr() % 16:
+            raise ValueError(f"caption_select: {n} must be 16-byte aligned with a row stride >= E that is a multiple of 4 floats "
+                             f"(stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16})")
+        lds.append(ld)
+    if lm_mean is not None and lm_mean.device != dev:
+        raise TypeError(f"caption_select: lm_mean: expected a tensor on {dev}, got {lm_mean.device}")
+    outs = []
+    for t, n, dt, shape in ((cos, "cos", torch.float32, (N, K)), (clip_score, "clip_score", torch.float32, (N, K)),
+                            (ref_score, "ref_score", torch.float32, (N, K)), (score, "score", torch.float32, (N, K)),
+                            (order, "order", torch.int32, (N, K)), (best, "best", torch.int32, (N,))):
+        if n == "ref_score" and ref is None:
+            if t is not None:
+                raise ValueError("caption_select: ref_score given without references")
+            outs.append(None)
+            continue
+        if t is None:
+            t = torch.empty(shape, device=dev, dtype=dt)
+        if t.dtype != dt or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"caption_select: {n} must be a contiguous {dt} {list(shape)} tensor on {dev}, got {t.dtype} {tuple(t.shape)}")
+        outs.append(t)
+    off_dev = None if off is None else off.to(dev)
+    check(lib.cclip_caption_select(_p(img), c_long(lds[0]), _p(txt), c_long(lds[1]), c_int(N), c_int(K), c_int(E), _p(lm_mean), _p(ref),
+                                   c_long(lds[2]), _p(off_dev), c_float(w), c_float(lm_weight), _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                                   _p(outs[3]), _p(outs[4]), _p(outs[5]), _stream()), "cclip_caption_select")
+    return tuple(outs)
+
+
 def attention_small_fwd(q, k, v, o, *, B: int, T: int, H: int, head_dim: int, lse=None, scale=None) -> None:
     """Generic-head_dim unmasked attention (TransformerMapper): same tensor conventions as attention_fwd."""
     d = _attn_desc(q, k, v, o, lse, B, T, H, False, None, scale, head_dim)

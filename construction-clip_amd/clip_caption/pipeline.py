@@ -22,7 +22,7 @@ import torch
 from cclip_hip import ops
 
 from .data import CAPTION_TYPES, VIOLATION_TYPES
-from .generate import _beam_outputs, _beam_rows, _replay_attention, generate2_batch, generate_beam_batch
+from .generate import _beam_outputs, _beam_rows, _replay_attention, generate2_batch, generate_beam_batch, generate_sample_batch
 
 
 def attribute_strings(caption_labels: Sequence[str], violation_labels: Sequence[str]) -> List[str]:
@@ -45,13 +45,23 @@ def build_attribute_table(tokenizer, caption_labels: Sequence[str], violation_la
     return table
 
 
+def _check_best_of(best_of, return_attention: bool) -> None:
+    if int(best_of) != best_of or best_of < 0:
+        raise ValueError(f"best_of must be an integer >= 0 (0 = beam search), got {best_of}")
+    if best_of and best_of > ops.CAPTION_SELECT_MAX_K:
+        raise NotImplementedError(f"best_of = {best_of}; the selection kernel ranks at most {ops.CAPTION_SELECT_MAX_K} candidates")
+    if best_of and return_attention:
+        raise NotImplementedError("return_attention is not available with best_of")
+
+
 class PendingCaptions:
     """What Captioner.submit returns: the device work is enqueued; result() reads it back and decodes the text."""
 
-    def __init__(self, cap: "Captioner", n: int, probs, index, ids, greedy: bool, pending=None, eager=None, proj=None):
+    def __init__(self, cap: "Captioner", n: int, probs, index, ids, greedy: bool, pending=None, eager=None, proj=None, select=None):
         self._cap, self._n, self._probs, self._index, self._ids = cap, n, probs, index, ids
         self._greedy, self._pending, self._eager = greedy, pending, eager
         self._proj = proj                                                 # the projected prefixes, kept for return_attention
+        self._select = select                                             # best_of: what Captioner._clip_select left on the device
         self._done = None
 
     def _attention(self, per):
@@ -94,7 +104,18 @@ class PendingCaptions:
             if self._proj is not None:
                 for rec, att in zip(records, self._attention(per)):
                     rec["attention"] = att
-            self._done = (records, {"ids": ids, "index": index, "tokens": per})
+            extras = {"ids": ids, "index": index, "tokens": per}
+            if self._select is not None:                                  # texts[i] is still unset: the selection names it
+                sel = self._select
+                K, cand = sel["K"], sel["texts"]
+                cos, cs, lm, order = (sel[k].cpu().reshape(self._n, K).tolist() for k in ("cos", "clip_score", "lm_mean", "order"))
+                for i, rec in enumerate(records):
+                    rec["candidates"] = [{"text": cand[i * K + k], "cos": cos[i][k], "clip_score": cs[i][k], "lm_logprob": lm[i][k]}
+                                         for k in order[i]]
+                    rec["prediction"] = rec["candidates"][0]["text"]
+                    rec["clip_score"] = rec["candidates"][0]["clip_score"]
+                extras.update(text_features=sel["text_features"], order=sel["order"])
+            self._done = (records, extras)
         return self._done if return_tokens else self._done[0]
 
 
@@ -168,20 +189,50 @@ class Captioner:
         N = feat.shape[0]
         return torch.cat([self.caption_model.clip_project(feat[i:i + 1]).reshape(1, -1) for i in range(N)]).contiguous()
 
+    def _clip_select(self, images, feat, per, K: int, lm_weight: float, score_model):
+        """CLIP's choice among the K draws of every image.  per: generate_sample_batch's N tuples (texts, tokens [K, steps],
+        lengths, sum_logprob) in draw order.  Returns what PendingCaptions.result needs, everything but the texts on the device."""
+        from clip.score import encode_distinct_texts
+        tok = self.tokenizer
+        texts, lm = [], []
+        for _, tokens, lengths, total in per:
+            rows, lens = tokens.cpu().numpy(), lengths.tolist()
+            texts += [tok.decode(list(rows[k][:lens[k]])) for k in range(K)]          # draw order (the tuple's texts are sorted)
+            lm.append(total / lengths)
+        scorer = self.clip_model if score_model is None else score_model
+        if scorer is not self.clip_model:                                  # the cosine needs both sides from one model
+            was = scorer.training
+            feat = torch.cat([scorer.encode_image(images[i:i + 1]).float() for i in range(images.shape[0])]).contiguous()
+        text_features = encode_distinct_texts(scorer, self._caption_tokens(texts))
+        if scorer is not self.clip_model and scorer.training != was:
+            scorer.train(was)
+        lm_mean = torch.cat(lm).float().contiguous()
+        cos, cs, _, score, order, best = ops.caption_select(feat, text_features, K, lm_mean=lm_mean, lm_weight=float(lm_weight))
+        return {"K": K, "texts": texts, "lm_mean": lm_mean, "cos": cos, "clip_score": cs, "score": score, "order": order, "best": best,
+                "text_features": text_features}
+
     @torch.no_grad()
     def submit(self, images: torch.Tensor, beam_size: int = 3, entry_length: int = 100, temperature: float = 0.5,
-               stop_token: int = 102, greedy: bool = False, top_p: float = 0.8, return_attention: bool = False) -> PendingCaptions:
+               stop_token: int = 102, greedy: bool = False, top_p: float = 0.8, return_attention: bool = False, best_of: int = 0,
+               lm_weight: float = 0.0, generator=None, uniforms=None, top_k: int = 0, score_model=None) -> PendingCaptions:
         """Enqueue the whole device stage for preprocessed images [N, 3, R, R] - encode_image, the zero-shot heads and attribute
         ids, clip_project, the decoder's input rows, the prefills and the batched beam launches - and return without waiting
         for the device; `.result()` reads back and decodes.  Where the batched kernel does not apply
         (ClipCaptionModel.beam_batch_native_ok) the work is done here, through generate_beam_batch / generate2_batch.
         return_attention: every record of `.result()` also gets "attention", the best beam's last-layer rows
-        [H, n, S0 + n - 1] on the device (S0 = prefix_length + attribute_length; generate_beam's return_attention)."""
+        [H, n, S0 + n - 1] on the device (S0 = prefix_length + attribute_length; generate_beam's return_attention).
+        best_of = K >= 1: instead of the beam search, K captions per image are DRAWN (generate_sample_batch with top_p, top_k,
+        temperature; `generator` or `uniforms` [entry_length, N * K] fix the draw) and CLIP picks among them: the N * K texts
+        go through score_model's text tower (default: the Captioner's CLIP model; distinct texts once) and one
+        cclip_caption_select launch ranks them by cos(image, text) + lm_weight * (mean token log-probability).  The sampler's
+        loop and the decoding of the candidates to text wait for the device, so this form returns after the selection is
+        enqueued rather than at once.  beam_size and greedy are not used then."""
         model = self.caption_model
         images = self._images(images)
         N = images.shape[0]
         if N < 1:
             raise ValueError("need at least one image")
+        _check_best_of(best_of, return_attention)
         P, A = self.prefix_length, self.attribute_length
         beams = 1 if greedy else beam_size
         ok = getattr(model, "beam_batch_native_ok", None)
@@ -191,6 +242,13 @@ class Captioner:
             feat = self._features_one_by_one(images)
             probs, index, ids = self._classify(feat)
             proj = self._project(feat)                                     # test.py:521,540: on the fp32 features
+            if best_of:
+                emb = torch.cat((proj.view(N, P, -1), model.gpt.transformer.wte(ids.long())), dim=1)
+                per = generate_sample_batch(model, self.tokenizer, emb, num_samples=int(best_of), entry_length=entry_length, top_p=top_p,
+                                            top_k=top_k, temperature=temperature, stop_token=stop_token, generator=generator,
+                                            uniforms=uniforms, return_tokens=True)
+                select = self._clip_select(images, feat, per, int(best_of), lm_weight, score_model)
+                return PendingCaptions(self, N, probs, index, ids, greedy, eager=([None] * N, per), select=select)
             if native:
                 D = proj.shape[1] // P
                 x = torch.empty(N * (P + A), D, device=feat.device, dtype=torch.float32)
@@ -213,17 +271,32 @@ class Captioner:
                 model.train(was_training)
 
     def describe(self, images, beam_size: int = 3, entry_length: int = 100, temperature: float = 0.5, stop_token: int = 102,
-                 greedy: bool = False, top_p: float = 0.8, return_tokens: bool = False, return_attention: bool = False):
+                 greedy: bool = False, top_p: float = 0.8, return_tokens: bool = False, return_attention: bool = False,
+                 best_of: int = 0, lm_weight: float = 0.0, generator=None, uniforms=None, top_k: int = 0, score_model=None):
         """The records of `images` (a preprocessed float tensor [N, 3, R, R], or a sequence of PIL images / uint8 HWC arrays).
         More images than one batched launch holds (64 // beams) go in chunks of that size; the next chunk is enqueued before
         the previous one is read back.  return_tokens: also {"ids" [N, A], "index" [N, 2], "tokens": per caption what
-        generate_beam_batch (generate2_batch with greedy) returns with return_tokens}.  return_attention: as for submit."""
+        generate_beam_batch (generate2_batch with greedy) returns with return_tokens}.  return_attention: as for submit.
+        best_of = K >= 1 (as for submit): K captions are drawn per image and the one CLIP scores highest becomes "prediction";
+        every record gains "clip_score" (the CLIPScore 2.5 max(cos, 0) of the prediction) and "candidates", K dicts {"text",
+        "cos", "clip_score", "lm_logprob"} best first; "tokens" of the extras holds generate_sample_batch's tuples, and the
+        extras gain "text_features" (fp32 [N * K, E], the rows the selection kernel saw, draw order) and "order" (int32 [N, K]).
+        uniforms: [entry_length, N * K], column i * K + j = draw j of image i.  Chunks hold 64 // K images."""
+        _check_best_of(best_of, return_attention)
         images = self._images(images)
-        per = max(1, ops.BEAM_BATCH_MAX_ROWS // (1 if greedy else max(1, beam_size)))
+        K = int(best_of)
+        per = max(1, ops.BEAM_BATCH_MAX_ROWS // (K if K else 1 if greedy else max(1, beam_size)))
         kw = dict(beam_size=beam_size, entry_length=entry_length, temperature=temperature, stop_token=stop_token, greedy=greedy,
                   top_p=top_p, return_attention=return_attention)
+        if best_of:
+            kw.update(best_of=best_of, lm_weight=lm_weight, generator=generator, top_k=top_k, score_model=score_model)
+            if uniforms is not None and tuple(uniforms.shape) != (entry_length, images.shape[0] * K):
+                raise ValueError(f"uniforms must be [{entry_length}, {images.shape[0] * K}] (entry_length, N * best_of), "
+                                 f"got {tuple(uniforms.shape)}")
         records, extras, prev = [], [], None
         for s in range(0, images.shape[0], per):
+            if K and uniforms is not None:
+                kw["uniforms"] = uniforms[:, s * K:(s + per) * K]
             nxt = self.submit(images[s:s + per], **kw)
             if prev is not None:
                 r, e = prev.result(True)
@@ -237,8 +310,11 @@ class Captioner:
         extras.append(e)
         if not return_tokens:
             return records
-        return records, {"ids": torch.cat([e["ids"] for e in extras]), "index": torch.cat([e["index"] for e in extras]),
-                         "tokens": [t for e in extras for t in e["tokens"]]}
+        out = {"ids": torch.cat([e["ids"] for e in extras]), "index": torch.cat([e["index"] for e in extras]),
+               "tokens": [t for e in extras for t in e["tokens"]]}
+        if K:
+            out.update(text_features=torch.cat([e["text_features"] for e in extras]), order=torch.cat([e["order"] for e in extras]))
+        return records, out
 
     def _caption_tokens(self, texts: List[str]) -> torch.Tensor:
         """CLIP token rows of generated captions; an over-long caption is cut where clip_tokenize can do that (`truncate`)"""
@@ -258,7 +334,8 @@ class Captioner:
         "image_relevance" (fp32 [patches]), "token_scores" (fp32 over the caption's tokens 1 .. EOT-1, summing to 1) and
         "clip_tokens" (the caption's CLIP token row), the last three on the device.  The overlays of the whole batch come back
         in one copy.  size / lut: as for clip.relevance_overlay; describe_kwargs go to describe (with return_tokens=True the
-        result is (records, extras), as there)."""
+        result is (records, extras), as there; with best_of=K the caption explained is the one CLIP selected, and
+        score_model=relevance_model scores the candidates on the model that explains them)."""
         import clip
         images = self._images(images)
         res = self.describe(images, **describe_kwargs)

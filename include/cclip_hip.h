@@ -621,6 +621,34 @@ int cclip_gpt2_beam_search_batch(const cclip_beam_batch_desc* d, hipStream_t str
 int cclip_relevance_overlay(const float* rel, int32_t N, int32_t g, const float* images, int64_t image_stride, int32_t R,
                             const float* lut, int32_t S, uint8_t* out, float* map_out, hipStream_t stream);
 
+/* ---- CLIP-guided caption selection ---------------------------------------------------------------
+ * K candidate captions for each of N images, scored against the image (CLIPScore, Hessel et al. 2021), optionally against the
+ * image's reference captions (RefCLIPScore), and ranked - one launch, one work-group per image (csrc/caption_select.hip).
+ * Every buffer is fp32 (the towers' outputs after .float(), raw, not normalised); there is no fp16 twin.
+ *   img [N][E] row stride ldi; txt [N*K][E] row stride ldt, row n*K + k = candidate k of image n;
+ *   lm_mean [N*K] or NULL (= 0): the mean token log-probability of the candidate;
+ *   ref [Rtot][E] row stride ldr with CSR offsets ref_off int32 [N+1] (image n owns rows ref_off[n] .. ref_off[n+1]-1; an
+ *   image may own none), both NULL = no RefCLIPScore (ref_score is then not touched and may be NULL).
+ *   cos[n][k]   = <i_n, t_nk> / (|i_n| |t_nk|), 0 when either norm is 0
+ *   clip_score  = w * max(cos, 0)
+ *   rmax[n][k]  = max(0, max_r cos(t_nk, ref_r)) over image n's references, 0 when it has none
+ *   ref_score   = 2 * clip_score * rmax / (clip_score + rmax), 0 when the denominator is 0
+ *   score       = cos + lm_weight * lm_mean
+ *   order[n][:] = the candidates by (score descending, k ascending), int32;  best[n] = order[n][0]
+ * Scores are compared through a monotone integer image of their fp32 bits (-0 == +0): order[n][:] is a permutation of
+ * 0 .. K-1 for any input, NaN included.  Values from non-finite features are otherwise undefined; no access leaves the buffers.
+ * |cos - exact| <= 4 (E/64 + 8) 2^-24.  No atomics: two calls agree bit for bit, and a row's results do not depend on N.
+ * CCLIP_ERR_ARG, nothing launched: a required pointer NULL; N <= 0; K < 1 or K > CCLIP_CAPTION_SELECT_MAX_K; E <= 0, E % 4 != 0
+ * or E > CCLIP_CAPTION_SELECT_MAX_E; a stride below E or not a multiple of 4; img / txt / ref not 16-byte aligned; ref without
+ * ref_off or ref_off without ref.  ref_off is read on the device only: a decreasing or out-of-bounds range is the caller's
+ * error (the Python layer validates the offsets on the host before upload). */
+#define CCLIP_CAPTION_SELECT_MAX_K 64
+#define CCLIP_CAPTION_SELECT_MAX_E 1024
+int cclip_caption_select(const float* img, int64_t ldi, const float* txt, int64_t ldt, int32_t N, int32_t K, int32_t E,
+                         const float* lm_mean, const float* ref, int64_t ldr, const int32_t* ref_off, float w, float lm_weight,
+                         float* cos, float* clip_score, float* ref_score, float* score, int32_t* order, int32_t* best,
+                         hipStream_t stream);
+
 /* ---- IEEE fp16 twins ---------------------------------------------------------------------------
  * Every entry point above whose 16-bit buffers are bf16 has a twin with the identical signature that
  * treats them as IEEE fp16 (same MFMA rate on gfx950; 3 more mantissa bits - the reference's own CUDA

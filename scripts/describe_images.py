@@ -2,7 +2,8 @@
 """Captions straight from image files - the loop of /root/reference/CLIP_prefix_caption/test.py:556-639 and the root
 predict.py:57-86 on the MI355X packages, through `clip_caption.Captioner`: per image the CLIP encode, the two zero-shot heads
 (caption type, violation type), the attribute prompt and the beam search, `--bs` images per call.  The records go to
-output_<suffix>.json with the fields of test.py:626-633.  Plotting (export_plot) is not carried over.
+output_<suffix>.json with the fields of test.py:626-633.  Plotting (export_plot) is not carried over.  `--best-of K` draws K
+captions per image and keeps the one CLIP says matches the photo (Captioner.describe(best_of=K)).
 
     python scripts/describe_images.py --json ../test.json --image-path .. --clip-checkpoint clip.pt --checkpoint model.pt
     python scripts/describe_images.py --synthetic                # offline: seeded state dicts, toy tokenizers, generated images"""
@@ -47,7 +48,12 @@ def build_parser():
     ap.add_argument("--top-p", type=float, default=0.8, help="--sample: nucleus mass (1 = off)")
     ap.add_argument("--top-k", type=int, default=0, help="--sample: keep the k most probable tokens (0 = off)")
     ap.add_argument("--temperature", type=float, default=1.0, help="--sample: softmax temperature")
-    ap.add_argument("--seed", type=int, default=0, help="--sample: seed of the draws (one seed, one set of captions)")
+    ap.add_argument("--seed", type=int, default=0, help="--sample / --best-of: seed of the draws (one seed, one set of captions)")
+    ap.add_argument("--best-of", type=int, default=0, metavar="K",
+                    help="draw K captions per image (with --top-p / --top-k / --temperature) and keep the one CLIP scores highest "
+                         "against the photo instead of the beam caption; each record gets \"clip_score\" and \"candidates\"")
+    ap.add_argument("--lm-weight", type=float, default=0.0, metavar="A",
+                    help="--best-of: rank by cos(image, caption) + A * (mean token log-probability)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=9, help="--synthetic: images to describe")
     ap.add_argument("--clip_synthetic", default="test-tiny", help="--synthetic: CLIP geometry")
@@ -110,17 +116,24 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.sample < 0:
         raise SystemExit("--sample must be >= 0")
+    if args.best_of < 0:
+        raise SystemExit("--best-of must be >= 0")
     from PIL import Image
     cap, annotations, image_path, tmp = setup(args)
     log = {"caption": []}
     arrays = {}
     entry_length = args.entry_length or (67 if args.greedy else 100)
     generator = torch.Generator(device=cap.device).manual_seed(args.seed) if args.sample else None
+    best_of = {}
+    if args.best_of:                                                   # (its own generator: --sample's draws stay what they were)
+        entry_length = args.entry_length or 67
+        best_of = dict(best_of=args.best_of, lm_weight=args.lm_weight, top_p=args.top_p, top_k=args.top_k, temperature=args.temperature,
+                       generator=torch.Generator(device=cap.device).manual_seed(args.seed))
     for i in range(0, len(annotations), args.bs):
         chunk = annotations[i:i + args.bs]
         images = [Image.open(os.path.join(image_path, a["file_name"])) for a in chunk]
         records = cap.describe(images, beam_size=args.beam_size, entry_length=entry_length, greedy=args.greedy,
-                               return_attention=args.attention_out is not None)
+                               return_attention=args.attention_out is not None, **best_of)
         samples = sample_captions(cap, images, args, generator) if args.sample else None
         for j, (a, r) in enumerate(zip(chunk, records)):
             if args.attention_out is not None:
@@ -136,6 +149,8 @@ def main(argv=None):
             })
             if samples is not None:
                 log["caption"][-1]["samples"] = samples[j]
+            if args.best_of:
+                log["caption"][-1].update(clip_score=r["clip_score"], candidates=r["candidates"])
         C.log_line(done=min(i + args.bs, len(annotations)), of=len(annotations))
     if tmp is not None:
         tmp.cleanup()
