@@ -685,6 +685,36 @@ def attention_probs(q, k, P, *, B: int, T: int, H: int, causal: bool = False, sc
                                              c_long(P.stride(1)), c_long(P.stride(2)), _stream()), "cclip_attention_probs")
 
 
+def _pair16(fname: str, a, an: str, b, bn: str):
+    """The two 16-bit row-major operands of a score kernel (csrc/score_tiles.h): on the device, 2-D, inner stride 1, equal widths.
+    Returns (rows of a, rows of b, D).  A wrong dtype is lm_head_score's ValueError or similarity_topk's TypeError (_req16, _fn)."""
+    pair = ((a, an), (b, bn))
+    if fname == "lm_head_score":
+        for t, n in pair:
+            if not t.is_cuda:
+                raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {t.device} (no CPU path)")
+        for t, n in pair:
+            if t.dtype not in HALF_TYPES or t.dtype != a.dtype:
+                raise ValueError(f"{fname}: {n} must be bfloat16 or float16, both alike, got {a.dtype} / {t.dtype}")
+    else:
+        for t, n in pair:
+            _req16(t, n)
+    for t, n in pair:
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"{fname}: {n} must be a 2-D view with inner stride 1, got {tuple(t.shape)} / {t.stride()}")
+    if b.shape[1] != a.shape[1]:
+        raise ValueError(f"{fname}: {an} has {a.shape[1]} columns, {bn} has {b.shape[1]}")
+    return a.shape[0], b.shape[0], a.shape[1]
+
+
+def _ld16(fname: str, t, n: str) -> int:
+    """Row stride (elements) of such an operand, checked for the kernel's 16-byte loads; a one-row view's is rounded to fit."""
+    if (t.shape[0] > 1 and t.stride(0) % 8) or t.data_ptr() % 16:
+        raise ValueError(f"{fname}: {n} must be 16-byte aligned with a row stride that is a multiple of 8 elements "
+                         f"(stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16})")
+    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0) // 8 * 8)
+
+
 SIMILARITY_TOPK_MAX_K = 64
 SIMILARITY_TOPK_MAX_D = 1024
 
@@ -701,14 +731,7 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
     row strides multiples of 8 elements, 16-byte aligned.  Returns (scores fp32 [Q, k] descending, index int32 [Q, k]); equal
     scores by the lower gallery index, NaN last.  The Q x N matrix is never formed: the only scratch is the per-split
     candidate workspace.  1 <= k <= 64, k <= N, D % 32 == 0, D <= 1024, N < 2^31.  Enqueues two launches; no host read."""
-    for t, n in ((q, "q"), (g, "g")):
-        _req16(t, n)
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise ValueError(f"similarity_topk: {n} must be a 2-D view with inner stride 1, got {tuple(t.shape)} / {t.stride()}")
-    Q, D = q.shape
-    N = g.shape[0]
-    if g.shape[1] != D:
-        raise ValueError(f"similarity_topk: q has {D} columns, g has {g.shape[1]}")
+    Q, N, D = _pair16("similarity_topk", q, "q", g, "g")
     if Q < 1 or N < 1:
         raise ValueError(f"similarity_topk: empty operand (Q = {Q}, N = {N})")
     if not 1 <= k <= SIMILARITY_TOPK_MAX_K:
@@ -719,10 +742,7 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
         raise NotImplementedError(f"similarity_topk: D = {D}; the kernel needs D % 32 == 0 and D <= {SIMILARITY_TOPK_MAX_D}")
     if N >= 2 ** 31:
         raise NotImplementedError(f"similarity_topk: N = {N}; the kernel's gallery index is int32 (N < 2^31)")
-    for t, n in ((q, "q"), (g, "g")):
-        if (t.shape[0] > 1 and t.stride(0) % 8) or t.data_ptr() % 16:
-            raise ValueError(f"similarity_topk: {n} must be 16-byte aligned with a row stride that is a multiple of 8 elements "
-                             f"(stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16})")
+    ldq, ldg = _ld16("similarity_topk", q, "q"), _ld16("similarity_topk", g, "g")
     fn = _fn("cclip_similarity_topk", q, g)
     if out_scores is None:
         out_scores = torch.empty(Q, k, device=q.device, dtype=torch.float32)
@@ -732,8 +752,6 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
     assert out_scores.is_contiguous() and out_index.is_contiguous() and tuple(out_scores.shape) == (Q, k) == tuple(out_index.shape)
     nbytes = similarity_topk_workspace(Q, N, k)
     ws = torch.empty(nbytes // 8, device=q.device, dtype=torch.int64)
-    ldq = q.stride(0) if Q > 1 else max(D, q.stride(0) // 8 * 8)
-    ldg = g.stride(0) if N > 1 else max(D, g.stride(0) // 8 * 8)
     check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(N), c_int(D), c_int(k), _p(out_scores), _p(out_index),
              _p(ws), c_long(nbytes), _stream()), "cclip_similarity_topk")
     return out_scores, out_index
@@ -755,20 +773,11 @@ def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, 
     pred_logit), each [R]: logp = z[label] - lse (exactly 0 where label == ignore_index, NaN for any other label outside
     [0, V)), lse = logsumexp(z), pred = argmax (equal logits: the lower column; NaN below every number) and its logit.
     D % 32 == 0, 32 <= D <= 1024.  A row's outputs do not depend on R.  Enqueues two launches; no host read."""
-    for t, n in ((x16, "x16"), (w16, "w16"), (labels_i32, "labels_i32")):
-        if not t.is_cuda:
-            raise TypeError(f"lm_head_score: {n}: expected a cuda tensor, got {t.device} (no CPU path)")
-    for t, n in ((x16, "x16"), (w16, "w16")):
-        if t.dtype not in HALF_TYPES or t.dtype != x16.dtype:
-            raise ValueError(f"lm_head_score: {n} must be bfloat16 or float16, both alike, got {x16.dtype} / {t.dtype}")
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise ValueError(f"lm_head_score: {n} must be a 2-D view with inner stride 1, got {tuple(t.shape)} / {t.stride()}")
+    R, V, D = _pair16("lm_head_score", x16, "x16", w16, "w16")
+    if not labels_i32.is_cuda:
+        raise TypeError(f"lm_head_score: labels_i32: expected a cuda tensor, got {labels_i32.device} (no CPU path)")
     if labels_i32.dtype != torch.int32:
         raise ValueError(f"lm_head_score: labels must be int32, got {labels_i32.dtype}")
-    R, D = x16.shape
-    V = w16.shape[0]
-    if w16.shape[1] != D:
-        raise ValueError(f"lm_head_score: x16 has {D} columns, w16 has {w16.shape[1]}")
     if R < 1 or V < 1:
         raise ValueError(f"lm_head_score: empty operand (R = {R}, V = {V})")
     if V >= 2 ** 31:
@@ -777,10 +786,7 @@ def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, 
         raise ValueError(f"lm_head_score: labels must be a contiguous [{R}] vector, got {tuple(labels_i32.shape)}")
     if D % 32 or not 32 <= D <= LM_HEAD_SCORE_MAX_D:
         raise NotImplementedError(f"lm_head_score: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {LM_HEAD_SCORE_MAX_D}")
-    for t, n in ((x16, "x16"), (w16, "w16")):
-        if (t.shape[0] > 1 and t.stride(0) % 8) or t.data_ptr() % 16:
-            raise ValueError(f"lm_head_score: {n} must be 16-byte aligned with a row stride that is a multiple of 8 elements "
-                             f"(stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16})")
+    ldx, ldw = _ld16("lm_head_score", x16, "x16"), _ld16("lm_head_score", w16, "w16")
     fn = _fn("cclip_lm_head_score", x16, w16)
     dev = x16.device
     outs = []
@@ -792,8 +798,6 @@ def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, 
             raise ValueError(f"lm_head_score: {n} must be a contiguous {dt} [{R}] vector on {dev}, got {t.dtype} {tuple(t.shape)}")
         outs.append(t)
     ws = torch.empty(lm_head_score_workspace(R, V) // 8, device=dev, dtype=torch.int64)
-    ldx = x16.stride(0) if R > 1 else max(D, x16.stride(0) // 8 * 8)
-    ldw = w16.stride(0) if V > 1 else max(D, w16.stride(0) // 8 * 8)
     check(fn(_p(x16), c_long(ldx), c_int(R), c_int(D), _p(w16), c_long(ldw), c_int(V), _p(labels_i32), c_int(ignore_index),
              _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(ws), _stream()), "cclip_lm_head_score")
     return tuple(outs)

@@ -11,7 +11,7 @@
 //   ref_score  = 2 clip_score rmax / (clip_score + rmax), 0 when the denominator is 0
 //   score      = cos + lm_weight lm_mean[n K + k]                              (cos itself when lm_mean is NULL)
 //   order[n,:] = the candidates by (score descending, k ascending);  best[n] = order[n,0]
-// Scores are compared through a monotone integer image of their fp32 bits (sample_rows.hip's sr_key; -0 == +0), a total order
+// Scores are compared through a monotone integer image of their fp32 bits (mono_bits of score_key.h; -0 == +0), a total order
 // on every bit pattern, so order[n,:] is a permutation of 0 .. K-1 for ANY input, NaN included.  Values computed from
 // non-finite features are otherwise undefined; every access stays inside the buffers.
 //
@@ -29,7 +29,7 @@
 // Error.  A lane adds at most E / 64 products one after the other and six butterfly levels follow, so each of the three sums
 // errs by at most (E / 64 + 6) 2^-24 of sum |a_i b_i| <= |a| |b|; with the two square roots, the product and the division
 // |cos - exact| <= 4 (E / 64 + 8) 2^-24.
-#include "cclip_common.h"
+#include "score_key.h"
 #include "../../include/cclip_hip.h"
 
 #define CS_Q 4                                    // float4s of a row a lane owns: CCLIP_CAPTION_SELECT_MAX_E / (4 * 64)
@@ -64,12 +64,6 @@ __device__ __forceinline__ float cs_dot(const CsRow& a, const CsRow& b) {
 // <a, b> / (|a| |b|) from the dot and the squared norms; 0 when either norm is 0
 __device__ __forceinline__ float cs_cos(float dot, float na, float nb) {
   return na == 0.0f || nb == 0.0f ? 0.0f : dot / (sqrtf(na) * sqrtf(nb));
-}
-
-__device__ __forceinline__ unsigned cs_key(float x) {
-  x += 0.0f;                                      // -0 -> +0: equal fp32 scores share one key
-  const unsigned b = __float_as_uint(x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
 __global__ __launch_bounds__(256) void caption_select_kernel(const float* __restrict__ img, long ldi, const float* __restrict__ txt,
@@ -107,7 +101,7 @@ __global__ __launch_bounds__(256) void caption_select_kernel(const float* __rest
         const float den = cs + rmax;
         ref_out[row] = den == 0.0f ? 0.0f : 2.0f * cs * rmax / den;
       }
-      s_key[k] = cs_key(sc);
+      s_key[k] = mono_bits(sc);
     }
   }
   __syncthreads();

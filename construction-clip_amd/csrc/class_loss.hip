@@ -14,16 +14,10 @@
 // (ONE trip at R <= 16384), so a staged copy would be read four times per element after every wave has waited at a barrier for
 // the whole vector - and at C = 8192 its 32 KB would cap the CU at five blocks instead of eight.  Read directly, lane l takes
 // col_class[c] with the same coalesced index as row[c]; the four waves of a block and every block on the CU hit the same lines.
-#include "cclip_common.h"
+#include "row_kernels.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // `dlogits` may alias `logits` (clip/loss.py overwrites the logits with their gradient in place), so neither carries
 // __restrict__: every element is read by the lane that later writes it, and the positives' sum is taken in pass one,
@@ -58,16 +52,7 @@ __global__ __launch_bounds__(256) void xent_rows_classes_kernel(const float* log
       step(v0, k0, c); step(v1, k1, c + 64); step(v2, k2, c + 128); step(v3, k3, c + 192);
     }
     for (; c < C; c += 64) step(row[c], col_class[c], c);
-    // combine (m, s, arg) across lanes; ties -> smallest index (torch.argmax returns the first max)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-      const int a2 = __shfl_xor(arg, o, 64);
-      const float mn = fmaxf(m, m2);
-      s = s * (m == mn ? 1.f : __expf(m - mn)) + s2 * (m2 == mn ? 1.f : __expf(m2 - mn));
-      if (m2 > m || (m2 == m && a2 < arg)) arg = a2;
-      m = mn;
-    }
+    wave_softmax_argmax(m, s, arg);
     psum = wave_sum(psum);
     pcnt = wave_sum_int(pcnt);
     const float lse = m + __logf(s);
@@ -105,8 +90,6 @@ __global__ __launch_bounds__(256) void xent_rows_classes_kernel(const float* log
 
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
-
-static int grid_rows4(int rows) { int g = (rows + 3) / 4; return g > 4096 ? 4096 : (g < 1 ? 1 : g); }
 
 extern "C" int cclip_xent_rows_classes(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* row_class,
                                        const int32_t* col_class, float grad_scale, float* loss_row, int32_t* pred,

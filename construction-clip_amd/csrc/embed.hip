@@ -8,7 +8,7 @@
 //   text_embed      x = token_embedding[text] + positional   (CLIP.encode_text head)
 //   embed_scatter   dtoken_embedding[text[i]] += dx[i]       (fp32 atomics, 256 contiguous B / wave-instr)
 //   colsum          out[c] (+)= sum_r in[r][c]               (bias grads, positional grads)
-#include "cclip_common.h"
+#include "row_kernels.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
@@ -364,8 +364,6 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
 
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
-
-static int grid_rows4(int rows) { int g = (rows + 3) / 4; return g > 4096 ? 4096 : (g < 1 ? 1 : g); }
 
 extern "C" int CCLIP_FN(cclip_patchify)(const float* image, void* out_bf16, int32_t B, int32_t R, int32_t P, hipStream_t stream) {
   if (!image || !out_bf16 || B <= 0 || P <= 0 || R % P || ((uintptr_t)image & 15) || ((uintptr_t)out_bf16 & 15)) return CCLIP_ERR_ARG;

@@ -2,7 +2,7 @@
 //     s[q, n] = sum_d Qm[q, d] G[n, d]            (fp32 accumulation on v_mfma_f32_16x16x32)
 // of every query, as (score fp32, gallery index int32) in descending order.  The Q x N matrix is never written.
 //
-// Order.  A candidate is one 64-bit key: the high word is the score's bits made monotone (NaN -> 0, the lowest; -0 -> +0),
+// Order.  A candidate is one 64-bit key: the high word is score_key (score_key.h: the bits made monotone, NaN -> 0, -0 -> +0),
 // the low word is ~index.  Larger key = better: higher score first, equal fp32 scores by the LOWER gallery index, NaN below
 // every number.  Keys of distinct gallery rows are distinct, so "the k largest keys" is one well-defined set whatever the
 // order candidates are met in: the result does not depend on how the gallery is split.  No atomics; two launches are bitwise equal.
@@ -12,20 +12,17 @@
 //
 // Phase 1 (topk_partial_kernel): grid = query blocks x gallery splits.  A work-group (4 waves) owns 64 * MT query rows, wave w
 // the rows 16 MT w ..; their A fragments stay in registers.  The split's gallery rows stream through LDS in tiles of GT rows
-// ([row][D] 16-bit, 16-byte chunk c of row r at chunk c ^ (r & mask): the swizzle of attention_tiles.h at row length D, conflict-free
-// for the B-fragment reads); the next tile's 16-byte global loads are in flight while the current one is multiplied.
+// (the swizzled [row][D] image, the tile mover and the multiply of score_tiles.h: one tile buffer, two barriers per tile); the
+// next tile's 16-byte global loads are in flight while the current one is multiplied.
 // The query is on the accumulator rows: lane (li, g) holds query rows 4g .. 4g+3 against gallery row 16 st + li of sub-tile st.
 // Each lane keeps its rows' running k-th-best score; a sub-tile none of whose scores beats it costs four compares and one
 // wave-uniform branch.  A score that does goes, one at a time, into the row's sorted list in LDS (all 64 lanes shift the list
 // in one step); about k ln(N / k) such inserts per row.  The lists go to the workspace: [Q][splits][k] keys.
 // Phase 2 (topk_merge_kernel): one work-group per query runs the same insert over its splits * k keys and decodes them.
-#include "cclip_common.h"
+#include "score_tiles.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
-
-typedef unsigned long long u64;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // one 16-byte chunk
 
 struct TopkArgs {
   const bf16* q; const bf16* g;
@@ -35,16 +32,6 @@ struct TopkArgs {
   u64* ws;
 };
 
-__device__ __forceinline__ unsigned score_key(float s) {
-  s += 0.0f;                                      // -0 -> +0: equal fp32 scores share one key
-  const unsigned b = __float_as_uint(s);
-  const unsigned key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return s != s ? 0u : key;
-}
-__device__ __forceinline__ float key_score(unsigned key) {
-  const unsigned b = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
-  return key == 0u ? __uint_as_float(0x7fc00000u) : __uint_as_float(b);
-}
 __device__ __forceinline__ u64 shfl64(u64 v, int src) {
   const unsigned lo = __shfl((unsigned)v, src, 64), hi = __shfl((unsigned)(v >> 32), src, 64);
   return ((u64)hi << 32) | lo;
@@ -61,21 +48,17 @@ __device__ __forceinline__ unsigned list_insert(volatile u64* L, int k, int lane
   return __shfl((unsigned)(nw >> 32), k - 1, 64);
 }
 
-// KSMAX: k-steps of 32 the A fragments are sized for (D <= 32 KSMAX); MT: query tiles of 16 rows per wave; GT: gallery rows per tile
+// <KSMAX, MT, GT> as in score_tiles.h: MT query tiles of 16 rows per wave, GT gallery rows per tile
 template <int KSMAX, int MT, int GT>
 __global__ __launch_bounds__(256) void topk_partial_kernel(const TopkArgs a) {
   constexpr int NST = GT / 16;                    // sub-tiles of 16 gallery rows
-  constexpr int IT = GT * KSMAX * 4 / 256;        // 16-byte chunks of a tile per thread, at most
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  const int D = a.D, k = a.k, Q = a.Q, N = a.N;
-  const int nks = D >> 5, cpr = D >> 3;           // k-steps; 16-byte chunks per row
-  const int rowbytes = D * 2;
-  const int low = cpr & -cpr;                     // swizzle over the largest power of two (<= 16) dividing a row's chunks
-  const int swz = (low > 16 ? 16 : low) - 1;
+  const int k = a.k, Q = a.Q, N = a.N;
+  const TileGeom geo(a.D);
   char* Gs = lds;
-  volatile u64* lists = (volatile u64*)(lds + GT * rowbytes) + (long)wave * (16 * MT) * k;
+  volatile u64* lists = (volatile u64*)(lds + GT * geo.rowbytes) + (long)wave * (16 * MT) * k;
 
   const int split = blockIdx.x % a.splits, qb = blockIdx.x / a.splits;
   const int n0 = split * a.rows_per_split;
@@ -86,14 +69,7 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(const TopkArgs a) {
   for (int i = lane; i < 16 * MT * k; i += 64) lists[i] = 0ull;
 
   bf16x8 af[MT][KSMAX];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int row = min(q0 + 16 * mt + li, Q - 1);
-    const bf16* qp = a.q + (long)row * a.ldq + 8 * g;
-#pragma unroll
-    for (int ks = 0; ks < KSMAX; ++ks)
-      if (ks < nks) af[mt][ks] = *(const bf16x8*)(qp + 32 * ks);
-  }
+  load_a_frags<KSMAX, MT>(af, a.q, a.ldq, q0, Q - 1, geo.nks, lane);
   // running k-th-best score of the rows this lane holds: NaN = list not full yet (everything passes), +inf = row beyond Q
   float tf[MT][4];
 #pragma unroll
@@ -102,49 +78,17 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(const TopkArgs a) {
     for (int r = 0; r < 4; ++r)
       tf[mt][r] = q0 + 16 * mt + 4 * g + r < Q ? __uint_as_float(0x7fc00000u) : __builtin_huge_valf();
 
-  int where[IT];                                  // (row << 8) | chunk of the it-th chunk this thread moves (beyond the tile: loaded, not kept)
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int idx = tid + 256 * it;
-    where[it] = idx < GT * cpr ? ((idx / cpr) << 8) | (idx % cpr) : 0;
-  }
-  u32x4 stage[IT];
-  // rows >= N are clamped (never selected), never read out of bounds
-#define TOPK_FETCH(base_)                                                                           \
-  _Pragma("unroll") for (int it = 0; it < IT; ++it) {                                                \
-    const int row_ = min((base_) + (where[it] >> 8), N - 1);                                         \
-    stage[it] = *(const u32x4*)(a.g + (long)row_ * a.ldg + (where[it] & 255) * 8);                   \
-  }
-
-  TOPK_FETCH(n0)
+  TileMover<KSMAX, GT> mover(geo, tid);
+  mover.fetch(a.g, a.ldg, n0, N - 1);             // rows >= N are clamped (never selected)
   for (int base = n0; base < n1; base += GT) {
     __syncthreads();                              // the previous tile has been read (and, first time, the lists are zero)
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-      if (tid + 256 * it < GT * cpr) {
-        const int row = where[it] >> 8, ch = where[it] & 255;
-        *(u32x4*)(Gs + row * rowbytes + ((ch ^ (row & swz)) << 4)) = stage[it];
-      }
+    mover.store(Gs);
     __syncthreads();
-    if (base + GT < n1) { TOPK_FETCH(base + GT) }
+    if (base + GT < n1) mover.fetch(a.g, a.ldg, base + GT, N - 1);
     if (!active) continue;
 
     f32x4 acc[MT][NST];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int st = 0; st < NST; ++st) acc[mt][st] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KSMAX; ++ks) {
-      if (ks >= nks) continue;
-#pragma unroll
-      for (int st = 0; st < NST; ++st) {
-        const int row = 16 * st + li, ch = 4 * ks + g;
-        const bf16x8 bfrag = *(const bf16x8*)(Gs + row * rowbytes + ((ch ^ (row & swz)) << 4));
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt][st] = CCLIP_MFMA_16x16x32(af[mt][ks], bfrag, acc[mt][st]);
-      }
-    }
+    tile_multiply<KSMAX, MT, GT>(acc, af, Gs, geo, lane);
 
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
@@ -237,13 +181,8 @@ static inline void topk_splits(int64_t Q, int64_t N, int* splits, int* rows_per_
 template <int KSMAX, int MT, int GT>
 static int topk_launch(const TopkArgs& a, hipStream_t stream) {
   const int nqb = (a.Q + 64 * MT - 1) / (64 * MT);
-  const size_t lds = (size_t)GT * a.D * 2 + (size_t)4 * 16 * MT * a.k * 8;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)topk_partial_kernel<KSMAX, MT, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return CCLIP_ERR_LAUNCH;
-  hipLaunchKernelGGL((topk_partial_kernel<KSMAX, MT, GT>), dim3((unsigned)(nqb * a.splits)), dim3(256), lds, stream, a);
-  return CCLIP_OK;
+  const size_t lds = (size_t)GT * a.D * 2 + (size_t)4 * 16 * MT * a.k * 8;   // one tile, the four waves' lists
+  return score_launch(topk_partial_kernel<KSMAX, MT, GT>, (unsigned)(nqb * a.splits), lds, a, stream);
 }
 
 }  // namespace CCLIP_NS
@@ -263,9 +202,7 @@ extern "C" int CCLIP_FN(cclip_similarity_topk)(const void* q, int64_t ldq, int32
                                                 int64_t workspace_bytes, hipStream_t stream) {
   if (!q || !g || !scores || !index || !workspace) return CCLIP_ERR_ARG;
   if (Q <= 0 || N <= 0 || N > 0x7fffffffLL || k < 1 || k > 64 || k > N) return CCLIP_ERR_ARG;
-  if (D <= 0 || (D & 31) || D > 1024) return CCLIP_ERR_ARG;
-  if ((ldq & 7) || (ldg & 7) || ldq < D || ldg < D) return CCLIP_ERR_ARG;
-  if (((uintptr_t)q | (uintptr_t)g) & 15) return CCLIP_ERR_ARG;
+  if (D <= 0 || !score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
   if (((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3) || ((uintptr_t)index & 3)) return CCLIP_ERR_ARG;
   TopkArgs a;
   a.q = (const bf16*)q; a.g = (const bf16*)g; a.ldq = ldq; a.ldg = ldg;

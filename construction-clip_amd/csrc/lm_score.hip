@@ -3,8 +3,8 @@
 // the log-sum-exp over j, the log-probability of labels[r], the argmax column and its logit.  The R x V logits are never
 // written: what reaches memory is one 24-byte partial per (row, vocabulary split), then four numbers per row.
 //
-// Logit independent of position.  As in embed_topk.hip every logit is ONE accumulator chain over d = 0, 32, 64 .. in that
-// order, whichever tile, split, lane or kernel variant its column and row land on.
+// Logit independent of position.  Every logit is ONE accumulator chain over d = 0, 32, 64 .. in that order (the tile multiply
+// of score_tiles.h), whichever tile, split, lane or kernel variant its column and row land on.
 // Reduction independent of R.  The vocabulary is cut into splits of LM_SPLIT_COLS columns: a function of V alone.  Inside a
 // split, lane li of a 16-lane group meets the columns n0 + li, n0 + li + 16, .. in ascending order and keeps, per row, an online
 // (max, sum of exp relative to it), the best column and the target logit; the 16 lanes are then combined by a fixed xor
@@ -12,16 +12,16 @@
 // accumulator row a hidden row sits, or on the variant (rows per wave, tile height) the launcher picks from R: a row's four
 // outputs are bit-identical scored alone or inside any batch.  No atomics: two launches are bitwise equal.
 //
-// Order of the argmax: the high word of embed_topk.hip's key (the logit's bits made monotone, NaN -> 0, -0 -> +0) with
+// Order of the argmax: score_key (score_key.h: the logit's bits made monotone, NaN -> 0, -0 -> +0) as the high word with
 // ~column as the low word.  The largest key wins: equal fp32 logits go to the LOWER column, NaN ranks below every number.
 //
 // Phase 1 (lm_partial_kernel): grid = row blocks x splits.  A work-group (4 waves) owns 64 * MT rows, wave w the rows
-// 16 MT w ..; their A fragments stay in registers.  W streams through two LDS buffers in tiles of GT vocabulary rows ([row][D]
-// 16-bit, 16-byte chunk c of row r at chunk c ^ (r & mask): conflict-free B-fragment reads); tile t + 1 is fetched into
+// 16 MT w ..; their A fragments stay in registers.  W streams through two LDS buffers in tiles of GT vocabulary rows (the
+// swizzled [row][D] image, the tile mover and the multiply of score_tiles.h); tile t + 1 is fetched into
 // registers while tile t is multiplied and lands in the other buffer, so a tile costs one barrier.  Rows beyond R and
 // columns beyond V are loaded clamped (never out of bounds) and masked: they contribute nothing.
 // Phase 2 (lm_merge_kernel): one thread per row folds its partials in split order.
-#include "cclip_common.h"
+#include "score_tiles.h"
 #include "../../include/cclip_hip.h"
 
 // the reductions below are written out operation by operation: no fused multiply-add may be formed from them, so that every
@@ -31,9 +31,6 @@
 #define LM_SPLIT_COLS 1024                        // vocabulary columns per split (a multiple of every GT)
 
 namespace CCLIP_NS {
-
-typedef unsigned long long u64;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // one 16-byte chunk
 
 struct LmPartial {                                // what one split knows about one row
   u64 key;                                        // best (monotone logit bits, ~column); 0 = none
@@ -51,33 +48,19 @@ struct LmArgs {
   LmPartial* ws;
 };
 
-__device__ __forceinline__ unsigned lm_score_key(float s) {
-  s += 0.0f;                                      // -0 -> +0: equal fp32 logits share one key
-  const unsigned b = __float_as_uint(s);
-  const unsigned key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return s != s ? 0u : key;
-}
-__device__ __forceinline__ float lm_key_score(unsigned key) {
-  const unsigned b = (key & 0x80000000u) ? (key ^ 0x80000000u) : ~key;
-  return key == 0u ? __uint_as_float(0x7fc00000u) : __uint_as_float(b);
-}
 // weight of a partial whose max is m inside a combination whose max is M (an empty partial, m = -inf, weighs nothing)
 __device__ __forceinline__ float lm_weight(float m, float M) { return m == -__builtin_huge_valf() ? 0.0f : __expf(m - M); }
 
-// KSMAX: k-steps of 32 the A fragments are sized for (D <= 32 KSMAX); MT: row tiles of 16 per wave; GT: vocabulary rows per tile
+// <KSMAX, MT, GT> as in score_tiles.h: MT row tiles of 16 per wave, GT vocabulary rows per tile
 template <int KSMAX, int MT, int GT>
 __global__ __launch_bounds__(256) void lm_partial_kernel(const LmArgs a) {
   constexpr int NST = GT / 16;                    // sub-tiles of 16 vocabulary rows
-  constexpr int IT = GT * KSMAX * 4 / 256;        // 16-byte chunks of a tile per thread, at most
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
-  const int D = a.D, R = a.R, V = a.V;
-  const int nks = D >> 5, cpr = D >> 3;           // k-steps; 16-byte chunks per row
-  const int rowbytes = D * 2;
-  const int low = cpr & -cpr;                     // swizzle over the largest power of two (<= 16) dividing a row's chunks
-  const int swz = (low > 16 ? 16 : low) - 1;
-  const int tilebytes = GT * rowbytes;
+  const int R = a.R, V = a.V;
+  const TileGeom geo(a.D);
+  const int tilebytes = GT * geo.rowbytes;
 
   const int split = blockIdx.x % a.splits, rb = blockIdx.x / a.splits;
   const int n0 = split * LM_SPLIT_COLS;
@@ -86,14 +69,7 @@ __global__ __launch_bounds__(256) void lm_partial_kernel(const LmArgs a) {
   const bool active = q0 < R;                     // (wave-uniform) a wave without rows only helps to load
 
   bf16x8 af[MT][KSMAX];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int row = min(q0 + 16 * mt + li, R - 1);
-    const bf16* xp = a.x + (long)row * a.ldx + 8 * g;
-#pragma unroll
-    for (int ks = 0; ks < KSMAX; ++ks)
-      if (ks < nks) af[mt][ks] = *(const bf16x8*)(xp + 32 * ks);
-  }
+  load_a_frags<KSMAX, MT>(af, a.x, a.ldx, q0, R - 1, geo.nks, lane);
   // per-row state of this lane: rows q0 + 16 mt + 4 g + r against the columns n0 + li + 16 i
   float rm[MT][4], rs[MT][4], rt[MT][4];
   unsigned bhi[MT][4];
@@ -108,50 +84,18 @@ __global__ __launch_bounds__(256) void lm_partial_kernel(const LmArgs a) {
       lab[mt][r] = row < R ? a.labels[row] : -1;  // a label outside the split's columns simply never matches
     }
 
-  int where[IT];                                  // (row << 8) | chunk of the it-th chunk this thread moves (beyond the tile: loaded, not kept)
-#pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int idx = tid + 256 * it;
-    where[it] = idx < GT * cpr ? ((idx / cpr) << 8) | (idx % cpr) : 0;
-  }
-  u32x4 stage[IT];
-  // rows >= V are clamped (masked below), never read out of bounds
-#define LM_FETCH(base_)                                                                             \
-  _Pragma("unroll") for (int it = 0; it < IT; ++it) {                                                \
-    const int row_ = min((base_) + (where[it] >> 8), V - 1);                                         \
-    stage[it] = *(const u32x4*)(a.w + (long)row_ * a.ldw + (where[it] & 255) * 8);                   \
-  }
-
-  LM_FETCH(n0)
+  TileMover<KSMAX, GT> mover(geo, tid);
+  mover.fetch(a.w, a.ldw, n0, V - 1);             // rows >= V are clamped (masked below)
   int buf = 0;
   for (int base = n0; base < n1; base += GT, buf ^= 1) {
     char* Ws = lds + buf * tilebytes;
-#pragma unroll
-    for (int it = 0; it < IT; ++it)
-      if (tid + 256 * it < GT * cpr) {
-        const int row = where[it] >> 8, ch = where[it] & 255;
-        *(u32x4*)(Ws + row * rowbytes + ((ch ^ (row & swz)) << 4)) = stage[it];
-      }
+    mover.store(Ws);
     __syncthreads();                              // tile `base` is whole; every wave has left the tile before last (this buffer's next content)
-    if (base + GT < n1) { LM_FETCH(base + GT) }
+    if (base + GT < n1) mover.fetch(a.w, a.ldw, base + GT, V - 1);
     if (!active) continue;
 
     f32x4 acc[MT][NST];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int st = 0; st < NST; ++st) acc[mt][st] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KSMAX; ++ks) {
-      if (ks >= nks) continue;
-#pragma unroll
-      for (int st = 0; st < NST; ++st) {
-        const int row = 16 * st + li, ch = 4 * ks + g;
-        const bf16x8 bfrag = *(const bf16x8*)(Ws + row * rowbytes + ((ch ^ (row & swz)) << 4));
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt][st] = CCLIP_MFMA_16x16x32(af[mt][ks], bfrag, acc[mt][st]);
-      }
-    }
+    tile_multiply<KSMAX, MT, GT>(acc, af, Ws, geo, lane);
 
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
@@ -168,13 +112,12 @@ __global__ __launch_bounds__(256) void lm_partial_kernel(const LmArgs a) {
           const float e = __expf(-fabsf(z - m));  // exp(min - max); the first column meets m = -inf: e = 0, s = 1
           rs[mt][r] = z > m ? rs[mt][r] * e + 1.0f : rs[mt][r] + e;   // NaN z: s = NaN, m unchanged
           rm[mt][r] = fmaxf(m, z);
-          const unsigned hi = lm_score_key(z);
+          const unsigned hi = score_key(z);
           if (hi > bhi[mt][r]) { bhi[mt][r] = hi; bi[mt][r] = col; }  // ascending columns: ties keep the lower one
           if (col == lab[mt][r]) rt[mt][r] = z;
         }
     }
   }
-#undef LM_FETCH
 
   if (!active) return;
   // the 16 lanes of a group -> one partial per row (xor butterfly: both partners compute the same bits)
@@ -231,7 +174,7 @@ __global__ __launch_bounds__(256) void lm_merge_kernel(const LmPartial* __restri
   logp[row] = lp;
   if (lse) lse[row] = l;
   if (pred) pred[row] = (int)~(unsigned)key;
-  if (pred_logit) pred_logit[row] = lm_key_score((unsigned)(key >> 32));
+  if (pred_logit) pred_logit[row] = key_score((unsigned)(key >> 32));
 }
 
 template <int KSMAX, int MT, int GT>
@@ -239,13 +182,8 @@ static int lm_launch(const LmArgs& a, hipStream_t stream) {
   static_assert(LM_SPLIT_COLS % GT == 0, "a split is a whole number of tiles");
   const long nrb = ((long)a.R + 64 * MT - 1) / (64 * MT);
   if (nrb * a.splits > 0x7fffffffL) return CCLIP_ERR_ARG;
-  const size_t lds = (size_t)2 * GT * a.D * 2;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)lm_partial_kernel<KSMAX, MT, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess)
-    return CCLIP_ERR_LAUNCH;
-  hipLaunchKernelGGL((lm_partial_kernel<KSMAX, MT, GT>), dim3((unsigned)(nrb * a.splits)), dim3(256), lds, stream, a);
-  return CCLIP_OK;
+  const size_t lds = (size_t)2 * GT * a.D * 2;    // two tiles
+  return score_launch(lm_partial_kernel<KSMAX, MT, GT>, (unsigned)(nrb * a.splits), lds, a, stream);
 }
 
 }  // namespace CCLIP_NS
@@ -263,9 +201,7 @@ extern "C" int CCLIP_FN(cclip_lm_head_score)(const void* x, int64_t ldx, int32_t
                                               float* pred_logit, void* workspace, hipStream_t stream) {
   if (!x || !w || !labels || !logp || !workspace) return CCLIP_ERR_ARG;
   if (R <= 0 || V <= 0) return CCLIP_ERR_ARG;
-  if (D < 32 || (D & 31) || D > 1024) return CCLIP_ERR_ARG;
-  if ((ldx & 7) || (ldw & 7) || ldx < D || ldw < D) return CCLIP_ERR_ARG;
-  if (((uintptr_t)x | (uintptr_t)w) & 15) return CCLIP_ERR_ARG;
+  if (D < 32 || !score_operands_ok(x, ldx, w, ldw, D)) return CCLIP_ERR_ARG;
   if (((uintptr_t)workspace & 7) || ((uintptr_t)logp & 3) || ((uintptr_t)lse & 3) || ((uintptr_t)pred & 3) ||
       ((uintptr_t)pred_logit & 3) || ((uintptr_t)labels & 3))
     return CCLIP_ERR_ARG;

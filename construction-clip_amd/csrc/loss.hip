@@ -8,7 +8,7 @@
 //                    (/root/reference/CLIP/train.py:162-173: CE(logits_per_image, arange) and
 //                    CE(logits_per_text, arange), accuracy = argmax == label) and for the caption
 //                    LM loss with ignore_index (/root/reference/CLIP_prefix_caption/train.py:357).
-#include "cclip_common.h"
+#include "row_kernels.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
@@ -60,16 +60,7 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float* logits, lon
       if (v > m) { s = s * __expf(m - v) + 1.f; m = v; arg = c; }
       else s += __expf(v - m);
     }
-    // combine (m, s, arg) across lanes; ties -> smallest index (torch.argmax returns the first max)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-      const int a2 = __shfl_xor(arg, o, 64);
-      const float mn = fmaxf(m, m2);
-      s = s * (m == mn ? 1.f : __expf(m - mn)) + s2 * (m2 == mn ? 1.f : __expf(m2 - mn));
-      if (m2 > m || (m2 == m && a2 < arg)) arg = a2;
-      m = mn;
-    }
+    wave_softmax_argmax(m, s, arg);
     const float lse = m + __logf(s);
     const bool ignored = label == ignore_index || label < 0 || label >= C;
     const float at_label = ignored ? 0.f : row[label];
@@ -112,8 +103,6 @@ __global__ __launch_bounds__(1024) void reduce_dot_kernel(const float* __restric
 
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
-
-static int grid_rows4(int rows) { int g = (rows + 3) / 4; return g > 4096 ? 4096 : (g < 1 ? 1 : g); }
 
 #ifndef CCLIP_F16
 extern "C" int cclip_l2norm_fwd(const float* x, int64_t ldx, int32_t rows, int32_t D, float* y, int64_t ldy,

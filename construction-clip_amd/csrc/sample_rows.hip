@@ -36,7 +36,7 @@
 //
 // One 256-thread work-group per row; passes over the row: max, four levels, draw.  48 KB of LDS, no global scratch, no
 // workspace, every loop bound known at launch.
-#include "cclip_common.h"
+#include "score_key.h"
 #include "../../include/cclip_hip.h"
 
 #define SR_BINS 4096                              // bins of a radix level (12 bits) = segments of the draw
@@ -59,12 +59,7 @@ struct SrShared {
   u64 mass_excl, bin_mass;
 };
 
-__device__ __forceinline__ u64 sr_key(float x, int id) {
-  x += 0.0f;                                      // -0 -> +0: equal fp32 logits share one key
-  const unsigned b = __float_as_uint(x);
-  const unsigned mono = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((u64)mono << 16) | (unsigned)(0xffff - id);
-}
+__device__ __forceinline__ u64 sr_key(float x, int id) { return ((u64)mono_bits(x) << 16) | (unsigned)(0xffff - id); }
 
 __device__ __forceinline__ u64 sr_mass(float x, float xmax, float inv_t) {
   const float e = __expf((x - xmax) * inv_t);

@@ -20,7 +20,7 @@
 // so nothing overflows at either end (|u| = 100: loss terms |u| and 0, gradients grad_scale and 0).  log1p(e) is taken as
 // log(w) + (e - (w - 1)) / w: w - 1 and e - (w - 1) are exact, and the second term is the first order of log((1 + e) / w), the
 // part of e that rounding 1 + e to w dropped (all of e once e < 2^-24, where log(w) = 0).
-#include "cclip_common.h"
+#include "row_kernels.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
@@ -72,13 +72,7 @@ __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* logits, 
       const float d = step(row[c], col_class[c], c);
       if (GRAD) drow[c] = d;
     }
-    // combine (m, arg) across lanes; ties -> smallest index (torch.argmax returns the first max)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float m2 = __shfl_xor(m, o, 64);
-      const int a2 = __shfl_xor(arg, o, 64);
-      if (m2 > m || (m2 == m && a2 < arg)) { m = m2; arg = a2; }
-    }
+    wave_argmax(m, arg);
     if (loss_row) { loss = wave_sum(loss); if (lane == 0) loss_row[r] = labelled ? loss : 0.f; }
     if (lane == 0) {
       if (pred) pred[r] = arg;
@@ -93,8 +87,6 @@ __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* logits, 
 
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
-
-static int grid_rows4(int rows) { int g = (rows + 3) / 4; return g > 4096 ? 4096 : (g < 1 ? 1 : g); }
 
 extern "C" int cclip_sigmoid_rows(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* row_class,
                                   const int32_t* col_class, const float* bias_dev, float grad_scale, float* loss_row,

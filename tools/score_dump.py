@@ -1,0 +1,203 @@
+"""Bit-identity check of the scoring and fp32 row kernels across a change that must not alter their results (a refactor of
+csrc/score_tiles.h, score_key.h or row_kernels.h, a compiler update): seeded inputs, every output tensor saved raw.
+
+    python tools/score_dump.py --out before.pt        # on the build to compare against
+    python tools/score_dump.py --compare before.pt    # on the new build: exit status 1 at the first tensor that differs
+
+similarity_topk and lm_head_score run in bf16 and fp16 over shapes that reach every kernel variant, both row-tile counts, a
+partly empty work-group, row widths that are not a power-of-two number of chunks, padded row strides, a column slice of a
+wider buffer, duplicated rows / equal columns, a NaN row, an ignored and an out-of-range label.  xent_rows,
+xent_rows_classes and sigmoid_rows: R = 9 over C = 1, 63, 64, 257, 300 without a gradient, with one, and with the gradient
+written over the logits, every input holding a row of ties and an all-NaN row; xent_rows also with a 16-bit gradient.
+caption_select: N = 3, K = 1, 5, 64, E = 4, 512, 1024 with references, with and without lm_mean, with a NaN score.
+sample_rows: V = 5, 4099, 50257 with top-k, with top-p and with neither, from fixed u.  l2norm_fwd and text_embed: one case."""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "construction-clip_amd")]
+from cclip_hip import ops  # noqa: E402
+
+DTYPES = ((torch.bfloat16, "bf16"), (torch.float16, "f16"))
+TOPK_SHAPES = [(1, 1, 64, 1), (3, 5, 128, 5), (16, 64, 512, 10), (130, 4097, 128, 10), (100, 1000, 768, 64), (16, 1000, 1024, 10),
+               (3, 1000, 32, 5), (100, 1000, 96, 5), (100, 4097, 160, 10)]
+LM_SHAPES = [(1, 1, 32), (3, 15, 32), (17, 300, 128), (300, 300, 128), (70, 2050, 512), (65, 4099, 768), (33, 1000, 1024)]
+ROW_R, ROW_C = 9, (1, 63, 64, 257, 300)
+
+
+def rnd(seed, *shape, scale=1.0):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
+
+
+def padded(t, pad):
+    """t's values as a view of a buffer whose rows are `pad` elements longer"""
+    buf = torch.zeros(t.shape[0], t.shape[1] + pad, dtype=t.dtype, device=t.device)
+    buf[:, :t.shape[1]] = t
+    return buf[:, :t.shape[1]]
+
+
+def topk_cases():
+    for dt, tag in DTYPES:
+        for i, (Q, N, D, k) in enumerate(TOPK_SHAPES):
+            q, g = rnd(100 + i, Q, D).to(dt).cuda(), rnd(200 + i, N, D).to(dt).cuda()
+            yield f"topk/{tag}/{Q}x{N}x{D}k{k}", dict(zip(("scores", "index"), ops.similarity_topk(q, g, k)))
+        Q, N, D, k = 130, 4097, 128, 10
+        q, g = rnd(150, Q, D).to(dt).cuda(), rnd(250, N, D).to(dt).cuda()
+        yield f"topk/{tag}/padded", dict(zip(("scores", "index"), ops.similarity_topk(padded(q, 8), padded(g, 24), k)))
+        dup = g.clone()
+        dup[1::3] = dup[0:-1:3][:dup[1::3].shape[0]]               # every third row repeats its predecessor: equal scores
+        yield f"topk/{tag}/duplicates", dict(zip(("scores", "index"), ops.similarity_topk(q, dup, k)))
+        nan = g.clone()
+        nan[77] = float("nan")
+        yield f"topk/{tag}/nan_row", dict(zip(("scores", "index"), ops.similarity_topk(q, nan, k)))
+
+
+def lm_cases():
+    names = ("logp", "lse", "pred", "pred_logit")
+    for dt, tag in DTYPES:
+        for i, (R, V, D) in enumerate(LM_SHAPES):
+            x, w = rnd(300 + i, R, D).to(dt).cuda(), rnd(400 + i, V, D, scale=0.3).to(dt).cuda()
+            labels = torch.randint(0, V, (R,), generator=torch.Generator().manual_seed(500 + i)).to(torch.int32).cuda()
+            yield f"lm/{tag}/{R}x{V}x{D}", dict(zip(names, ops.lm_head_score(x, w, labels)))
+        R, V, D = 70, 2050, 128
+        wide = rnd(350, R, D + 64).to(dt).cuda()
+        w = rnd(450, V, D, scale=0.3).to(dt).cuda()
+        w[1500] = w[20]                                             # two equal columns: the lower one wins a tie
+        labels = torch.randint(0, V, (R,), generator=torch.Generator().manual_seed(550)).to(torch.int32)
+        labels[3], labels[4], labels[5] = -100, V, -1               # ignored; out of range above and below
+        yield f"lm/{tag}/slice_labels_equal_columns", dict(zip(names, ops.lm_head_score(wide[:, 32:32 + D], w, labels.cuda())))
+
+
+def row_inputs(C, seed):
+    logits = rnd(seed, ROW_R, C, scale=3.0)
+    logits[2] = 1.5                                                 # a row of ties: the first column is the argmax
+    logits[6] = float("nan")                                        # a row without a maximum
+    g = torch.Generator().manual_seed(seed + 1)
+    row_class = torch.randint(-1, 4, (ROW_R,), generator=g).to(torch.int32)
+    col_class = torch.randint(-1, 4, (C,), generator=g).to(torch.int32)
+    labels = torch.randint(0, C, (ROW_R,), generator=g).to(torch.int32)
+    labels[1] = -100
+    return logits.cuda(), labels.cuda(), row_class.cuda(), col_class.cuda()
+
+
+def row_cases():
+    bias = torch.tensor([-0.75], device="cuda")
+    for C in ROW_C:
+        for grad in ("none", "f32", "alias", "bf16", "f16"):
+            logits, labels, row_class, col_class = row_inputs(C, 600 + C)
+            f = lambda dt=torch.float32: torch.zeros(ROW_R, device="cuda", dtype=dt)  # noqa: E731
+            dl = {"none": None, "f32": torch.zeros_like(logits), "alias": logits, "bf16": torch.zeros_like(logits, dtype=torch.bfloat16),
+                  "f16": torch.zeros_like(logits, dtype=torch.float16)}[grad]
+            out = {"loss_row": f(), "pred": f(torch.int32)}
+            if dl is not None:
+                out.update(dlogits=dl, rowdot=f())
+            ops.xent_rows(logits, labels, loss_row=out["loss_row"], pred=out["pred"], dlogits=dl, grad_scale=0.37, rowdot=out.get("rowdot"))
+            yield f"xent_rows/C{C}/{grad}", out
+            if grad in ("bf16", "f16"):
+                continue
+            logits, labels, row_class, col_class = row_inputs(C, 600 + C)
+            dl = {"none": None, "f32": torch.zeros_like(logits), "alias": logits}[grad]
+            out = {"loss_row": f(), "pred": f(torch.int32), "hit": f()}
+            if dl is not None:
+                out.update(dlogits=dl, rowdot=f())
+            ops.xent_rows_classes(logits, row_class, col_class, loss_row=out["loss_row"], pred=out["pred"], hit=out["hit"], dlogits=dl,
+                                  grad_scale=0.37, rowdot=out.get("rowdot"))
+            yield f"xent_rows_classes/C{C}/{grad}", out
+            logits, labels, row_class, col_class = row_inputs(C, 600 + C)
+            dl = {"none": None, "f32": torch.zeros_like(logits), "alias": logits}[grad]
+            out = {"loss_row": f(), "pred": f(torch.int32), "hit": f()}
+            if dl is not None:
+                out.update(dlogits=dl, rowdot=f(), rowsum=f())
+            ops.sigmoid_rows(logits, row_class, col_class, bias, loss_row=out["loss_row"], pred=out["pred"], hit=out["hit"], dlogits=dl,
+                             grad_scale=0.37, rowdot=out.get("rowdot"), rowsum=out.get("rowsum"))
+            yield f"sigmoid_rows/C{C}/{grad}", out
+
+
+def select_cases():
+    N = 3
+    names = ("cos", "clip_score", "ref_score", "score", "order", "best")
+    for K in (1, 5, 64):
+        for E in (4, 512, 1024):
+            img, txt, ref = rnd(700 + E, N, E).cuda(), rnd(710 + K + E, N * K, E).cuda(), rnd(720 + E, 4, E).cuda()
+            if K > 1:
+                txt[1] = txt[0]                                     # two candidates with equal scores: the lower k first
+            lm = rnd(730 + K, N * K).cuda()
+            lm_nan = lm.clone()
+            lm_nan[N * K // 2] = float("nan")
+            for tag, lm_mean in (("no_lm", None), ("lm", lm), ("lm_nan", lm_nan)):
+                out = ops.caption_select(img, txt, K, lm_mean=lm_mean, ref=ref, ref_off=[0, 3, 3, 4], lm_weight=0.2)
+                yield f"caption_select/K{K}/E{E}/{tag}", dict(zip(names, out))
+
+
+def sample_cases():
+    n = 4
+    u = torch.tensor([0.0, 0.31, 0.77, 0.999], device="cuda")
+    for V in (5, 4099, 50257):
+        logits = rnd(800 + V, n, V, scale=2.0)
+        logits[1, : min(V, 3)] = logits[1].max()                    # tied maxima
+        logits = logits.cuda()
+        for tag, kw in (("top_k", dict(top_k=4)), ("top_p", dict(top_p=0.8)), ("plain", {})):
+            done = torch.tensor([0, 0, 1, 0], dtype=torch.int32, device="cuda")
+            out = ops.sample_rows(logits, u, done, inv_temperature=1.25, stop_token=2, **kw)
+            yield f"sample_rows/V{V}/{tag}", dict(zip(("token", "logprob", "n_kept", "kept_mass"), out), done=done)
+
+
+def grid_cases():
+    x = rnd(900, 9, 70).cuda()
+    y, inv = torch.zeros_like(x), torch.zeros(9, device="cuda")
+    ops.l2norm_fwd(x, y, inv)
+    yield "l2norm_fwd/9x70", {"y": y, "inv_norm": inv}
+    rows, L, D, V = 10, 5, 72, 11
+    text = torch.randint(-1, V + 1, (rows,), generator=torch.Generator().manual_seed(901)).to(torch.int32).cuda()
+    out = torch.zeros(rows, D, device="cuda")
+    ops.text_embed(text, rnd(902, V, D).cuda(), rnd(903, L, D).cuda(), out, rows=rows, L=L)
+    yield f"text_embed/{rows}x{D}", {"x": out}
+
+
+def cases():
+    """(name, {tensor name: tensor}) of every launch, in a fixed order"""
+    for gen in (topk_cases, lm_cases, row_cases, select_cases, sample_cases, grid_cases):
+        yield from gen()
+
+
+def raw(t):
+    """the tensor's bytes on the host, as int8: every bit pattern (NaN payloads, 16-bit floats) compares as it is"""
+    return t.detach().contiguous().cpu().view(torch.int8)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument("--out", help="run the cases and save every output tensor here")
+    g.add_argument("--compare", help="run the cases and compare with the tensors saved here, byte by byte")
+    args = ap.parse_args()
+    saved = torch.load(args.compare) if args.compare else {}
+    n_cases = n = 0
+    for name, tensors in cases():
+        for key, t in tensors.items():
+            if t is None:
+                continue
+            now = (str(t.dtype), tuple(t.shape), raw(t))
+            old = saved.get(f"{name}:{key}")
+            if args.compare and not (old is not None and old[:2] == now[:2] and torch.equal(old[2], now[2])):
+                print(f"DIFFERENT  {name}:{key}", flush=True)
+                sys.exit(1)
+            saved[f"{name}:{key}"] = now
+            n += 1
+        n_cases += 1
+        print(f"{'same' if args.compare else 'run '}  {name}", flush=True)
+    if args.compare:
+        if n != len(saved):
+            print(f"DIFFERENT  {len(saved)} tensors saved, {n} produced", flush=True)
+            sys.exit(1)
+        print(f"{n_cases} cases, {n} tensors byte-identical to {args.compare}")
+    else:
+        torch.save(saved, args.out)
+        print(f"{n_cases} cases, {n} tensors saved to {args.out}")
+
+
+if __name__ == "__main__":
+    main()
