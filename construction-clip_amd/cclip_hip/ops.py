@@ -1515,10 +1515,14 @@ def xent_rows(logits, labels_i32, *, loss_row=None, pred=None, dlogits=None, gra
                               c_long(0 if dlogits is None else dlogits.stride(0)), _p(rowdot), _stream()), "cclip_xent_rows")
 
 
-def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pred=None, hit=None, dlogits=None,
-                      grad_scale: float = 1.0, rowdot=None) -> None:
-    """Class-aware row cross-entropy (include/cclip_hip.h, cclip_xent_rows_classes): the positives of row r are the columns
-    whose class equals row_class[r]; a negative class id is 'unlabelled'.  fp32 only; dlogits may be `logits` itself."""
+_PER_ROW = (("loss_row", torch.float32), ("pred", torch.int32), ("hit", torch.float32), ("rowdot", torch.float32),
+            ("rowsum", torch.float32))
+
+
+def _class_rows(logits, row_class_i32, col_class_i32, dlogits, *per_row):
+    """The arguments the class-vector row losses share (xent_rows_classes, sigmoid_rows): fp32 logits [R, C] with unit column
+    stride, the int32 class vectors [R] and [C], the optional fp32 gradient, which may be `logits` itself, and the optional
+    per-row outputs [R] in the order of _PER_ROW.  Returns (R, C)."""
     _req(logits, torch.float32, "logits"); _req(row_class_i32, torch.int32, "row_class"); _req(col_class_i32, torch.int32, "col_class")
     if logits.dim() != 2 or logits.stride(1) != 1:
         raise ValueError(f"logits: expected [R, C] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
@@ -1526,8 +1530,7 @@ def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pr
     for t, n, name in ((row_class_i32, R, "row_class"), (col_class_i32, C, "col_class")):
         if t.shape != (n,) or not t.is_contiguous():
             raise ValueError(f"{name}: expected contiguous [{n}], got {tuple(t.shape)}")
-    for t, dt, name in ((loss_row, torch.float32, "loss_row"), (pred, torch.int32, "pred"), (hit, torch.float32, "hit"),
-                        (rowdot, torch.float32, "rowdot")):
+    for t, (name, dt) in zip(per_row, _PER_ROW):
         if t is not None:
             _req(t, dt, name)
             if t.shape != (R,) or not t.is_contiguous():
@@ -1536,6 +1539,14 @@ def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pr
         _req(dlogits, torch.float32, "dlogits")
         if dlogits.shape != (R, C) or dlogits.stride(1) != 1:
             raise ValueError(f"dlogits: expected [{R}, {C}] with unit column stride, got {tuple(dlogits.shape)}")
+    return R, C
+
+
+def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pred=None, hit=None, dlogits=None,
+                      grad_scale: float = 1.0, rowdot=None) -> None:
+    """Class-aware row cross-entropy (include/cclip_hip.h, cclip_xent_rows_classes): the positives of row r are the columns
+    whose class equals row_class[r]; a negative class id is 'unlabelled'.  fp32 only; dlogits may be `logits` itself."""
+    R, C = _class_rows(logits, row_class_i32, col_class_i32, dlogits, loss_row, pred, hit, rowdot)
     check(lib.cclip_xent_rows_classes(_p(logits), c_long(logits.stride(0)), c_int(R), c_int(C), _p(row_class_i32),
                                       _p(col_class_i32), c_float(grad_scale), _p(loss_row), _p(pred), _p(hit), _p(dlogits),
                                       c_long(0 if dlogits is None else dlogits.stride(0)), _p(rowdot), _stream()),
@@ -1547,27 +1558,11 @@ def sigmoid_rows(logits, row_class_i32, col_class_i32, bias, *, loss_row=None, p
     """Pairwise sigmoid (SigLIP) row loss (include/cclip_hip.h, cclip_sigmoid_rows): cell (r, c) is a positive when column c
     carries row r's class, a negative otherwise; a negative class id is 'unlabelled'.  `bias` is a one-element fp32 device
     tensor (never read on the host).  fp32 only; dlogits may be `logits` itself; rowdot / rowsum come only with dlogits."""
-    _req(logits, torch.float32, "logits"); _req(row_class_i32, torch.int32, "row_class"); _req(col_class_i32, torch.int32, "col_class")
     _req(bias, torch.float32, "bias")
-    if logits.dim() != 2 or logits.stride(1) != 1:
-        raise ValueError(f"logits: expected [R, C] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
     if bias.numel() != 1:
         raise ValueError(f"bias: expected one element, got {tuple(bias.shape)}")
-    R, C = logits.shape
-    for t, n, name in ((row_class_i32, R, "row_class"), (col_class_i32, C, "col_class")):
-        if t.shape != (n,) or not t.is_contiguous():
-            raise ValueError(f"{name}: expected contiguous [{n}], got {tuple(t.shape)}")
-    for t, dt, name in ((loss_row, torch.float32, "loss_row"), (pred, torch.int32, "pred"), (hit, torch.float32, "hit"),
-                        (rowdot, torch.float32, "rowdot"), (rowsum, torch.float32, "rowsum")):
-        if t is not None:
-            _req(t, dt, name)
-            if t.shape != (R,) or not t.is_contiguous():
-                raise ValueError(f"{name}: expected contiguous [{R}], got {tuple(t.shape)}")
-    if dlogits is not None:
-        _req(dlogits, torch.float32, "dlogits")
-        if dlogits.shape != (R, C) or dlogits.stride(1) != 1:
-            raise ValueError(f"dlogits: expected [{R}, {C}] with unit column stride, got {tuple(dlogits.shape)}")
-    elif rowdot is not None or rowsum is not None:
+    R, C = _class_rows(logits, row_class_i32, col_class_i32, dlogits, loss_row, pred, hit, rowdot, rowsum)
+    if dlogits is None and (rowdot is not None or rowsum is not None):
         raise ValueError("rowdot / rowsum are written only together with dlogits")
     check(lib.cclip_sigmoid_rows(_p(logits), c_long(logits.stride(0)), c_int(R), c_int(C), _p(row_class_i32), _p(col_class_i32),
                                  _p(bias), c_float(grad_scale), _p(loss_row), _p(pred), _p(hit), _p(dlogits),

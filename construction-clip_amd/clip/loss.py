@@ -19,16 +19,23 @@ token rows equally across ranks for the data-parallel (square) form.
 `sigmoid_loss` / `SigmoidLoss` is the second objective: SigLIP's pairwise sigmoid loss over the same logits plus a learnable
 bias, pairwise or class-aware by the same `labels=` conventions, on ops.sigmoid_rows (one logits GEMM, one row-kernel launch).
 
+Two autograd Functions, `_Contrastive` (both softmax forms) and `_Sigmoid`, differ in their row kernels and statistics.  The
+steps around those are written once: `_normalise_gather` (two l2norm_fwd, the all-gather), `_feature_grads` (cross GEMMs,
+reduce-scatter, local GEMMs), `_backward_tail` (two l2norm_bwd, the logit_scale gradient) and `_classes` (what `labels` and
+`text_labels` mean, with the refusals).  tools/loss_dump.py records the launch sequence and the results of every form.
+
 All arithmetic goes through cclip_hip.ops (HIP kernels); torch.distributed only moves bytes.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
 from cclip_hip import ops
+
+from .parallel import collectives_active as _collectives
 
 
 def _world(group) -> Tuple[int, int]:
@@ -37,182 +44,175 @@ def _world(group) -> Tuple[int, int]:
     return 0, 1
 
 
-def _collectives(group) -> bool:
-    from .parallel import collectives_active
-    return collectives_active(group)
+class _Ranks(NamedTuple):
+    group: object
+    dp: bool                # the collectives run: world > 1, or a forced one-rank RCCL pass (clip.parallel.collectives_active)
+    rank: int
+    world: int
+
+
+def _ranks(group) -> _Ranks:
+    dp = _collectives(group)
+    return _Ranks(group, dp, *(_world(group) if dp else (0, 1)))
+
+
+class _Features(NamedTuple):
+    i_n: torch.Tensor       # this rank's normalised rows [N_loc, E], [M_loc, E]
+    t_n: torch.Tensor
+    inv_i: torch.Tensor     # their 1 / norm
+    inv_t: torch.Tensor
+    i_all: Optional[torch.Tensor]   # every rank's rows [N, E] (None: the one-sided form never reads them), [M, E]
+    t_all: torch.Tensor
+    packed: bool            # i_n | t_n are the column halves of one buffer; the gradient buffers then follow suit
+
+
+def _scalar(x: torch.Tensor) -> torch.Tensor:
+    """a scalar as a one-element fp32 device tensor: the launchers read it on the device, never on the host"""
+    return x.detach().float().reshape(1).contiguous()
+
+
+def _pair(rows_i: int, rows_t: int, E: int, dev, packed: bool):
+    """fp32 buffers for an image side [rows_i, E] and a text side [rows_t, E] -> (whole, image, text).  Packed (square forms)
+    they are the column halves of ONE [rows_i, 2E] buffer [ I | T ], which one collective moves whole; else whole is None."""
+    if packed:
+        whole = torch.empty(rows_i, 2 * E, device=dev, dtype=torch.float32)
+        return whole, whole[:, :E], whole[:, E:]
+    return None, torch.empty(rows_i, E, device=dev, dtype=torch.float32), torch.empty(rows_t, E, device=dev, dtype=torch.float32)
+
+
+def _normalise_gather(fi, ft, mloc: int, r: _Ranks, packed: bool, one_sided: bool) -> _Features:
+    """L2-normalise both sides and, under data parallelism, exchange them with ONE all-gather: of the packed [N_loc, 2E]
+    buffer, or one-sided (only L = s I_loc T_all^T is formed, nothing reads I_all) of the text rows alone."""
+    dev = fi.device
+    nloc, E = fi.shape
+    whole, i_n, t_n = _pair(nloc, mloc, E, dev, packed)
+    inv_i = torch.empty(nloc, device=dev, dtype=torch.float32)
+    inv_t = torch.empty(mloc, device=dev, dtype=torch.float32)
+    ops.l2norm_fwd(fi, i_n, inv_i)
+    ops.l2norm_fwd(ft, t_n, inv_t)
+    if not r.dp:
+        return _Features(i_n, t_n, inv_i, inv_t, i_n, t_n, packed)
+    if one_sided:
+        t_all = torch.empty(mloc * r.world, E, device=dev, dtype=torch.float32)
+        dist.all_gather_into_tensor(t_all, t_n, group=r.group)
+        return _Features(i_n, t_n, inv_i, inv_t, None, t_all, packed)
+    gathered = torch.empty(nloc * r.world, 2 * E, device=dev, dtype=torch.float32)
+    dist.all_gather_into_tensor(gathered, whole, group=r.group)
+    return _Features(i_n, t_n, inv_i, inv_t, gathered[:, :E], gathered[:, E:], packed)
+
+
+def _feature_grads(L_i, L_t, f: _Features, ls, r: _Ranks):
+    """d/d(normalised features) -> (d_i [N_loc, E], d_t [M_loc, E]) from the logits gradients L_i [N_loc, M] and L_t [M_loc, N]:
+    the other ranks' rows that used our features (cross GEMMs over all N | M rows, brought home by ONE reduce-scatter) plus our
+    own rows (local GEMMs, beta = 1).  L_t None is the one-sided form: no row block has image columns, so d_i is the local
+    product alone and only the text half crosses."""
+    dev, E = L_i.device, f.i_n.shape[1]
+    nloc, M = L_i.shape
+    if L_t is None:
+        d_i = torch.empty(nloc, E, device=dev, dtype=torch.float32)
+        ops.gemm_f32(L_i, f.t_all.t(), d_i, alpha_log_dev=ls)                    # d I_loc = s dL_i T_all
+        cross = cross_t = torch.empty(M, E, device=dev, dtype=torch.float32)
+    else:
+        cross, cross_i, cross_t = _pair(L_t.shape[1], M, E, dev, f.packed)
+        ops.gemm_f32(L_t.t(), f.t_n.t(), cross_i, alpha_log_dev=ls)              # -> d I_all = s dL_t^T T_loc
+    ops.gemm_f32(L_i.t(), f.i_n.t(), cross_t, alpha_log_dev=ls)                  # -> d T_all = s dL_i^T I_loc
+    if r.dp:
+        d = torch.empty(cross.shape[0] // r.world, cross.shape[1], device=dev, dtype=torch.float32)
+        dist.reduce_scatter_tensor(d, cross, group=r.group)
+    else:
+        d = cross
+    if L_t is None:
+        return d_i, d
+    d_i, d_t = (d[:, :E], d[:, E:]) if f.packed else (cross_i, cross_t)
+    ops.gemm_f32(L_i, f.t_all.t(), d_i, alpha_log_dev=ls, beta=1.0)              # += s dL_i T_all
+    ops.gemm_f32(L_t, f.i_all.t(), d_t, alpha_log_dev=ls, beta=1.0)              # += s dL_t I_all
+    return d_i, d_t
+
+
+def _backward_tail(saved, dloss):
+    """The backward of both Functions from saved = (d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot): through the two normalisations,
+    and this rank's logit_scale gradient, all times the upstream gradient g -> (g, (dfi, dft, dscale))."""
+    d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot = saved
+    dev = i_n.device
+    g = _scalar(dloss)
+    dfi = torch.empty(i_n.shape, device=dev, dtype=torch.float32)
+    dft = torch.empty(t_n.shape, device=dev, dtype=torch.float32)
+    ops.l2norm_bwd(d_i, i_n, inv_i, dfi, mul_dev=g)
+    ops.l2norm_bwd(d_t, t_n, inv_t, dft, mul_dev=g)
+    dscale = torch.empty(1, device=dev, dtype=torch.float32)
+    ops.reduce_dot(rowdot, None, dscale, mul_dev=g)
+    return g, (dfi, dft, dscale.reshape(()))
 
 
 class _Contrastive(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, fi, ft, logit_scale, group):
-        rank, world = _world(group)
-        dp = _collectives(group)              # world > 1, or a forced one-rank RCCL pass (clip.parallel.collectives_active)
-        dev = fi.device
-        fi, ft = fi.contiguous().float(), ft.contiguous().float()
-        ls = logit_scale.detach().float().reshape(1).contiguous()
-        nloc, E = fi.shape
-        N = nloc * world
-        need_grad = any(ctx.needs_input_grad[:3])
-
-        packed = torch.empty(nloc, 2 * E, device=dev, dtype=torch.float32)      # [ In | Tn ]
-        i_n, t_n = packed[:, :E], packed[:, E:]
-        inv_i = torch.empty(nloc, device=dev, dtype=torch.float32)
-        inv_t = torch.empty(nloc, device=dev, dtype=torch.float32)
-        ops.l2norm_fwd(fi, i_n, inv_i)
-        ops.l2norm_fwd(ft, t_n, inv_t)
-        if dp:
-            gathered = torch.empty(N, 2 * E, device=dev, dtype=torch.float32)
-            dist.all_gather_into_tensor(gathered, packed, group=group)
-        else:
-            gathered = packed
-        i_all, t_all = gathered[:, :E], gathered[:, E:]
-
-        L_i = torch.empty(nloc, N, device=dev, dtype=torch.float32)
-        L_t = torch.empty(nloc, N, device=dev, dtype=torch.float32)
-        ops.gemm_f32(i_n, t_all, L_i, alpha_log_dev=ls)
-        ops.gemm_f32(t_n, i_all, L_t, alpha_log_dev=ls)
-        labels = (torch.arange(nloc, device=dev) + rank * nloc).to(torch.int32)
-        loss_rows = torch.empty(2, nloc, device=dev, dtype=torch.float32)
-        rowdot = torch.empty(2, nloc, device=dev, dtype=torch.float32) if need_grad else None
-        pred = torch.empty(nloc, device=dev, dtype=torch.int32)
-        gs = 1.0 / (2.0 * N)
-        # gradients of the GLOBAL mean loss overwrite the logits in place (nothing else needs them)
-        ops.xent_rows(L_i, labels, loss_row=loss_rows[0], pred=pred, dlogits=L_i if need_grad else None, grad_scale=gs,
-                      rowdot=rowdot[0] if need_grad else None)
-        ops.xent_rows(L_t, labels, loss_row=loss_rows[1], dlogits=L_t if need_grad else None, grad_scale=gs,
-                      rowdot=rowdot[1] if need_grad else None)
-        out = torch.empty(2, device=dev, dtype=torch.float32)                    # [loss, #correct]
-        ops.reduce_dot(loss_rows.view(-1), None, out[0:1], alpha=gs)
-        hit = (pred == labels).to(torch.float32)                                 # integer compare (bookkeeping)
-        ops.reduce_dot(hit, None, out[1:2])
-        if dp:
-            dist.all_reduce(out, group=group)
-        if need_grad:
-            # d/d(normalised features): local rows + the other ranks' rows that used our features
-            cross = torch.empty(N, 2 * E, device=dev, dtype=torch.float32)
-            ops.gemm_f32(L_t.t(), t_n.t(), cross[:, :E], alpha_log_dev=ls)       # -> d I_all = s dL_t^T T_loc
-            ops.gemm_f32(L_i.t(), i_n.t(), cross[:, E:], alpha_log_dev=ls)       # -> d T_all = s dL_i^T I_loc
-            if dp:
-                d = torch.empty(nloc, 2 * E, device=dev, dtype=torch.float32)
-                dist.reduce_scatter_tensor(d, cross, group=group)
-            else:
-                d = cross
-            ops.gemm_f32(L_i, t_all.t(), d[:, :E], alpha_log_dev=ls, beta=1.0)   # += s dL_i T_all
-            ops.gemm_f32(L_t, i_all.t(), d[:, E:], alpha_log_dev=ls, beta=1.0)   # += s dL_t I_all
-            ctx.saved = (d, packed, inv_i, inv_t, rowdot)
-        ctx.mark_non_differentiable(out)
-        loss = out[0].clone()
-        ctx.stats = out
-        return loss, out
-
-    @staticmethod
-    def backward(ctx, dloss, _dout):
-        d, packed, inv_i, inv_t, rowdot = ctx.saved
-        E = packed.shape[1] // 2
-        g = dloss.detach().float().reshape(1).contiguous()
-        dfi = torch.empty(packed.shape[0], E, device=packed.device, dtype=torch.float32)
-        dft = torch.empty_like(dfi)
-        ops.l2norm_bwd(d[:, :E], packed[:, :E], inv_i, dfi, mul_dev=g)
-        ops.l2norm_bwd(d[:, E:], packed[:, E:], inv_t, dft, mul_dev=g)
-        dscale = torch.empty(1, device=packed.device, dtype=torch.float32)
-        ops.reduce_dot(rowdot.view(-1), None, dscale, mul_dev=g)
-        ctx.saved = None
-        return dfi, dft, dscale.reshape(()), None
-
-
-class _ContrastiveClasses(torch.autograd.Function):
-    """The class-aware form: row i of the image side carries class a_i, row j of the text side class b_j, and the positives of
-    a row are the columns of its class (uniform soft targets, both directions; DESIGN.md 'Class-aware contrastive loss').
-    Single process: I [N,E] against T [M,E], M free.  Data parallel: the square form (text j carries a_j), with the choreography
-    of _Contrastive plus ONE all-gather of the int32 class vector."""
+    """The softmax loss in both forms.  Class-aware (a_loc, b_loc given): row i of the image side carries class a_i, row j of
+    the text side class b_j, and the positives of a row are the columns of its class (uniform soft targets, both directions;
+    DESIGN.md 'Class-aware contrastive loss').  Single process: I [N,E] against T [M,E], M free.  Data parallel: the square
+    form (text j carries a_j), with ONE more all-gather, of the int32 class vector.  Pairwise (no class vectors): the positive
+    of global row g is column g, on ops.xent_rows, always square and always packed."""
 
     @staticmethod
     def forward(ctx, fi, ft, logit_scale, group, a_loc, b_loc):
-        dp = _collectives(group)
-        world = _world(group)[1] if dp else 1
+        r = _ranks(group)
         dev = fi.device
         fi, ft = fi.contiguous().float(), ft.contiguous().float()
-        ls = logit_scale.detach().float().reshape(1).contiguous()
+        ls = _scalar(logit_scale)
+        pairwise = a_loc is None
         nloc, E = fi.shape
-        mloc = ft.shape[0]
-        N, M = nloc * world, mloc * world
+        mloc = nloc if pairwise else ft.shape[0]
+        N, M = nloc * r.world, mloc * r.world
         need_grad = any(ctx.needs_input_grad[:3])
 
-        inv_i = torch.empty(nloc, device=dev, dtype=torch.float32)
-        inv_t = torch.empty(mloc, device=dev, dtype=torch.float32)
-        if dp:                                                                   # square: one packed buffer, as _Contrastive
-            packed = torch.empty(nloc, 2 * E, device=dev, dtype=torch.float32)  # [ In | Tn ]
-            i_n, t_n = packed[:, :E], packed[:, E:]
-        else:
-            i_n = torch.empty(nloc, E, device=dev, dtype=torch.float32)
-            t_n = torch.empty(mloc, E, device=dev, dtype=torch.float32)
-        ops.l2norm_fwd(fi, i_n, inv_i)
-        ops.l2norm_fwd(ft, t_n, inv_t)
-        if dp:
-            gathered = torch.empty(N, 2 * E, device=dev, dtype=torch.float32)
-            dist.all_gather_into_tensor(gathered, packed, group=group)
-            i_all, t_all = gathered[:, :E], gathered[:, E:]
+        f = _normalise_gather(fi, ft, mloc, r, packed=pairwise or r.dp, one_sided=False)
+        if pairwise:
+            labels = (torch.arange(nloc, device=dev) + r.rank * nloc).to(torch.int32)
+        elif r.dp:
             a_all = torch.empty(N, device=dev, dtype=torch.int32)
             dist.all_gather_into_tensor(a_all, a_loc, group=group)
             b_all = a_all
         else:
-            i_all, t_all, a_all, b_all = i_n, t_n, a_loc, b_loc
+            a_all, b_all = a_loc, b_loc
 
         L_i = torch.empty(nloc, M, device=dev, dtype=torch.float32)
         L_t = torch.empty(mloc, N, device=dev, dtype=torch.float32)
-        ops.gemm_f32(i_n, t_all, L_i, alpha_log_dev=ls)
-        ops.gemm_f32(t_n, i_all, L_t, alpha_log_dev=ls)
+        ops.gemm_f32(f.i_n, f.t_all, L_i, alpha_log_dev=ls)
+        ops.gemm_f32(f.t_n, f.i_all, L_t, alpha_log_dev=ls)
         loss_rows = torch.empty(nloc + mloc, device=dev, dtype=torch.float32)
         rowdot = torch.empty(nloc + mloc, device=dev, dtype=torch.float32) if need_grad else None
-        hit = torch.empty(nloc, device=dev, dtype=torch.float32)
         gs_i, gs_t = 1.0 / (2.0 * N), 1.0 / (2.0 * M)                            # fixed GLOBAL denominators: host constants
-        # gradients of the GLOBAL mean loss overwrite the logits in place (nothing else needs them)
-        ops.xent_rows_classes(L_i, a_loc, b_all, loss_row=loss_rows[:nloc], hit=hit, dlogits=L_i if need_grad else None,
-                              grad_scale=gs_i, rowdot=rowdot[:nloc] if need_grad else None)
-        ops.xent_rows_classes(L_t, b_loc, a_all, loss_row=loss_rows[nloc:], dlogits=L_t if need_grad else None,
-                              grad_scale=gs_t, rowdot=rowdot[nloc:] if need_grad else None)
-        out = torch.empty(2, device=dev, dtype=torch.float32)                    # [loss, #correct by class]
-        ops.reduce_dot(loss_rows[:nloc], None, out[0:1], alpha=gs_i)
-        ops.reduce_dot(loss_rows[nloc:], None, out[0:1], alpha=gs_t, accumulate=True)
+        out = torch.empty(2, device=dev, dtype=torch.float32)                    # [loss, #correct (by class)]
+
+        def side(L, rows, gs):
+            # gradients of the GLOBAL mean loss overwrite the logits in place (nothing else needs them)
+            return dict(loss_row=loss_rows[rows], dlogits=L if need_grad else None, grad_scale=gs,
+                        rowdot=rowdot[rows] if need_grad else None)
+
+        image_rows, text_rows = slice(0, nloc), slice(nloc, None)
+        if pairwise:
+            pred = torch.empty(nloc, device=dev, dtype=torch.int32)
+            ops.xent_rows(L_i, labels, pred=pred, **side(L_i, image_rows, gs_i))
+            ops.xent_rows(L_t, labels, **side(L_t, text_rows, gs_t))
+            ops.reduce_dot(loss_rows, None, out[0:1], alpha=gs_i)                # N == M: both halves in one launch
+            hit = (pred == labels).to(torch.float32)                             # integer compare (bookkeeping)
+        else:
+            hit = torch.empty(nloc, device=dev, dtype=torch.float32)
+            ops.xent_rows_classes(L_i, a_loc, b_all, hit=hit, **side(L_i, image_rows, gs_i))
+            ops.xent_rows_classes(L_t, b_loc, a_all, **side(L_t, text_rows, gs_t))
+            ops.reduce_dot(loss_rows[image_rows], None, out[0:1], alpha=gs_i)
+            ops.reduce_dot(loss_rows[text_rows], None, out[0:1], alpha=gs_t, accumulate=True)
         ops.reduce_dot(hit, None, out[1:2])
-        if dp:
+        if r.dp:
             dist.all_reduce(out, group=group)
         if need_grad:
-            # d/d(normalised features): local rows + the other ranks' rows that used our features
-            if dp:
-                cross = torch.empty(N, 2 * E, device=dev, dtype=torch.float32)
-                cross_i, cross_t = cross[:, :E], cross[:, E:]
-            else:
-                cross_i = torch.empty(N, E, device=dev, dtype=torch.float32)
-                cross_t = torch.empty(M, E, device=dev, dtype=torch.float32)
-            ops.gemm_f32(L_t.t(), t_n.t(), cross_i, alpha_log_dev=ls)            # -> d I_all = s dL_t^T T_loc
-            ops.gemm_f32(L_i.t(), i_n.t(), cross_t, alpha_log_dev=ls)            # -> d T_all = s dL_i^T I_loc
-            if dp:
-                d = torch.empty(nloc, 2 * E, device=dev, dtype=torch.float32)
-                dist.reduce_scatter_tensor(d, cross, group=group)
-                d_i, d_t = d[:, :E], d[:, E:]
-            else:
-                d_i, d_t = cross_i, cross_t
-            ops.gemm_f32(L_i, t_all.t(), d_i, alpha_log_dev=ls, beta=1.0)        # += s dL_i T_all
-            ops.gemm_f32(L_t, i_all.t(), d_t, alpha_log_dev=ls, beta=1.0)        # += s dL_t I_all
-            ctx.saved = (d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot)
+            ctx.saved = (*_feature_grads(L_i, L_t, f, ls, r), f.i_n, f.t_n, f.inv_i, f.inv_t, rowdot)
         ctx.mark_non_differentiable(out)
-        loss = out[0].clone()
-        ctx.stats = out
-        return loss, out
+        return out[0].clone(), out
 
     @staticmethod
     def backward(ctx, dloss, _dout):
-        d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot = ctx.saved
-        g = dloss.detach().float().reshape(1).contiguous()
-        dfi = torch.empty(i_n.shape, device=i_n.device, dtype=torch.float32)
-        dft = torch.empty(t_n.shape, device=i_n.device, dtype=torch.float32)
-        ops.l2norm_bwd(d_i, i_n, inv_i, dfi, mul_dev=g)
-        ops.l2norm_bwd(d_t, t_n, inv_t, dft, mul_dev=g)
-        dscale = torch.empty(1, device=i_n.device, dtype=torch.float32)
-        ops.reduce_dot(rowdot, None, dscale, mul_dev=g)
+        _, grads = _backward_tail(ctx.saved, dloss)
         ctx.saved = None
-        return dfi, dft, dscale.reshape(()), None, None, None
+        return (*grads, None, None, None)
 
 
 def _as_classes(labels: torch.Tensor, rows: int, device, name: str) -> torch.Tensor:
@@ -221,6 +221,24 @@ def _as_classes(labels: torch.Tensor, rows: int, device, name: str) -> torch.Ten
     if labels.shape != (rows,):
         raise ValueError(f"{name}: expected shape [{rows}] (one class id per feature row), got {tuple(labels.shape)}")
     return labels.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _classes(what: str, image_features, text_features, group, labels, text_labels):
+    """What `labels` / `text_labels` mean to both entry points -> the int32 class vectors (image side [N_loc], text side
+    [M_loc]) on the features' device, or (None, None) for the pairwise form."""
+    if labels is None:
+        if text_labels is not None:
+            raise ValueError("text_labels needs labels (the image side's class ids)")
+        return None, None
+    if text_labels is not None and _collectives(group):
+        raise NotImplementedError(f"{what} with text_labels (rectangular) is single-process only; "
+                                  "under data parallelism pass labels alone (class_ids(tokens, group) gives them)")
+    a = _as_classes(labels, image_features.shape[0], image_features.device, "labels")
+    if text_labels is not None:
+        return a, _as_classes(text_labels, text_features.shape[0], image_features.device, "text_labels")
+    if text_features.shape[0] != image_features.shape[0]:
+        raise ValueError("labels without text_labels is the square form: image and text features need equal row counts")
+    return a, a
 
 
 def contrastive_loss(image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
@@ -236,21 +254,8 @@ def contrastive_loss(image_features: torch.Tensor, text_features: torch.Tensor, 
     text side has its own classes - e.g. the U distinct texts of a batch, each encoded once (`unique_texts`); single process
     only.  A negative id is 'unlabelled': such a row adds no loss and no gradient, such a column is a negative for every row.
     The means divide by the fixed global row counts N and M.  `labels=None` is the pairwise loss (positives on the diagonal)."""
-    if labels is None:
-        if text_labels is not None:
-            raise ValueError("text_labels needs labels (the image side's class ids)")
-        return _Contrastive.apply(image_features, text_features, logit_scale, group)
-    if text_labels is not None and _collectives(group):
-        raise NotImplementedError("class-aware contrastive loss with text_labels (rectangular) is single-process only; "
-                                  "under data parallelism pass labels alone (class_ids(tokens, group) gives them)")
-    a = _as_classes(labels, image_features.shape[0], image_features.device, "labels")
-    if text_labels is None:
-        if text_features.shape[0] != image_features.shape[0]:
-            raise ValueError("labels without text_labels is the square form: image and text features need equal row counts")
-        b = a
-    else:
-        b = _as_classes(text_labels, text_features.shape[0], image_features.device, "text_labels")
-    return _ContrastiveClasses.apply(image_features, text_features, logit_scale, group, a, b)
+    a, b = _classes("class-aware contrastive loss", image_features, text_features, group, labels, text_labels)
+    return _Contrastive.apply(image_features, text_features, logit_scale, group, a, b)
 
 
 def class_ids(tokens: torch.Tensor, group: Optional["dist.ProcessGroup"] = None) -> torch.Tensor:
@@ -278,44 +283,32 @@ def unique_texts(tokens: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 class _Sigmoid(torch.autograd.Function):
     """The pairwise sigmoid (SigLIP) loss: every cell (i, j) of L = s I T^T is a binary problem of its own, u = L + b against
     y = +1 where text j carries image i's class and -1 elsewhere, summed and divided by the GLOBAL image count N (DESIGN.md
-    'Sigmoid loss').  A plain sum over cells, and every cell lies in exactly one rank's row block: ONE logits GEMM and ONE row
-    kernel launch (ops.sigmoid_rows), and under data parallelism only the normalised TEXT features travel."""
+    'Sigmoid loss').  A plain sum over cells, and every cell lies in exactly one rank's row block: the one-sided half of
+    _Contrastive's scheme - ONE logits GEMM and ONE row kernel launch (ops.sigmoid_rows), and under data parallelism only the
+    normalised TEXT features travel."""
 
     @staticmethod
     def forward(ctx, fi, ft, logit_scale, logit_bias, group, a_loc, b_loc):
-        dp = _collectives(group)
-        rank, world = _world(group) if dp else (0, 1)
+        r = _ranks(group)
         dev = fi.device
         fi, ft = fi.contiguous().float(), ft.contiguous().float()
-        ls = logit_scale.detach().float().reshape(1).contiguous()
-        lb = logit_bias.detach().float().reshape(1).contiguous()
-        nloc, E = fi.shape
-        mloc = ft.shape[0]
-        N, M = nloc * world, mloc * world
+        ls, lb = _scalar(logit_scale), _scalar(logit_bias)
+        nloc, mloc = fi.shape[0], ft.shape[0]
+        N, M = nloc * r.world, mloc * r.world
         need_grad = any(ctx.needs_input_grad[:4])
 
-        i_n = torch.empty(nloc, E, device=dev, dtype=torch.float32)
-        t_n = torch.empty(mloc, E, device=dev, dtype=torch.float32)
-        inv_i = torch.empty(nloc, device=dev, dtype=torch.float32)
-        inv_t = torch.empty(mloc, device=dev, dtype=torch.float32)
-        ops.l2norm_fwd(fi, i_n, inv_i)
-        ops.l2norm_fwd(ft, t_n, inv_t)
-        if dp:                                                                   # square; nothing reads I_all
-            t_all = torch.empty(M, E, device=dev, dtype=torch.float32)
-            dist.all_gather_into_tensor(t_all, t_n, group=group)
-        else:
-            t_all = t_n
+        f = _normalise_gather(fi, ft, mloc, r, packed=False, one_sided=True)     # square under data parallelism
         if a_loc is None:                                                        # pairwise: the positive of global row g is column g
-            a_loc = (torch.arange(nloc, device=dev) + rank * nloc).to(torch.int32)
+            a_loc = (torch.arange(nloc, device=dev) + r.rank * nloc).to(torch.int32)
             b_all = torch.arange(M, device=dev).to(torch.int32)
-        elif dp:
+        elif r.dp:
             b_all = torch.empty(M, device=dev, dtype=torch.int32)
             dist.all_gather_into_tensor(b_all, a_loc, group=group)
         else:
             b_all = b_loc
 
         L = torch.empty(nloc, M, device=dev, dtype=torch.float32)
-        ops.gemm_f32(i_n, t_all, L, alpha_log_dev=ls)
+        ops.gemm_f32(f.i_n, f.t_all, L, alpha_log_dev=ls)
         loss_rows = torch.empty(nloc, device=dev, dtype=torch.float32)
         hit = torch.empty(nloc, device=dev, dtype=torch.float32)
         rowdot = torch.empty(nloc, device=dev, dtype=torch.float32) if need_grad else None
@@ -329,38 +322,21 @@ class _Sigmoid(torch.autograd.Function):
         ops.reduce_dot(hit, None, out[1:2])
         if need_grad:
             ops.reduce_dot(rowsum, None, out[2:3])
-        if dp:
+        if r.dp:
             dist.all_reduce(out, group=group)                                    # the bias gradient rides with the statistics
         if need_grad:
-            d_i = torch.empty(nloc, E, device=dev, dtype=torch.float32)
-            cross_t = torch.empty(M, E, device=dev, dtype=torch.float32)
-            ops.gemm_f32(L, t_all.t(), d_i, alpha_log_dev=ls)                    # d I_loc = s dL T_all
-            ops.gemm_f32(L.t(), i_n.t(), cross_t, alpha_log_dev=ls)              # d T_all = s dL^T I_loc
-            if dp:
-                d_t = torch.empty(mloc, E, device=dev, dtype=torch.float32)
-                dist.reduce_scatter_tensor(d_t, cross_t, group=group)
-            else:
-                d_t = cross_t
-            ctx.saved = (d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot, out)
+            ctx.saved = (*_feature_grads(L, None, f, ls, r), f.i_n, f.t_n, f.inv_i, f.inv_t, rowdot, out)
         stats = out[:2]
         ctx.mark_non_differentiable(stats)
         return out[0].clone(), stats
 
     @staticmethod
     def backward(ctx, dloss, _dstats):
-        d_i, d_t, i_n, t_n, inv_i, inv_t, rowdot, out = ctx.saved
-        dev = i_n.device
-        g = dloss.detach().float().reshape(1).contiguous()
-        dfi = torch.empty(i_n.shape, device=dev, dtype=torch.float32)
-        dft = torch.empty(t_n.shape, device=dev, dtype=torch.float32)
-        ops.l2norm_bwd(d_i, i_n, inv_i, dfi, mul_dev=g)
-        ops.l2norm_bwd(d_t, t_n, inv_t, dft, mul_dev=g)
-        dscale = torch.empty(1, device=dev, dtype=torch.float32)
-        dbias = torch.empty(1, device=dev, dtype=torch.float32)
-        ops.reduce_dot(rowdot, None, dscale, mul_dev=g)                          # this rank's part
-        ops.reduce_dot(out[2:3], None, dbias, mul_dev=g)                         # already GLOBAL (all-reduced in forward)
+        g, grads = _backward_tail(ctx.saved[:7], dloss)                          # dscale: this rank's part
+        dbias = torch.empty(1, device=g.device, dtype=torch.float32)
+        ops.reduce_dot(ctx.saved[7][2:3], None, dbias, mul_dev=g)                # already GLOBAL (all-reduced in forward)
         ctx.saved = None
-        return dfi, dft, dscale.reshape(()), dbias.reshape(()), None, None, None
+        return (*grads, dbias.reshape(()), None, None, None)
 
 
 def sigmoid_loss(image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
@@ -384,24 +360,9 @@ def sigmoid_loss(image_features: torch.Tensor, text_features: torch.Tensor, logi
     (clip.parallel.allreduce_gradients).  logit_bias does not live in the model's arena: this rank's sum of dL rides in the one
     all-reduce that carries the statistics, backward returns the GLOBAL bias gradient on every rank, and it must NOT be summed
     again."""
-    n = image_features.shape[0]
-    if labels is None:
-        if text_labels is not None:
-            raise ValueError("text_labels needs labels (the image side's class ids)")
-        if text_features.shape[0] != n:
-            raise ValueError("the pairwise form needs equal image and text row counts")
-        a = b = None
-    else:
-        if text_labels is not None and _collectives(group):
-            raise NotImplementedError("sigmoid loss with text_labels (rectangular) is single-process only; under data "
-                                      "parallelism pass labels alone (class_ids(tokens, group) gives them)")
-        a = _as_classes(labels, n, image_features.device, "labels")
-        if text_labels is None:
-            if text_features.shape[0] != n:
-                raise ValueError("labels without text_labels is the square form: image and text features need equal row counts")
-            b = a
-        else:
-            b = _as_classes(text_labels, text_features.shape[0], image_features.device, "text_labels")
+    a, b = _classes("sigmoid loss", image_features, text_features, group, labels, text_labels)
+    if a is None and text_features.shape[0] != image_features.shape[0]:
+        raise ValueError("the pairwise form needs equal image and text row counts")
     return _Sigmoid.apply(image_features, text_features, logit_scale, logit_bias, group, a, b)
 
 

@@ -2,13 +2,11 @@
 
   * the float64 reference - the definition of DESIGN.md 'Class-aware contrastive loss' as soft-target cross-entropy in plain
     torch, gradients by autograd.  It never touches the code under test.
-  * `ops_shim`: tests/cpu_ops_shim.py plus a torch restatement of the contract of cclip_xent_rows_classes
-    (include/cclip_hip.h), so that clip/loss.py's class-aware choreography runs on CPU tensors and over gloo."""
-import types
-
+  * `ops_shim`: tests/cpu_ops_shim.py itself (it restates cclip_xent_rows_classes too), so that clip/loss.py's class-aware
+    choreography runs on CPU tensors and over gloo."""
 import torch
 
-import cpu_ops_shim
+import cpu_ops_shim as ops_shim  # noqa: F401
 
 LOSS_TOL, GRAD_TOL = 1e-5, 1e-4          # the fp32 head's own bounds (tests/test_clip_parity_gpu.py, test_head_is_fp32_exact)
 
@@ -53,33 +51,3 @@ def ref_loss_and_grads(fi, ft, ls, a, b, upstream=1.0):
     loss, correct = ref_loss(f2, t2, l2, a.to(f2.device), b.to(f2.device))
     (loss * upstream).backward()
     return loss.detach(), correct, f2.grad, t2.grad, l2.grad
-
-
-# ---- CPU stand-in for the launcher -----------------------------------------------------------------------------------------
-def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pred=None, hit=None, dlogits=None,
-                      grad_scale=1.0, rowdot=None):
-    assert logits.dtype == torch.float32 and row_class_i32.dtype == torch.int32 and col_class_i32.dtype == torch.int32
-    assert row_class_i32.shape == (logits.shape[0],) and col_class_i32.shape == (logits.shape[1],)
-    a, b = row_class_i32.long(), col_class_i32.long()
-    match = (a[:, None] == b[None, :]) & (a[:, None] >= 0)
-    cnt = match.sum(1)
-    has = cnt > 0
-    w = match.to(logits.dtype) / cnt.clamp(min=1)[:, None]
-    arg = logits.argmax(1)
-    if loss_row is not None:
-        lse = torch.logsumexp(logits, dim=1)
-        loss_row.copy_(torch.where(has, lse - (w * logits).sum(1), torch.zeros_like(lse)))
-    if pred is not None:
-        pred.copy_(arg.to(torch.int32))
-    if hit is not None:
-        hit.copy_(((a >= 0) & (b[arg] == a)).to(torch.float32))
-    if dlogits is not None:
-        d = (torch.softmax(logits, 1) - w) * grad_scale
-        d[~has] = 0
-        if rowdot is not None:
-            rowdot.copy_((d * logits).sum(1))
-        dlogits.copy_(d)
-
-
-ops_shim = types.SimpleNamespace(**{k: v for k, v in vars(cpu_ops_shim).items() if callable(v) and not k.startswith("_")},
-                                 xent_rows_classes=xent_rows_classes)

@@ -1,6 +1,6 @@
 """TEST-ONLY stand-in for cclip_hip.ops on CPU tensors, so that the multi-process (gloo, world_size 2)
-tests can exercise the data-parallel choreography of clip/loss.py and clip/parallel.py - all-gather layout,
-label offsets, reduce-scatter of the cross terms, gradient buckets - in this GPU-less container.
+tests can exercise the data-parallel choreography of clip/loss.py (pairwise, class-aware and sigmoid) and clip/parallel.py -
+all-gather layout, label offsets, reduce-scatter of the cross terms, gradient buckets - in this GPU-less container.
 Each function restates the contract of the HIP launcher of the same name (include/cclip_hip.h) with plain torch.
 It is never importable from the product package."""
 import torch
@@ -42,6 +42,58 @@ def xent_rows(logits, labels_i32, *, loss_row=None, pred=None, dlogits=None, gra
         if rowdot is not None:
             rowdot.copy_((d * logits).sum(1))
         dlogits.copy_(d.to(dlogits.dtype))
+
+
+def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pred=None, hit=None, dlogits=None,
+                      grad_scale=1.0, rowdot=None):
+    assert logits.dtype == torch.float32 and row_class_i32.dtype == torch.int32 and col_class_i32.dtype == torch.int32
+    assert row_class_i32.shape == (logits.shape[0],) and col_class_i32.shape == (logits.shape[1],)
+    a, b = row_class_i32.long(), col_class_i32.long()
+    match = (a[:, None] == b[None, :]) & (a[:, None] >= 0)
+    cnt = match.sum(1)
+    has = cnt > 0
+    w = match.to(logits.dtype) / cnt.clamp(min=1)[:, None]
+    arg = logits.argmax(1)
+    if loss_row is not None:
+        lse = torch.logsumexp(logits, dim=1)
+        loss_row.copy_(torch.where(has, lse - (w * logits).sum(1), torch.zeros_like(lse)))
+    if pred is not None:
+        pred.copy_(arg.to(torch.int32))
+    if hit is not None:
+        hit.copy_(((a >= 0) & (b[arg] == a)).to(torch.float32))
+    if dlogits is not None:
+        d = (torch.softmax(logits, 1) - w) * grad_scale
+        d[~has] = 0
+        if rowdot is not None:
+            rowdot.copy_((d * logits).sum(1))
+        dlogits.copy_(d)
+
+
+def sigmoid_rows(logits, row_class_i32, col_class_i32, bias, *, loss_row=None, pred=None, hit=None, dlogits=None,
+                 grad_scale=1.0, rowdot=None, rowsum=None):
+    assert logits.dtype == torch.float32 and row_class_i32.dtype == torch.int32 and col_class_i32.dtype == torch.int32
+    assert bias.dtype == torch.float32 and bias.numel() == 1
+    assert row_class_i32.shape == (logits.shape[0],) and col_class_i32.shape == (logits.shape[1],)
+    assert dlogits is not None or (rowdot is None and rowsum is None)
+    a, b = row_class_i32.long(), col_class_i32.long()
+    labelled = a >= 0
+    y = (((a[:, None] == b[None, :]) & labelled[:, None]).to(logits.dtype) * 2 - 1)
+    x = -y * (logits + bias.reshape(()))
+    arg = logits.argmax(1)
+    if loss_row is not None:
+        loss_row.copy_(torch.nn.functional.softplus(x).sum(1) * labelled)
+    if pred is not None:
+        pred.copy_(arg.to(torch.int32))
+    if hit is not None:
+        hit.copy_((labelled & (b[arg] == a)).to(torch.float32))
+    if dlogits is not None:
+        d = -y * torch.sigmoid(x) * grad_scale
+        d[~labelled] = 0
+        if rowdot is not None:
+            rowdot.copy_((d * logits).sum(1))
+        if rowsum is not None:
+            rowsum.copy_(d.sum(1))
+        dlogits.copy_(d)
 
 
 def reduce_dot(a, b, out, *, alpha=1.0, mul_dev=None, accumulate=False):

@@ -2,16 +2,14 @@
 
   * the float64 reference - the definition of DESIGN.md 'Sigmoid loss' in plain torch (softplus of the signed, biased logits),
     gradients by autograd.  It never touches the code under test.
-  * `ops_shim`: tests/cpu_ops_shim.py plus a torch restatement of the contract of cclip_sigmoid_rows (include/cclip_hip.h), so
-    that clip/loss.py's sigmoid choreography runs on CPU tensors and over gloo.
+  * `ops_shim`: tests/cpu_ops_shim.py itself (it restates cclip_sigmoid_rows too), so that clip/loss.py's sigmoid choreography
+    runs on CPU tensors and over gloo.
 
 Bounds: the fp32 head's own (class_loss_helpers).  The loss is a sum over C columns of non-negative terms rather than a
 log-sum, so its 1e-5 is read relatively: |got - ref| <= 1e-5 * max(1, |ref|)."""
-import types
-
 import torch
 
-import cpu_ops_shim
+import cpu_ops_shim as ops_shim  # noqa: F401
 from class_loss_helpers import GRAD_TOL, LOSS_TOL, rel  # noqa: F401
 
 
@@ -61,35 +59,3 @@ def ref_loss_and_grads(fi, ft, ls, lb, a, b, upstream=1.0):
     L.retain_grad()
     (loss * upstream).backward()
     return (loss.detach(), correct, f2.grad, t2.grad, l2.grad, b2.grad, (L.grad * L.detach()).abs().sum(), L.grad.abs().sum())
-
-
-# ---- CPU stand-in for the launcher -----------------------------------------------------------------------------------------
-def sigmoid_rows(logits, row_class_i32, col_class_i32, bias, *, loss_row=None, pred=None, hit=None, dlogits=None,
-                 grad_scale=1.0, rowdot=None, rowsum=None):
-    assert logits.dtype == torch.float32 and row_class_i32.dtype == torch.int32 and col_class_i32.dtype == torch.int32
-    assert bias.dtype == torch.float32 and bias.numel() == 1
-    assert row_class_i32.shape == (logits.shape[0],) and col_class_i32.shape == (logits.shape[1],)
-    assert dlogits is not None or (rowdot is None and rowsum is None)
-    a, b = row_class_i32.long(), col_class_i32.long()
-    labelled = a >= 0
-    y = (((a[:, None] == b[None, :]) & labelled[:, None]).to(logits.dtype) * 2 - 1)
-    x = -y * (logits + bias.reshape(()))
-    arg = logits.argmax(1)
-    if loss_row is not None:
-        loss_row.copy_(torch.nn.functional.softplus(x).sum(1) * labelled)
-    if pred is not None:
-        pred.copy_(arg.to(torch.int32))
-    if hit is not None:
-        hit.copy_((labelled & (b[arg] == a)).to(torch.float32))
-    if dlogits is not None:
-        d = -y * torch.sigmoid(x) * grad_scale
-        d[~labelled] = 0
-        if rowdot is not None:
-            rowdot.copy_((d * logits).sum(1))
-        if rowsum is not None:
-            rowsum.copy_(d.sum(1))
-        dlogits.copy_(d)
-
-
-ops_shim = types.SimpleNamespace(**{k: v for k, v in vars(cpu_ops_shim).items() if callable(v) and not k.startswith("_")},
-                                 sigmoid_rows=sigmoid_rows)
