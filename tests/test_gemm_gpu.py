@@ -1,7 +1,12 @@
 """GPU parity of the bf16 MFMA GEMM (cclip_gemm_bf16) against a plain torch fp32 matmul of the
 same bf16-rounded operands.  Tolerance: fp32 accumulation of exact bf16 products differs from
 torch's only by summation order -> 2e-3 relative to the row's |a|.|b| bound is generous; outputs
-rounded to bf16 get one extra 2^-8 relative rounding."""
+rounded to bf16 get one extra 2^-8 relative rounding.
+
+The tolerances here are fractions of the tensor-wide maximum: they show that a path launches and is roughly right, not that every
+element is.  Per-element float64 coverage lives in tests/test_kernels_f16_gpu.py (the tile configurations) and in
+tests/test_gemm_paths_f64_gpu.py (the skinny path, configuration 4, the folded-LayerNorm forms with rowstats_combine, and the fast
+epilogue forms of configurations 8 / 10 in both dtypes)."""
 import pytest
 import torch
 

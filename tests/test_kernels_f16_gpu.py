@@ -26,11 +26,12 @@ import math
 import pytest
 import torch
 
+from gemm_refs_f64 import (C_ACC, FLOOR, SENT, U, WORST, _acc_bound, _act64, _assert_sensitive, _mats, _worst_report, canvas,  # noqa: F401
+                           check_canvas, rnd, within)
+
 pytestmark = pytest.mark.gpu
 
 DTS = [torch.float16, torch.bfloat16]
-C_ACC = 2.0
-SENT = -7.25          # exact in bf16, fp16 and fp32
 
 
 def ops():
@@ -42,92 +43,13 @@ def G(seed):
     return torch.Generator(device="cuda").manual_seed(seed)
 
 
-def U(dt):
-    return 2.0 ** -11 if dt == torch.float16 else 2.0 ** -8
-
-
-def FLOOR(dt):
-    return 2.0 ** -24 if dt == torch.float16 else 0.0
-
-
-def rnd(shape, dt, g, scale=1.0):
-    return (torch.randn(shape, device="cuda", generator=g) * scale).to(dt)
-
-
-def canvas(rows, cols, dt, rows_pad=3, cols_pad=8):
-    """(buffer, logical view): NaN inside [rows, cols], SENT in the padding rows / columns; row stride = cols + cols_pad rounded to 8"""
-    ld = (cols + cols_pad + 7) // 8 * 8
-    buf = torch.full((rows + rows_pad, ld), SENT, device="cuda", dtype=dt)
-    buf[:rows, :cols] = float("nan")
-    return buf, buf[:rows, :cols]
-
-
-def check_canvas(name, buf, rows, cols):
-    pad = torch.ones_like(buf, dtype=torch.bool)
-    pad[:rows, :cols] = False
-    assert bool((buf[pad] == SENT).all()), f"{name}: a write landed outside the logical output"
-
-
-WORST = {}            # (check family, dtype) -> largest err / bound seen; printed at the end of the module (pytest -s)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _worst_report():
-    yield
-    for (fam, dt), r in sorted(WORST.items()):
-        print(f"worst err/bound  {fam:<24} {dt:<9} {r:.3g}")
-
-
-def within(name, got, ref, bound, dt=None):
-    got64 = got.double()
-    fin = torch.isfinite(got64)
-    assert bool(fin.all()), f"{name}: {int((~fin).sum())} non-finite outputs, first {(~fin).nonzero()[:4].tolist()}"
-    err = (got64 - ref).abs()
-    bad = ~(err <= bound)
-    if bool(bad.any()):
-        idx = bad.nonzero()[:6].tolist()
-        t = tuple(idx[0])
-        pytest.fail(f"{name}: {int(bad.sum())}/{bad.numel()} outside the bound; first {idx}; got {got64[t].item():.6g} ref {ref[t].item():.6g} "
-                    f"bound {bound[t].item():.3g}; worst err/bound {(err / bound.clamp_min(1e-300)).max().item():.3g}")
-    worst = (err / bound.clamp_min(1e-300)).max().item()
-    key = (name.split(" ")[0] + (" f32" if got.dtype == torch.float32 else " 16-bit"), str(dt or got.dtype).replace("torch.", ""))
-    WORST[key] = max(WORST.get(key, 0.0), worst)
-    return worst
+# the GEMM helpers (U, FLOOR, rnd, canvas, check_canvas, within / WORST, _mats, _acc_bound, _assert_sensitive, _act64) live in
+# tests/gemm_refs_f64.py, shared with tests/test_gemm_paths_f64_gpu.py
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # GEMM
 # ---------------------------------------------------------------------------------------------------------------------------
-def _mats(A, B, akc, bkc):
-    """A [M,K], B [N,K] in fp64 from the operands as stored"""
-    Am = A.double() if akc else A.double().t()
-    Bm = B.double() if bkc else B.double().t()
-    return Am, Bm
-
-
-def _acc_bound(Am, Bm, scale=1.0):
-    K = Am.shape[1]
-    return C_ACC * 2.0 ** -24 * math.sqrt(K) * scale * (Am.abs() @ Bm.abs().t())
-
-
-def _assert_sensitive(got, ref, bound, Am, Bm, alpha=1.0, slope=None):
-    """The bound must reject a reference with the LAST 64-deep K-tile's contribution removed from one 16x16 output sub-tile
-    (the middle one of the logical output): an error the size of one MFMA step in one tile is visible."""
-    M, N, K = Am.shape[0], Bm.shape[0], Am.shape[1]
-    k0 = (K - 1) // 64 * 64
-    m0, n0 = (M // 2) // 16 * 16, (N // 2) // 16 * 16
-    m1, n1 = min(m0 + 16, M), min(n0 + 16, N)
-    part = alpha * (Am[m0:m1, k0:] @ Bm[n0:n1, k0:].t())
-    if slope is not None:
-        part = part * slope[m0:m1, n0:n1]
-    wrong = ref.clone()
-    wrong[m0:m1, n0:n1] -= part
-    err = (got.double() - wrong).abs()
-    assert bool((err[m0:m1, n0:n1] > bound[m0:m1, n0:n1]).any()), "the bound cannot see one missing K-tile in one 16x16 sub-tile"
-    full = ref - alpha * (Am[:, k0:] @ Bm[:, k0:].t()) * (1.0 if slope is None else slope)
-    assert bool(((got.double() - full).abs() > bound).any()), "the bound cannot see one missing K-tile"
-
-
 # (cfg, layouts it accepts)
 CFG_LAYOUTS = {1: [(1, 1), (1, 0), (0, 0)], 2: [(1, 1), (1, 0), (0, 0)], 3: [(1, 1), (1, 0), (0, 0)], 5: [(1, 1), (1, 0), (0, 0)],
                7: [(1, 1)], 8: [(1, 1)], 11: [(0, 0)]}
@@ -163,40 +85,6 @@ def test_gemm_plain_f64(cfg, akc, bkc, M, N, K, dt):
     b16 = bound + U(dt) * ref.abs() + FLOOR(dt)
     within(f"cfg{cfg} {akc}{bkc} {M}x{N}x{K} 16-bit", out16, ref, b16)
     _assert_sensitive(out16, ref, b16, Am, Bm)
-
-
-def _act64(v, act, aux):
-    """fp64 activation and its slope d act / d v (the factor an accumulation error is multiplied by)"""
-    c = math.sqrt(2 / math.pi)
-    if act == 0:
-        return v, torch.ones_like(v)
-    if act == 1:
-        s = torch.sigmoid(1.702 * v)
-        return v * s, (s + 1.702 * v * s * (1 - s)).abs()
-    if act == 2:
-        t = torch.tanh(v)
-        return t, 1 - t * t
-    if act == 3:
-        t = torch.tanh(c * (v + 0.044715 * v ** 3))
-        y = 0.5 * v * (1 + t)
-        d = 0.5 * (1 + t) + 0.5 * v * (1 - t * t) * c * (1 + 3 * 0.044715 * v * v)
-        return y, d.abs()
-    if act == 4:
-        return torch.relu(v), (v > 0).double()
-    a = aux.double()
-    if act == 16:
-        s = torch.sigmoid(1.702 * a)
-        gd = s * (1 + 1.702 * a * (1 - s))
-    elif act == 17:
-        gd = 1 - a * a
-    elif act == 18:
-        t = torch.tanh(c * (a + 0.044715 * a ** 3))
-        gd = 0.5 * (1 + t) + 0.5 * a * (1 - t * t) * c * (1 + 3 * 0.044715 * a * a)
-    elif act == 19:
-        gd = (a > 0).double()
-    else:
-        raise ValueError(act)
-    return v * gd, gd.abs()
 
 
 # the epilogue instantiations (csrc/gemm_bf16_impl.h gemm_launch_cfg; configuration 8: csrc/gemm_bf16_cfg8.hip): anything else is
