@@ -63,7 +63,11 @@ class ParamArena:
 
     def refresh_shadows(self, force: bool = False) -> None:
         """Re-cast fp32 masters -> bf16 shadows (one launch) if any parameter was modified in place since
-        the last cast (optimizer.step / load_state_dict bump the version counters)."""
+        the last cast (optimizer.step / load_state_dict / any in-place op on the parameter bump the version counters).
+        In-place writes through `p.data` (`p.data.mul_()`, `p.data.copy_()`) and raw-pointer writes into `flat` bump no version
+        counter and are therefore NOT seen here: after such a write call `refresh_shadows(force=True)`, which re-casts
+        unconditionally and moves `shadow_gen`, so that every copy derived from the shadows (the transposed shadows, the
+        folded-LayerNorm inference weights) is rebuilt as well."""
         stamp = self._current_stamp()
         if force or stamp != self._stamp:
             ops.cast_f32_to_bf16(self.flat, self.bflat)

@@ -103,7 +103,7 @@ class BlockStack:
         self.fp8_wide = True
         self._fp8_weights = None
         # inference: LayerNorm folded into the projection behind it (forward(), `fold`); the gamma-scaled weight copies and their
-        # column sums are rebuilt when `weights_version` (the arena's parameter stamp) moves
+        # column sums are rebuilt when `weights_version` (the arena's `shadow_gen`: it moves whenever the shadows are rewritten) moves
         self._fold_w = None
         self._fold_version = None
 

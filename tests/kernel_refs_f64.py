@@ -274,18 +274,27 @@ def reduce_dot(a, b=None, alpha=1.0, mul=1.0, out0=0.0, drop_wave=None):
 # AdamW (both forms), fp32 GEMM
 # ---------------------------------------------------------------------------------------------------------------------------
 def adamw(p, g, m, v, *, lr, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0, steps=(1,), correct_bias=True,
-          grad_scale=1.0, mode=0, f32_hyper=True):
+          grad_scale=1.0, mode=0, f32_hyper=True, skip=None):
     """len(steps) updates with the same gradient, step numbers as listed.  mode 0: transformers.AdamW (update, then decoupled
     decay), mode 1: torch.optim.AdamW (decay first, eps added after the bias-corrected sqrt).  f32_hyper: the hyper-parameters
     and the bias corrections are the fp32 values the C entry point receives / forms (float arguments; bc = (float)(1 - b^t)),
     so the reference is fed what the kernel is fed; False keeps them in double (the comparison with torch's own optimiser).
+    A trajectory: `g` a list / tuple of gradients and / or `lr` a list / tuple of learning rates, one per step; `skip` a list /
+    tuple with one entry per step, None or a boolean mask of the elements that are SKIPPED at that step - their p, m, v and the
+    three bounds are carried unchanged (an optimiser that leaves a parameter without a gradient alone).
     Returns (dict p / m / v, dict of bounds), the bounds carried through the steps."""
     r = f32 if f32_hyper else float
-    lr, b1, b2, eps, wd, gsc = r(lr), r(beta1), r(beta2), r(eps), r(weight_decay), r(grad_scale)
-    p, g, m, v = p.double().clone(), g.double(), m.double().clone(), v.double().clone()
+    b1, b2, eps, wd, gsc = r(beta1), r(beta2), r(eps), r(weight_decay), r(grad_scale)
+    n_steps = len(steps)
+    gs = list(g) if isinstance(g, (list, tuple)) else [g] * n_steps
+    lrs = [r(x) for x in lr] if isinstance(lr, (list, tuple)) else [r(lr)] * n_steps
+    skips = [None] * n_steps if skip is None else list(skip)
+    assert len(gs) == n_steps and len(lrs) == n_steps and len(skips) == n_steps, "one gradient / lr / skip mask per step"
+    p, m, v = p.double().clone(), m.double().clone(), v.double().clone()
     dp, dm, dv = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
-    gr = g * gsc
-    for step in steps:
+    for step, g_t, lr, sk in zip(steps, gs, lrs, skips):
+        gr = g_t.double() * gsc
+        held = None if sk is None else tuple(t.clone() for t in (p, m, v, dp, dm, dv))
         bc1 = r(1.0 - b1 ** step) if correct_bias else 1.0
         bc2 = r(1.0 - b2 ** step) if correct_bias else 1.0
         # g * grad_scale (E), the two products and the sum (3E)
@@ -319,6 +328,8 @@ def adamw(p, g, m, v, *, lr, beta1=0.9, beta2=0.999, eps=1e-6, weight_decay=0.0,
             p = p - upd
             dp = dp + d_upd + E32 * p.abs()
         dp = dp + FLT_MIN
+        if held is not None:
+            p, m, v, dp, dm, dv = (torch.where(sk, old, new) for old, new in zip(held, (p, m, v, dp, dm, dv)))
     return dict(p=p, m=m, v=v), dict(p=dp, m=dm, v=dv)
 
 

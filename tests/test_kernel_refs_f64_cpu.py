@@ -226,6 +226,62 @@ def test_adamw_reference_mode0_matches_the_restated_transformers_adamw(wd, corre
     assert bool((bnd["p"] > 0).all())
 
 
+@pytest.mark.parametrize("wd,correct_bias", [(0.0, True), (2.0 ** -7, True), (2.0 ** -7, False)])
+def test_adamw_reference_trajectory_and_skip_mask_match_the_restated_transformers_adamw(wd, correct_bias):
+    """The trajectory form: 4 steps, a gradient and a learning rate per step (the first lr is 0, as under a warm-up schedule), and
+    a skip mask per step, against the oracle handed grad=None for the skipped parameters.  Three parameters in one flat vector:
+    `a` always has a gradient, `b` has none at steps 3 and 4, `c` has none at step 2 and has one again afterwards.  The oracle
+    keeps a step count per parameter (transformers.AdamW), the reference takes the step numbers it is given: with the global
+    numbers 1..4 they agree wherever no counted step was skipped before (a, b; c too without bias correction); c under bias
+    correction agrees when the reference is given c's own count."""
+    from oracle.optim_oracle import HFAdamW
+    g = G(9)
+    n, names = 64, ("a", "b", "c")
+    p0 = {k: torch.randn(n, generator=g, dtype=torch.float64) for k in names}
+    grads = [{k: torch.randn(n, generator=g, dtype=torch.float64) * 10.0 ** (i - 2) for k in names} for i in range(4)]
+    for gs in grads:
+        gs["a"][:4] = 0.0
+    lrs = [0.0, HYP["lr"] / 2, HYP["lr"], HYP["lr"] * 0.75]
+    absent = {"a": (), "b": (3, 4), "c": (2,)}
+    hyp = {k: v for k, v in HYP.items() if k != "lr"}
+    params = {k: v.clone() for k, v in p0.items()}
+    opt = HFAdamW(params, lr=0.0, betas=(HYP["beta1"], HYP["beta2"]), eps=HYP["eps"], weight_decay=wd, correct_bias=correct_bias)
+    after_first = None
+    for i, lr in enumerate(lrs):
+        opt.lr = lr
+        opt.step({k: (None if i + 1 in absent[k] else grads[i][k]) for k in names})
+        if i == 0:
+            after_first = {k: v.clone() for k, v in params.items()}
+    flat = lambda d: torch.cat([d[k] for k in names])                  # noqa: E731
+    skip = [torch.cat([torch.full((n,), i + 1 in absent[k]) for k in names]) for i in range(4)]
+    z = torch.zeros(3 * n, dtype=torch.float64)
+    kw = dict(weight_decay=wd, mode=0, correct_bias=correct_bias, f32_hyper=False, **hyp)
+    ref, bnd = KR.adamw(flat(p0), [flat(gs) for gs in grads], z, z, lr=lrs, steps=(1, 2, 3, 4), skip=skip, **kw)
+    first, _ = KR.adamw(flat(p0), [flat(grads[0])], z, z, lr=lrs[:1], steps=(1,), skip=skip[:1], **kw)
+    assert torch.equal(first["p"], flat(p0)), "lr = 0: the parameter does not move"
+    assert torch.equal(first["p"], flat(after_first)) and bool((first["m"][4:] != 0).all()) and bool((first["v"][4:] != 0).all())
+    for j, k in enumerate(names):
+        sl = slice(j * n, (j + 1) * n)
+        if k == "c" and correct_bias:
+            own, _ = KR.adamw(p0[k], [gs[k] for gs in grads], z[sl], z[sl], lr=lrs, steps=(1, 2, 2, 3), skip=[s[sl] for s in skip], **kw)
+            got = own
+            assert not torch.equal(own["p"], ref["p"][sl]), "the global and the per-parameter step count must differ here"
+        else:
+            got = {nm: ref[nm][sl] for nm in ("p", "m", "v")}
+        same(k + " p", got["p"], params[k])
+        same(k + " m", got["m"], opt.state[k]["exp_avg"])
+        same(k + " v", got["v"], opt.state[k]["exp_avg_sq"])
+    # a skipped element carries everything unchanged, the bounds included
+    two, b2 = KR.adamw(flat(p0), [flat(gs) for gs in grads[:2]], z, z, lr=lrs[:2], steps=(1, 2), skip=skip[:2], **kw)
+    b_sl = slice(n, 2 * n)
+    for nm in ("p", "m", "v"):
+        assert torch.equal(ref[nm][b_sl], two[nm][b_sl]) and torch.equal(bnd[nm][b_sl], b2[nm][b_sl]), nm
+    # the sequence form with one entry repeated is the present form
+    rep, brep = KR.adamw(flat(p0), [flat(grads[1])] * 3, z, z, lr=[HYP["lr"]] * 3, steps=(1, 2, 3), skip=[None] * 3, **kw)
+    old, bold = KR.adamw(flat(p0), flat(grads[1]), z, z, lr=HYP["lr"], steps=(1, 2, 3), **kw)
+    assert all(torch.equal(rep[nm], old[nm]) and torch.equal(brep[nm], bold[nm]) for nm in ("p", "m", "v"))
+
+
 @pytest.mark.parametrize("M,N,K", [(31, 33, 32), (33, 32, 31), (65, 33, 64)])
 def test_gemm_reference_matches_matmul(M, N, K):
     g = G(M + N + K)
