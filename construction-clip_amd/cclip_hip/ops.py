@@ -1204,25 +1204,38 @@ def block_ptr_array(blocks):
     return arr
 
 
-def gpt2_decode_step(blocks_arr, n_layer, x, kcache, vcache, pos, scratch16, *, heads, hidden, act, linear_layout,
-                     lnf_w=None, lnf_b=None, wte16=None, logits=None) -> None:
-    """One KV-cached decode step for x.shape[0] sequences, issued natively (cclip_gpt2_decode_step).
-    kcache / vcache: [n_layer, n_seq_alloc, max_len, width] 16-bit; x: fp32 [n_seq, width] (in place)."""
-    _req(x, torch.float32, "x")
+def decode_step_desc(blocks_arr, n_layer, x, kcache, vcache, pos, scratch16, *, heads, hidden, act, linear_layout,
+                     lnf_w=None, lnf_b=None, wte16=None, logits=None, into: Optional[DecodeDesc] = None) -> DecodeDesc:
+    """The DecodeDesc (a new one, or `into`) of one step for the x.shape[0] sequences of x (fp32 [n_seq, width]), with the checks
+    of the layout the kernels index by: cache rows dense and `width` apart, k and v strided alike, a scratch of
+    n_seq * (5 * width + hidden) cache-dtype elements.  Reads shapes, strides and addresses only: no library, no GPU."""
+    s = DecodeDesc() if into is None else into
     nb, D = x.shape
-    assert x.is_contiguous() and kcache.dim() == 4 and kcache.stride(3) == 1 and kcache.stride(2) == D and kcache.stride() == vcache.stride()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.device == kcache.device
+    assert kcache.dim() == 4 and kcache.stride(3) == 1 and kcache.stride(2) == D and kcache.stride() == vcache.stride()
     assert scratch16.numel() >= nb * (5 * D + hidden) and scratch16.dtype == kcache.dtype
-    d = DecodeDesc()
-    d.n_layer, d.n_seq, d.width, d.heads, d.hidden, d.act, d.linear_layout, d.pos = n_layer, nb, D, heads, hidden, act, int(linear_layout), pos
-    d.blocks = blocks_arr
-    d.x, d.kcache, d.vcache = x.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
-    d.ld_layer, d.ld_seq = kcache.stride(0), kcache.stride(1)
-    d.scratch16 = scratch16.data_ptr()
+    s.n_layer, s.n_seq, s.width, s.heads, s.hidden, s.act, s.linear_layout, s.pos = n_layer, nb, D, heads, hidden, act, int(linear_layout), pos
+    s.blocks = blocks_arr
+    s.x, s.kcache, s.vcache = x.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
+    s.ld_layer, s.ld_seq = kcache.stride(0), kcache.stride(1)
+    s.scratch16 = scratch16.data_ptr()
+    if wte16 is not None:
+        s.lnf_w, s.lnf_b, s.wte16, s.vocab = lnf_w.data_ptr(), lnf_b.data_ptr(), wte16.data_ptr(), wte16.shape[0]
     if logits is not None:
-        _req(logits, torch.float32, "logits")
-        d.lnf_w, d.lnf_b, d.wte16 = lnf_w.data_ptr(), lnf_b.data_ptr(), wte16.data_ptr()
-        d.vocab, d.logits, d.ld_logits = wte16.shape[0], logits.data_ptr(), logits.stride(0)
-    check(_fn("cclip_gpt2_decode_step", kcache)(ctypes.byref(d), _stream()), "cclip_gpt2_decode_step")
+        assert logits.dtype == torch.float32 and logits.device == kcache.device
+        s.logits, s.ld_logits = logits.data_ptr(), logits.stride(0)
+    return s
+
+
+def _launch(name: str, d, kcache) -> None:
+    _req16(kcache, "kcache")
+    check(_fn(name, kcache)(ctypes.byref(d), _stream()), name)
+
+
+def gpt2_decode_step(blocks_arr, n_layer, x, kcache, *args, **kw) -> None:
+    """One KV-cached decode step for x.shape[0] sequences, issued natively (cclip_gpt2_decode_step; arguments: decode_step_desc).
+    kcache / vcache: [n_layer, n_seq_alloc, max_len, width] 16-bit; x: fp32 [n_seq, width] (in place)."""
+    _launch("cclip_gpt2_decode_step", decode_step_desc(blocks_arr, n_layer, x, kcache, *args, **kw), kcache)
 
 
 class BeamDesc(ctypes.Structure):
@@ -1235,72 +1248,6 @@ class BeamDesc(ctypes.Structure):
                 ("state", c_void_p), ("select_ws", c_void_p)]
 
 
-BEAM_MAX_BEAMS, BEAM_MAX_LAYERS, BEAM_SELECT_WS_FLOATS = 8, 24, 256 * 8 * 20
-
-
-class BeamState:
-    """Device state of one persistent beam search (cclip_gpt2_beam_search): token rows, scores, lengths, stop flags, the
-    cache-slot table and the kernel's bookkeeping words."""
-
-    def __init__(self, n_beams: int, max_len: int, max_tokens: int, device):
-        assert 1 <= n_beams <= BEAM_MAX_BEAMS
-        self.n_beams, self.max_len = n_beams, max_len
-        self.tokens = torch.zeros(n_beams, max_tokens, device=device, dtype=torch.int32)
-        self.scores = torch.zeros(n_beams, device=device, dtype=torch.float32)
-        self.seq_lengths = torch.ones(n_beams, device=device, dtype=torch.float32)
-        self.is_stopped = torch.zeros(n_beams, device=device, dtype=torch.int32)
-        self.slot_of = torch.zeros(max_len, BEAM_MAX_BEAMS, device=device, dtype=torch.int32)
-        self.state = torch.zeros(8, device=device, dtype=torch.int32)
-        self.select_ws = torch.empty(BEAM_SELECT_WS_FLOATS, device=device, dtype=torch.float32)
-        self.x = None
-
-
-def _beam_step_desc(s, x, rows, blocks_arr, n_layer, kcache, vcache, pos, scratch16, max_len, *, heads, hidden, act, linear_layout,
-                    lnf_w, lnf_b, wte16, wte_f32, wpe_f32) -> None:
-    """The checks and the `step` fields that gpt2_beam_search and gpt2_beam_search_batch share (`rows` sequences in x / the cache)."""
-    D = wte16.shape[1]
-    assert kcache.dim() == 4 and kcache.shape[1] == rows and kcache.stride(3) == 1 and kcache.stride(2) == D and kcache.stride() == vcache.stride()
-    assert kcache.shape[2] == max_len and scratch16.numel() >= rows * (5 * D + hidden) and scratch16.dtype == kcache.dtype
-    assert n_layer <= BEAM_MAX_LAYERS and wte_f32.dtype == torch.float32 and wpe_f32.dtype == torch.float32
-    assert wte_f32.is_contiguous() and wpe_f32.is_contiguous() and wte16.is_contiguous() and wpe_f32.shape[0] >= max_len
-    s.n_layer, s.n_seq, s.width, s.heads, s.hidden, s.act, s.linear_layout, s.pos = n_layer, rows, D, heads, hidden, act, int(linear_layout), pos
-    s.blocks = blocks_arr
-    s.x, s.kcache, s.vcache = x.data_ptr(), kcache.data_ptr(), vcache.data_ptr()
-    s.ld_layer, s.ld_seq = kcache.stride(0), kcache.stride(1)
-    s.scratch16 = scratch16.data_ptr()
-    s.lnf_w, s.lnf_b, s.wte16, s.vocab = lnf_w.data_ptr(), lnf_b.data_ptr(), wte16.data_ptr(), wte16.shape[0]
-
-
-def gpt2_beam_search(blocks_arr, n_layer, st: BeamState, kcache, vcache, pos, scratch16, n_steps, *, heads, hidden, act, lnf_w, lnf_b,
-                     wte16, wte_f32, wpe_f32, temperature, stop_token, first_logits=None, logits=None, grid_cap: int = 0) -> None:
-    """`n_steps` KV-cached decode steps + beam selections in ONE persistent launch (cclip_gpt2_beam_search; Conv1D layout).
-    first_logits ([vocab] fp32, the prefill's last row) given: starts with the one-sequence selection of the first loop
-    iteration.  The cache ([n_layer, n_beams, max_len, width]) holds the prefix in slot 0; beams are reordered through
-    st.slot_of."""
-    nb = st.n_beams
-    D = wte16.shape[1]
-    if st.x is None:
-        st.x = torch.empty(nb, D, device=kcache.device, dtype=torch.float32)
-    d = BeamDesc()
-    s = d.step
-    _beam_step_desc(s, st.x, nb, blocks_arr, n_layer, kcache, vcache, pos, scratch16, st.max_len, heads=heads, hidden=hidden, act=act,
-                    linear_layout=False, lnf_w=lnf_w, lnf_b=lnf_b, wte16=wte16, wte_f32=wte_f32, wpe_f32=wpe_f32)
-    if logits is not None:
-        _req(logits, torch.float32, "logits")
-        s.logits, s.ld_logits = logits.data_ptr(), logits.stride(0)
-    d.n_steps, d.first, d.stop_token, d.ld_tokens, d.max_len, d.grid_cap = n_steps, int(first_logits is not None), stop_token, st.tokens.stride(0), st.max_len, grid_cap
-    d.temperature = temperature
-    if first_logits is not None:
-        _req(first_logits, torch.float32, "first_logits")
-        assert first_logits.is_contiguous() and first_logits.numel() == wte16.shape[0]
-        d.first_logits = first_logits.data_ptr()
-    d.wte_f32, d.wpe_f32 = wte_f32.data_ptr(), wpe_f32.data_ptr()
-    d.slot_of, d.tokens = st.slot_of.data_ptr(), st.tokens.data_ptr()
-    d.scores, d.seq_lengths, d.is_stopped = st.scores.data_ptr(), st.seq_lengths.data_ptr(), st.is_stopped.data_ptr()
-    d.state, d.select_ws = st.state.data_ptr(), st.select_ws.data_ptr()
-    check(_fn("cclip_gpt2_beam_search", kcache)(ctypes.byref(d), _stream()), "cclip_gpt2_beam_search")
-
-
 class BeamBatchDesc(ctypes.Structure):
     _fields_ = [("step", DecodeDesc),
                 ("n_cap", c_int), ("beams", c_int), ("n_steps", c_int), ("stop_token", c_int), ("ld_tokens", c_int), ("max_len", c_int),
@@ -1311,54 +1258,101 @@ class BeamBatchDesc(ctypes.Structure):
                 ("state", c_void_p), ("cap_state", c_void_p), ("select_ws", c_void_p)]
 
 
+BEAM_MAX_BEAMS, BEAM_MAX_LAYERS, BEAM_SELECT_WS_FLOATS = 8, 24, 256 * 8 * 20
 BEAM_BATCH_MAX_ROWS = 64
+_BEAM_BUFFERS = ("slot_of", "tokens", "scores", "seq_lengths", "is_stopped", "state", "select_ws")
+
+
+def _alloc_beam_state(st, n_cap: int, n_beams: int, max_len: int, max_tokens: int, device) -> None:
+    """The buffers both persistent kernels keep per search: row c * n_beams + b is beam b of caption c."""
+    R = n_cap * n_beams
+    st.n_beams, st.max_len = n_beams, max_len
+    st.tokens = torch.zeros(R, max_tokens, device=device, dtype=torch.int32)
+    st.scores = torch.zeros(R, device=device, dtype=torch.float32)
+    st.seq_lengths = torch.ones(R, device=device, dtype=torch.float32)
+    st.is_stopped = torch.zeros(R, device=device, dtype=torch.int32)
+    st.state = torch.zeros(8, device=device, dtype=torch.int32)
+    st.select_ws = torch.empty(n_cap * BEAM_SELECT_WS_FLOATS, device=device, dtype=torch.float32)
+    st.x = None                    # fp32 [R, width]: the first descriptor filled from this state allocates it
+
+
+class BeamState:
+    """Device state of one persistent beam search (cclip_gpt2_beam_search): token rows, scores, lengths, stop flags, the
+    cache-slot table and the kernel's bookkeeping words."""
+
+    def __init__(self, n_beams: int, max_len: int, max_tokens: int, device):
+        assert 1 <= n_beams <= BEAM_MAX_BEAMS
+        _alloc_beam_state(self, 1, n_beams, max_len, max_tokens, device)
+        self.slot_of = torch.zeros(max_len, BEAM_MAX_BEAMS, device=device, dtype=torch.int32)
 
 
 class BeamBatchState:
-    """Device state of one batched persistent beam search (cclip_gpt2_beam_search_batch) over n_cap captions: token rows,
-    scores, lengths and stop flags of the n_cap * beams rows (row c * beams + b), the per-caption cache-slot tables and the
-    kernel's bookkeeping words."""
+    """Device state of one batched persistent beam search (cclip_gpt2_beam_search_batch) over n_cap captions: BeamState's
+    buffers for the n_cap * beams rows, the per-caption cache-slot tables and the per-caption bookkeeping words."""
 
     def __init__(self, n_cap: int, n_beams: int, max_len: int, max_tokens: int, device):
         assert n_beams >= 1 and n_cap >= 1                 # (> 8 beams or > 64 rows: the kernel refuses them)
-        self.n_cap, self.n_beams, self.max_len = n_cap, n_beams, max_len
-        R = n_cap * n_beams
-        self.tokens = torch.zeros(R, max_tokens, device=device, dtype=torch.int32)
-        self.scores = torch.zeros(R, device=device, dtype=torch.float32)
-        self.seq_lengths = torch.ones(R, device=device, dtype=torch.float32)
-        self.is_stopped = torch.zeros(R, device=device, dtype=torch.int32)
+        _alloc_beam_state(self, n_cap, n_beams, max_len, max_tokens, device)
+        self.n_cap = n_cap
         self.slot_of = torch.zeros(n_cap, max_len, BEAM_MAX_BEAMS, device=device, dtype=torch.int32)
-        self.state = torch.zeros(8, device=device, dtype=torch.int32)
         self.cap_state = torch.zeros(n_cap, 8, device=device, dtype=torch.int32)
-        self.select_ws = torch.empty(n_cap * BEAM_SELECT_WS_FLOATS, device=device, dtype=torch.float32)
-        self.x = torch.empty(R, 0, device=device, dtype=torch.float32)
 
 
-def gpt2_beam_search_batch(blocks_arr, n_layer, st: BeamBatchState, kcache, vcache, pos, scratch16, n_steps, *, heads, hidden, act,
-                           lnf_w, lnf_b, wte16, wte_f32, wpe_f32, temperature, stop_token, first_logits, grid_cap: int = 0,
-                           linear_layout: bool = False) -> None:
-    """The first selection of every caption from first_logits ([n_cap, vocab] fp32, the prefills' last rows), then up to
-    `n_steps` KV-cached decode steps + selections of all st.n_cap captions in ONE persistent launch
-    (cclip_gpt2_beam_search_batch; Conv1D layout).  kcache / vcache: [n_layer, n_cap * beams, max_len, width], caption c's
-    prefix in slot c * beams.  Raises on a shape the kernel refuses (> 64 rows, > 8 beams, nn.Linear layout)."""
-    nb, nc = st.n_beams, st.n_cap
-    R = nb * nc
-    D = wte16.shape[1]
-    if st.x.shape[1] != D:
-        st.x = torch.empty(R, D, device=kcache.device, dtype=torch.float32)
-    _req(first_logits, torch.float32, "first_logits")
-    assert first_logits.is_contiguous() and first_logits.shape == (nc, wte16.shape[0])
-    assert st.tokens.shape[1] >= n_steps + 1
+def _fill_beam_desc(d, blocks_arr, n_layer, st, kcache, vcache, pos, scratch16, n_steps, *, wte16, wte_f32, wpe_f32, temperature,
+                    stop_token, first_logits=None, grid_cap: int = 0, linear_layout: bool = False, **step_kw) -> None:
+    """What BeamDesc and BeamBatchDesc share: `step` for the st.tokens.shape[0] rows of the search (step_kw: heads, hidden, act,
+    lnf_w, lnf_b and, one caption only, logits), the beam-only checks, and the state object's buffers and the search scalars,
+    which the two structs name alike."""
+    rows, (V, D) = st.tokens.shape[0], wte16.shape
+    if st.x is None:
+        st.x = torch.empty(rows, D, device=kcache.device, dtype=torch.float32)
+    decode_step_desc(blocks_arr, n_layer, st.x, kcache, vcache, pos, scratch16, wte16=wte16, linear_layout=linear_layout, into=d.step,
+                     **step_kw)
+    assert n_layer <= BEAM_MAX_LAYERS and kcache.shape[1] == rows and kcache.shape[2] == st.max_len
+    assert wte_f32.dtype == torch.float32 and wpe_f32.dtype == torch.float32
+    assert wte_f32.is_contiguous() and wpe_f32.is_contiguous() and wte16.is_contiguous() and wpe_f32.shape[0] >= st.max_len
+    d.n_steps, d.stop_token, d.ld_tokens, d.max_len, d.grid_cap = n_steps, stop_token, st.tokens.stride(0), st.max_len, grid_cap
+    d.temperature = temperature
+    d.wte_f32, d.wpe_f32 = wte_f32.data_ptr(), wpe_f32.data_ptr()
+    if first_logits is not None:                              # one row of V per caption
+        assert first_logits.dtype == torch.float32 and first_logits.device == kcache.device
+        assert first_logits.is_contiguous() and first_logits.numel() == rows // st.n_beams * V
+        d.first_logits = first_logits.data_ptr()
+    for name in _BEAM_BUFFERS:
+        setattr(d, name, getattr(st, name).data_ptr())
+
+
+def beam_search_desc(*args, first_logits=None, **kw) -> BeamDesc:
+    """BeamDesc of a one-caption search (arguments: _fill_beam_desc, st a BeamState).  first_logits ([vocab] fp32, the prefill's
+    last row) given: the launch starts with the one-sequence selection of the first loop iteration.  The cache ([n_layer,
+    n_beams, max_len, width]) holds the prefix in slot 0; beams are reordered through st.slot_of."""
+    d = BeamDesc()
+    _fill_beam_desc(d, *args, first_logits=first_logits, **kw)
+    d.first = int(first_logits is not None)
+    return d
+
+
+def gpt2_beam_search(blocks_arr, n_layer, st: BeamState, kcache, *args, **kw) -> None:
+    """`n_steps` KV-cached decode steps + beam selections in ONE persistent launch (cclip_gpt2_beam_search; Conv1D layout;
+    arguments: beam_search_desc)."""
+    _launch("cclip_gpt2_beam_search", beam_search_desc(blocks_arr, n_layer, st, kcache, *args, **kw), kcache)
+
+
+def beam_search_batch_desc(blocks_arr, n_layer, st: BeamBatchState, kcache, vcache, pos, scratch16, n_steps, *, first_logits, **kw) -> BeamBatchDesc:
+    """BeamBatchDesc of a search over st.n_cap captions (arguments: _fill_beam_desc).  first_logits: [n_cap, vocab] fp32, the
+    prefills' last rows; kcache / vcache: [n_layer, n_cap * beams, max_len, width], caption c's prefix in slot c * beams."""
+    assert first_logits.dim() == 2 and first_logits.shape[0] == st.n_cap and st.tokens.shape[1] >= n_steps + 1
     d = BeamBatchDesc()
-    _beam_step_desc(d.step, st.x, R, blocks_arr, n_layer, kcache, vcache, pos, scratch16, st.max_len, heads=heads, hidden=hidden, act=act,
-                    linear_layout=linear_layout, lnf_w=lnf_w, lnf_b=lnf_b, wte16=wte16, wte_f32=wte_f32, wpe_f32=wpe_f32)
-    d.n_cap, d.beams, d.n_steps, d.stop_token = nc, nb, n_steps, stop_token
-    d.ld_tokens, d.max_len, d.grid_cap, d.temperature = st.tokens.stride(0), st.max_len, grid_cap, temperature
-    d.first_logits, d.wte_f32, d.wpe_f32 = first_logits.data_ptr(), wte_f32.data_ptr(), wpe_f32.data_ptr()
-    d.slot_of, d.tokens = st.slot_of.data_ptr(), st.tokens.data_ptr()
-    d.scores, d.seq_lengths, d.is_stopped = st.scores.data_ptr(), st.seq_lengths.data_ptr(), st.is_stopped.data_ptr()
-    d.state, d.cap_state, d.select_ws = st.state.data_ptr(), st.cap_state.data_ptr(), st.select_ws.data_ptr()
-    check(_fn("cclip_gpt2_beam_search_batch", kcache)(ctypes.byref(d), _stream()), "cclip_gpt2_beam_search_batch")
+    _fill_beam_desc(d, blocks_arr, n_layer, st, kcache, vcache, pos, scratch16, n_steps, first_logits=first_logits, **kw)
+    d.n_cap, d.beams, d.cap_state = st.n_cap, st.n_beams, st.cap_state.data_ptr()
+    return d
+
+
+def gpt2_beam_search_batch(blocks_arr, n_layer, st: BeamBatchState, kcache, *args, **kw) -> None:
+    """The first selection of every caption, then up to `n_steps` KV-cached decode steps + selections of all st.n_cap captions
+    in ONE persistent launch (cclip_gpt2_beam_search_batch; Conv1D layout; arguments: beam_search_batch_desc).  Raises on a
+    shape the kernel refuses (> 64 rows, > 8 beams, nn.Linear layout)."""
+    _launch("cclip_gpt2_beam_search_batch", beam_search_batch_desc(blocks_arr, n_layer, st, kcache, *args, **kw), kcache)
 
 
 # --------------------------------------------------------------------------------------------

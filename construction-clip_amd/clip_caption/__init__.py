@@ -1,5 +1,6 @@
 """MI355X build of the prefix-caption model classes of /root/reference/CLIP_prefix_caption/train.py."""
-from .model import (CaptionScores, ClipCaptionModel, ClipCaptionPrefix, GPT2LMHeadModel, KVCache, MLP, MappingType,  # noqa: F401
+from .decode import KVCache  # noqa: F401
+from .model import (CaptionScores, ClipCaptionModel, ClipCaptionPrefix, GPT2LMHeadModel, MLP, MappingType,  # noqa: F401
                     TransformerMapper, evaluate_captions)
 from .metrics import corpus_bleu_mean, sentence_bleu  # noqa: F401
 from .generate import (caption_attention_map, generate2, generate2_batch, generate_beam, generate_beam_batch,  # noqa: F401

@@ -32,6 +32,7 @@ from cclip_hip import ops
 from cclip_hip.arena import ParamArena
 from cclip_hip.stack import BlockStack, BlockWeights, Scratch, StackGeometry
 
+from .decode import DecodeMixin
 from .weights import GPT2_MODELS, CaptionGeometry, init_caption_state_dict, init_transformer_mapper_state_dict
 
 
@@ -274,48 +275,13 @@ class GPT2LMHeadModel(_Holder):
         return SimpleNamespace(logits=self._owner()._logits_from_embeds(inputs_embeds, attention_mask))
 
 
-class KVCache:
-    """Per-layer keys / values of the positions processed so far: k, v [n_layer, n_seq, max_len, n_embd] in the
-    compute dtype, `length` positions valid.  reorder(idx) is beam search's `generated = generated[next_tokens_source]`
-    (test.py:416) applied to the cache."""
-
-    def __init__(self, n_layer: int, n_seq: int, max_len: int, width: int, device, dtype):
-        self.k = torch.empty(n_layer, n_seq, max_len, width, device=device, dtype=dtype)
-        self.v = torch.empty_like(self.k)
-        self.length = 0
-
-    @property
-    def n_seq(self) -> int:
-        return self.k.shape[1]
-
-    @property
-    def max_len(self) -> int:
-        return self.k.shape[2]
-
-    def reorder(self, idx: torch.Tensor) -> "KVCache":
-        idx = idx.to(self.k.device).long()
-        L = self.length
-        out = KVCache.__new__(KVCache)
-        out.k = torch.empty(self.k.shape[0], idx.numel(), *self.k.shape[2:], device=self.k.device, dtype=self.k.dtype)
-        out.v = torch.empty_like(out.k)
-        out.k[:, :, :L] = self.k[:, idx, :L]
-        out.v[:, :, :L] = self.v[:, idx, :L]
-        out.length = L
-        return out
-
-    def expand(self, n: int) -> "KVCache":
-        """one sequence -> n identical ones (`generated.expand(beam_size, ...)`, test.py:398)"""
-        assert self.n_seq == 1
-        return self.reorder(torch.zeros(n, dtype=torch.long))
-
-
 _GPT_KEYS = {"ln1_w": "ln_1.weight", "ln1_b": "ln_1.bias", "w_qkv": "attn.c_attn.weight", "b_qkv": "attn.c_attn.bias",
              "w_o": "attn.c_proj.weight", "b_o": "attn.c_proj.bias", "ln2_w": "ln_2.weight", "ln2_b": "ln_2.bias",
              "w_fc": "mlp.c_fc.weight", "b_fc": "mlp.c_fc.bias", "w_proj": "mlp.c_proj.weight", "b_proj": "mlp.c_proj.bias"}
 _MATS = ("w_qkv", "w_o", "w_fc", "w_proj")
 
 
-class ClipCaptionModel(nn.Module):
+class ClipCaptionModel(DecodeMixin, nn.Module):
     def __init__(self, prefix_length: int, clip_length: Optional[int] = None, prefix_size: int = 512, num_layers: int = 8,
                  mapping_type: MappingType = MappingType.MLP, gpt2_type: str = ""):
         super().__init__()
@@ -549,17 +515,16 @@ class ClipCaptionModel(nn.Module):
     # ---- shared forward to the final hidden states ----
     def _hidden_forward(self, x: torch.Tensor, B: int, S: int, mask: Optional[torch.Tensor], saved: Optional[dict],
                         cu: Optional[torch.Tensor] = None, rowmap: Optional[torch.Tensor] = None,
-                        tail_rows: Optional[torch.Tensor] = None):
+                        tail_rows: Optional[torch.Tensor] = None, attn_probe=None):
         keep = None
         if mask is not None:
             keep = mask.detach().to(torch.float32).contiguous()
             assert keep.shape == (B, S), f"attention_mask {tuple(mask.shape)} vs sequence {(B, S)}"
             if rowmap is not None:
                 keep = keep.view(-1)[rowmap].contiguous()              # packed rows: the mask entries of the live positions
-        return self._stack.forward(x, B, saved=saved, key_keep=keep, T=S, cu=cu, tail_rows=tail_rows)
+        return self._stack.forward(x, B, saved=saved, key_keep=keep, T=S, cu=cu, tail_rows=tail_rows, attn_probe=attn_probe)
 
     def _pack_rows(self) -> bool:
-        import os
         v = getattr(self, "pack_rows", None)
         return (os.environ.get("CCLIP_PACK_TEXT", "1") != "0") if v is None else bool(v)
 
@@ -578,27 +543,41 @@ class ClipCaptionModel(nn.Module):
         ops.gemm_bf16(xf, ar.b["model.transformer.wte.weight"], out_f32=logits)
         return logits, (xf, st) if train else None
 
+    def _lm_all(self, xo: torch.Tensor, B: int, S: int) -> torch.Tensor:
+        """_lm_rows on every row of the B sequences of S positions in xo: inference logits fp32 [B, S, V]."""
+        rows = torch.arange(B * S, device=xo.device, dtype=torch.int32)
+        return self._lm_rows(xo, rows, False)[0].unflatten(0, (B, S))
+
+    def _positioned_rows(self, inputs_embeds: torch.Tensor, positions_added: bool = False) -> torch.Tensor:
+        """fp32 rows [B*S, D] of `inputs_embeds` [B, S, D] + wpe[s], in a buffer of their own (the stack works in place on its
+        input rows).  positions_added: the embeddings already hold `+ wpe[s]`, and are only copied."""
+        B, S, D = inputs_embeds.shape
+        emb = inputs_embeds.detach().float().contiguous().view(B * S, D)
+        if positions_added:
+            return emb.clone()
+        x = torch.empty(B * S, D, device=emb.device, dtype=torch.float32)
+        ops.add_positional(emb, self._arena.params["model.transformer.wpe.weight"].data, x, rows=B * S, S=S)
+        return x
+
+    def _infer_hidden(self, inputs_embeds: torch.Tensor, mask=None, attn_probe=None) -> torch.Tensor:
+        """The inference pass of the stack over `inputs_embeds` [B, S, D] (+ positions) under the key-padding `mask`: the final
+        hidden states [B*S, D].  attn_probe: BlockStack.forward's tap on every layer's q / k rows."""
+        self._ensure_runtime()
+        self._arena.refresh_shadows()
+        B, S, _ = inputs_embeds.shape
+        return self._hidden_forward(self._positioned_rows(inputs_embeds), B, S, mask, None, attn_probe=attn_probe)
+
     def _logits_from_embeds(self, inputs_embeds: torch.Tensor, attention_mask) -> torch.Tensor:
         """GPT2LMHeadModel(inputs_embeds=..., attention_mask=...).logits, inference only (generate loops, test.py:381)."""
         if torch.is_grad_enabled() and inputs_embeds.requires_grad:
             raise NotImplementedError("train through ClipCaptionModel.forward / caption_loss")
-        self._ensure_runtime()
-        self._arena.refresh_shadows()
-        B, S, D = inputs_embeds.shape
-        x = torch.empty(B * S, D, device=inputs_embeds.device, dtype=torch.float32)
-        ops.add_positional(inputs_embeds.detach().float().contiguous().view(B * S, D),
-                           self._arena.params["model.transformer.wpe.weight"].data, x, rows=B * S, S=S)
-        xo = self._hidden_forward(x, B, S, attention_mask, None)
-        rows = torch.arange(B * S, device=x.device, dtype=torch.int32)
-        return self._lm_rows(xo, rows, False)[0].unflatten(0, (B, S))
+        return self._lm_all(self._infer_hidden(inputs_embeds, attention_mask), *inputs_embeds.shape[:2])
 
     def _logits_and_attentions(self, inputs_embeds: torch.Tensor, attention_mask, layers, q_rows, want_logits: bool):
         """The pass of _logits_from_embeds with a tap on the requested layers: while layer l's packed q / k rows are live, one
         ops.attention_probs launch writes its probabilities.  Returns (logits or None, fp32 [len(layers), B, H, n_q, S])."""
         if torch.is_grad_enabled() and inputs_embeds.requires_grad:
             raise NotImplementedError("attention maps are inference only: detach the embeddings (or use torch.no_grad())")
-        self._ensure_runtime()
-        self._arena.refresh_shadows()
         g = self.model.geo
         B, S, D = inputs_embeds.shape
         dev = inputs_embeds.device
@@ -621,28 +600,17 @@ class ClipCaptionModel(nn.Module):
             rows = torch.tensor([r % S for r in pos], dtype=torch.int32).to(dev)
             n_q = len(pos)
         out = torch.empty(len(layers), B, H, n_q, S, device=dev, dtype=torch.float32)
-        causal = self._stack.geo.causal
 
         def probe(l, q, k, key_keep):
             idx = slot.get(l)
             if idx:
-                ops.attention_probs(q, k, out[idx[0]], B=B, T=S, H=H, causal=causal, key_keep=key_keep, q_rows=rows)
+                ops.attention_probs(q, k, out[idx[0]], B=B, T=S, H=H, causal=self._stack.geo.causal, key_keep=key_keep, q_rows=rows)
                 for i in idx[1:]:                                           # a layer named twice
                     out[i].copy_(out[idx[0]])
 
         with torch.no_grad():
-            x = torch.empty(B * S, D, device=dev, dtype=torch.float32)
-            ops.add_positional(inputs_embeds.detach().float().contiguous().view(B * S, D),
-                               self._arena.params["model.transformer.wpe.weight"].data, x, rows=B * S, S=S)
-            keep = None
-            if attention_mask is not None:
-                keep = attention_mask.detach().to(torch.float32).contiguous()
-                assert keep.shape == (B, S), f"attention_mask {tuple(attention_mask.shape)} vs sequence {(B, S)}"
-            xo = self._stack.forward(x, B, key_keep=keep, T=S, attn_probe=probe)
-            logits = None
-            if want_logits:
-                logits = self._lm_rows(xo, torch.arange(B * S, device=dev, dtype=torch.int32), False)[0].unflatten(0, (B, S))
-        return logits, out
+            xo = self._infer_hidden(inputs_embeds, attention_mask, probe)
+            return (self._lm_all(xo, B, S) if want_logits else None), out
 
     def attention_probs(self, inputs_embeds: torch.Tensor, attention_mask=None, layers=None, q_rows=None) -> torch.Tensor:
         """GPT-2's attention probabilities for `inputs_embeds` [B, S, D] (S <= 256): fp32 [len(layers), B, n_head, n_q, S], what
@@ -652,200 +620,6 @@ class ClipCaptionModel(nn.Module):
         One forward of the stack and one probability launch per requested layer; inference only - no gradient slot, `.grad`
         or KV cache is touched."""
         return self._logits_and_attentions(inputs_embeds, attention_mask, layers, q_rows, False)[1]
-
-    def _cached_logits(self, inputs_embeds: torch.Tensor, cache: Optional[KVCache]):
-        """(logits [B, S_new, V], cache) for the new positions `inputs_embeds` [B, S_new, D] appended after cache.length."""
-        if torch.is_grad_enabled() and inputs_embeds.requires_grad:
-            raise NotImplementedError("KV-cached decode is inference only")
-        self._ensure_runtime()
-        self._arena.refresh_shadows()
-        g = self.model.geo
-        B, S, D = inputs_embeds.shape
-        dev = inputs_embeds.device
-        wpe = self._arena.params["model.transformer.wpe.weight"].data
-        emb = inputs_embeds.detach().float().contiguous()
-        if cache is None:                                     # prefill: the ordinary causal forward, keys / values kept
-            cache = KVCache(g.n_layer, B, g.n_positions, D, dev, self.compute_dtype)
-            x = torch.empty(B * S, D, device=dev, dtype=torch.float32)
-            ops.add_positional(emb.view(B * S, D), wpe, x, rows=B * S, S=S)
-            xo = self._stack.forward(x, B, T=S, kv_out=(cache.k, cache.v))
-            cache.length = S
-            rows = torch.arange(B * S, device=dev, dtype=torch.int32)
-            return self._lm_rows(xo, rows, False)[0].unflatten(0, (B, S)), cache
-        if S != 1 or B != cache.n_seq:
-            raise NotImplementedError(f"decode step takes one new token per cached sequence, got {tuple(inputs_embeds.shape)} for {cache.n_seq} sequences")
-        pos = cache.length
-        if pos >= cache.max_len:
-            raise RuntimeError(f"sequence longer than n_positions = {cache.max_len}")
-        x = emb.view(B, D) + wpe[pos]
-        if os.environ.get("CCLIP_DECODE_DRIVER", "native") != "native":       # launch by launch from Python (reference form)
-            xo = self._stack.decode_step(x, cache.k, cache.v, pos)
-            cache.length = pos + 1
-            rows = torch.arange(B, device=dev, dtype=torch.int32)
-            return self._lm_rows(xo, rows, False)[0].view(B, 1, -1), cache
-        # the whole per-token launch sequence (and ln_f + lm_head) from one native call
-        st = self._stack
-        if getattr(self, "_decode_ptrs", None) is None or self._decode_ptrs[0] is not self._arena:
-            self._decode_ptrs = (self._arena, ops.block_ptr_array(st.blocks))
-        V = g.vocab_size
-        p = self._arena.params
-        hidden = st.geo.hidden or 4 * D
-        scratch = torch.empty(B * (5 * D + hidden), device=dev, dtype=self.compute_dtype)
-        logits = torch.empty(B, (V + 7) // 8 * 8, device=dev, dtype=torch.float32)[:, :V]
-        ops.gpt2_decode_step(self._decode_ptrs[1], g.n_layer, x, cache.k, cache.v, pos, scratch, heads=st.geo.heads, hidden=hidden,
-                             act=st.geo.act, linear_layout=st.geo.linear_layout, lnf_w=p["model.transformer.ln_f.weight"].data,
-                             lnf_b=p["model.transformer.ln_f.bias"].data, wte16=self._arena.b["model.transformer.wte.weight"], logits=logits)
-        cache.length = pos + 1
-        return logits.view(B, 1, -1) if logits.is_contiguous() else logits.unsqueeze(1), cache
-
-    def beam_native_ok(self, beam_size: int) -> bool:
-        """the persistent beam-search kernel covers GPT-2 geometry (Conv1D weights, head_dim 64, <= 24 layers) and <= 8 beams"""
-        if os.environ.get("CCLIP_BEAM_NATIVE", "1") == "0" or not 1 <= beam_size <= ops.BEAM_MAX_BEAMS:
-            return False
-        self._ensure_runtime()
-        g, sg = self.model.geo, self._stack.geo
-        V = g.vocab_size
-        return (not sg.linear_layout and g.n_layer <= ops.BEAM_MAX_LAYERS and sg.head_dim == 64 and sg.width % 64 == 0
-                and (sg.hidden or 4 * sg.width) % 32 == 0 and sg.act in (ops.ACT_NONE, ops.ACT_GELU_NEW) and g.n_positions <= 2048
-                and -(-V // 256) <= 256 and next(self.parameters()).is_cuda)
-
-    @torch.no_grad()
-    def beam_search_native(self, inputs_embeds: torch.Tensor, beam_size: int, entry_length: int, temperature: float,
-                           stop_token: int, prompt_tokens: Optional[torch.Tensor] = None, grid_cap: int = 0):
-        """The reference's generate_beam loop (test.py:380-434) after the prefix: prefill here, then every decode step and
-        every selection inside ONE persistent kernel launch (ops.gpt2_beam_search).  Returns (tokens [beams, n] int64,
-        seq_lengths [beams], scores [beams]) exactly where the reference's loop stops (`is_stopped.all()` or entry_length)."""
-        self._ensure_runtime()
-        self._arena.refresh_shadows()
-        g, st = self.model.geo, self._stack
-        B, S, D = inputs_embeds.shape
-        assert B == 1, "beam search starts from one sequence"
-        dev = inputs_embeds.device
-        p = self._arena.params
-        wpe = p["model.transformer.wpe.weight"].data
-        max_len = g.n_positions
-        if S + entry_length - 1 > max_len:
-            raise RuntimeError(f"sequence longer than n_positions = {max_len}")
-        cache = KVCache(g.n_layer, beam_size, max_len, D, dev, self.compute_dtype)
-        x = torch.empty(S, D, device=dev, dtype=torch.float32)
-        ops.add_positional(inputs_embeds.detach().float().contiguous().view(S, D), wpe, x, rows=S, S=S)
-        xo = st.forward(x, 1, T=S, kv_out=(cache.k, cache.v))          # prefix keys / values -> cache slot 0
-        first_logits = self._lm_rows(xo, torch.tensor([S - 1], device=dev, dtype=torch.int32), False)[0].view(-1).float().contiguous()
-        n_prompt = 0 if prompt_tokens is None else int(prompt_tokens.numel())
-        bs = ops.BeamState(beam_size, max_len, n_prompt + entry_length, dev)
-        if n_prompt:
-            bs.tokens[0, :n_prompt] = prompt_tokens.view(-1).to(dev, torch.int32)
-            bs.state[4] = n_prompt
-        if getattr(self, "_decode_ptrs", None) is None or self._decode_ptrs[0] is not self._arena:
-            self._decode_ptrs = (self._arena, ops.block_ptr_array(st.blocks))
-        hidden = st.geo.hidden or 4 * D
-        scratch = torch.empty(beam_size * (5 * D + hidden), device=dev, dtype=self.compute_dtype)
-        ops.gpt2_beam_search(self._decode_ptrs[1], g.n_layer, bs, cache.k, cache.v, S, scratch, entry_length - 1, heads=st.geo.heads,
-                             hidden=hidden, act=st.geo.act, lnf_w=p["model.transformer.ln_f.weight"].data,
-                             lnf_b=p["model.transformer.ln_f.bias"].data, wte16=self._arena.b["model.transformer.wte.weight"],
-                             wte_f32=p["model.transformer.wte.weight"].data, wpe_f32=wpe, temperature=float(temperature),
-                             stop_token=int(stop_token), first_logits=first_logits,
-                             grid_cap=grid_cap or int(os.environ.get("CCLIP_BEAM_GRID", "0")))
-        state = bs.state.tolist()                                       # the one host sync of the caption
-        if state[1]:
-            raise RuntimeError("cclip_gpt2_beam_search: a grid barrier timed out (workgroups not co-resident?)")
-        n_sel = state[3] if state[2] else entry_length
-        return bs.tokens[:, :n_prompt + n_sel].long(), bs.seq_lengths, bs.scores
-
-    def beam_batch_native_ok(self, beam_size: int, seq_len: int = 0, entry_length: int = 1) -> bool:
-        """the batched persistent kernel covers what beam_native_ok covers (<= 64 rows per launch: at least one caption);
-        its cache holds seq_len + entry_length positions, which must fit n_positions"""
-        return (beam_size <= ops.BEAM_BATCH_MAX_ROWS and entry_length >= 1 and seq_len + entry_length <= self.model.geo.n_positions
-                and self.beam_native_ok(beam_size))
-
-    @torch.no_grad()
-    def beam_search_native_batch(self, inputs_embeds: torch.Tensor, beam_size: int, entry_length: int, temperature: float,
-                                 stop_token: int, grid_cap: int = 0):
-        """beam_search_native for N captions [N, S, D] at once: the prefills (caption by caption), then launches of at most
-        64 // beam_size captions of cclip_gpt2_beam_search_batch, one host sync each.  Returns (tokens [N, beams, n] int64,
-        seq_lengths [N, beams], scores [N, beams], n_sel [N]); caption i's tokens are valid up to n_sel[i] columns (where its
-        own loop stops), the columns after that are zero."""
-        return self.beam_batch_collect(self.beam_batch_enqueue(inputs_embeds, beam_size, entry_length, temperature, stop_token,
-                                                               grid_cap=grid_cap))
-
-    @torch.no_grad()
-    def beam_batch_enqueue(self, inputs_embeds: torch.Tensor, beam_size: int, entry_length: int, temperature: float,
-                           stop_token: int, grid_cap: int = 0, positions_added: bool = False):
-        """The device half of beam_search_native_batch: every prefill and every batched launch is enqueued on the current
-        stream and nothing is read back, so the host does not wait for the device here.  positions_added: the rows already
-        hold `+ wpe[s]` (what cclip_caption_embed writes), so the positional add is skipped.  Returns the pending launches for
-        beam_batch_collect."""
-        self._ensure_runtime()
-        self._arena.refresh_shadows()
-        g, st = self.model.geo, self._stack
-        N, S, D = inputs_embeds.shape
-        if N < 1 or entry_length < 1:
-            raise ValueError(f"need N >= 1 captions and entry_length >= 1, got N = {N}, entry_length = {entry_length}")
-        if S + entry_length > g.n_positions:
-            raise RuntimeError(f"sequence longer than n_positions = {g.n_positions}")
-        dev = inputs_embeds.device
-        p = self._arena.params
-        wpe = p["model.transformer.wpe.weight"].data
-        max_len = S + entry_length                                       # the cache holds what this search can reach
-        # prefill caption by caption, as beam_search_native does: the tiled GEMMs' tile / split choice depends on the row count,
-        # so one prefill of all N would make a caption's first logits (and so its tokens) depend on the batch around it
-        emb = inputs_embeds.detach().float().contiguous()
-        pre = KVCache(g.n_layer, N, S, D, dev, self.compute_dtype)
-        first_all = torch.empty(N, g.vocab_size, device=dev, dtype=torch.float32)
-        last = torch.full((1,), S - 1, device=dev, dtype=torch.int32)    # (a fill launch: no host-to-device copy to wait for)
-        for i in range(N):
-            if positions_added:
-                x = emb[i].clone()                                       # (the stack works in place on its input rows)
-            else:
-                x = torch.empty(S, D, device=dev, dtype=torch.float32)
-                ops.add_positional(emb[i], wpe, x, rows=S, S=S)
-            xo = st.forward(x, 1, T=S, kv_out=(pre.k[:, i:i + 1], pre.v[:, i:i + 1]))
-            first_all[i] = self._lm_rows(xo, last, False)[0].view(-1)
-        if getattr(self, "_decode_ptrs", None) is None or self._decode_ptrs[0] is not self._arena:
-            self._decode_ptrs = (self._arena, ops.block_ptr_array(st.blocks))
-        hidden = st.geo.hidden or 4 * D
-        per = max(1, ops.BEAM_BATCH_MAX_ROWS // beam_size)
-        grid_cap = grid_cap or int(os.environ.get("CCLIP_BEAM_GRID", "0"))
-        launches = []
-        for c0 in range(0, N, per):
-            n = min(per, N - c0)
-            R = n * beam_size
-            k = torch.zeros(g.n_layer, R, max_len, D, device=dev, dtype=self.compute_dtype)
-            v = torch.zeros_like(k)
-            k.view(g.n_layer, n, beam_size, max_len, D)[:, :, 0, :S].copy_(pre.k[:, c0:c0 + n])
-            v.view(g.n_layer, n, beam_size, max_len, D)[:, :, 0, :S].copy_(pre.v[:, c0:c0 + n])
-            bs = ops.BeamBatchState(n, beam_size, max_len, entry_length, dev)
-            scratch = torch.empty(R * (5 * D + hidden), device=dev, dtype=self.compute_dtype)
-            ops.gpt2_beam_search_batch(self._decode_ptrs[1], g.n_layer, bs, k, v, S, scratch, entry_length - 1, heads=st.geo.heads,
-                                       hidden=hidden, act=st.geo.act, lnf_w=p["model.transformer.ln_f.weight"].data,
-                                       lnf_b=p["model.transformer.ln_f.bias"].data, wte16=self._arena.b["model.transformer.wte.weight"],
-                                       wte_f32=p["model.transformer.wte.weight"].data, wpe_f32=wpe, temperature=float(temperature),
-                                       stop_token=int(stop_token), first_logits=first_all[c0:c0 + n].contiguous(), grid_cap=grid_cap,
-                                       linear_layout=bool(st.geo.linear_layout))
-            launches.append((c0, n, bs, (k, v, scratch)))                # (the buffers live until the launch has been read)
-        return dict(N=N, beams=beam_size, entry_length=entry_length, device=dev, launches=launches)
-
-    @torch.no_grad()
-    def beam_batch_collect(self, pending):
-        """The host half of beam_search_native_batch: reads every pending launch back (one host sync per launch) and returns
-        what beam_search_native_batch returns."""
-        N, beam_size, entry_length, dev = pending["N"], pending["beams"], pending["entry_length"], pending["device"]
-        tokens = torch.zeros(N, beam_size, entry_length, device=dev, dtype=torch.int64)
-        lengths = torch.empty(N, beam_size, device=dev, dtype=torch.float32)
-        scores = torch.empty(N, beam_size, device=dev, dtype=torch.float32)
-        n_sel = torch.empty(N, dtype=torch.int64)
-        for c0, n, bs, _ in pending["launches"]:
-            state, cap = bs.state.tolist(), bs.cap_state.cpu()          # the one host sync of the launch
-            if state[1]:
-                raise RuntimeError("cclip_gpt2_beam_search_batch: a grid barrier timed out (workgroups not co-resident?)")
-            ns = torch.where(cap[:, 2] != 0, cap[:, 3], torch.full_like(cap[:, 3], entry_length)).long()
-            n_sel[c0:c0 + n] = ns
-            keep = torch.arange(entry_length)[None, :] < ns[:, None]      # columns past a caption's stop are not its tokens
-            tokens[c0:c0 + n] = (bs.tokens.view(n, beam_size, entry_length).long() * keep.to(dev)[:, None, :])
-            lengths[c0:c0 + n] = bs.seq_lengths.view(n, beam_size)
-            scores[c0:c0 + n] = bs.scores.view(n, beam_size)
-        pending["launches"] = []
-        return tokens[:, :, :int(n_sel.max())], lengths, scores, n_sel
 
     def _embed_and_run(self, tokens, prefix, attribute, mask, train: bool, pack: bool = False):
         self._ensure_runtime()
@@ -925,14 +699,12 @@ class ClipCaptionModel(nn.Module):
         if not tokens.is_cuda:
             raise RuntimeError("ClipCaptionModel: HIP path only (no CPU fallback)")
         B, S = tokens.shape[0], self.prefix_length + attribute.shape[1] + tokens.shape[1]
-        rows = torch.arange(B * S, device=tokens.device, dtype=torch.int32)
         if torch.is_grad_enabled() and any(q.requires_grad for q in self.parameters()):
             self._ensure_runtime()
+            rows = torch.arange(B * S, device=tokens.device, dtype=torch.int32)
             logits = _CaptionLogits.apply(self, tokens, prefix, attribute, mask, rows, *self._arena.params.values())
-        else:
-            xo, _ = self._embed_and_run(tokens, prefix, attribute, mask, False)
-            logits = self._lm_rows(xo, rows, False)[0]
-        return SimpleNamespace(logits=logits.reshape(B, S, -1) if logits.stride(0) == logits.shape[1] else logits.unflatten(0, (B, S)))
+            return SimpleNamespace(logits=logits.reshape(B, S, -1) if logits.stride(0) == logits.shape[1] else logits.unflatten(0, (B, S)))
+        return SimpleNamespace(logits=self._lm_all(self._embed_and_run(tokens, prefix, attribute, mask, False)[0], B, S))
 
     def caption_loss(self, tokens, prefix, attribute, mask=None, attribute_length: Optional[int] = None):
         """Fused train.py:354-357: logits[:, P+A-1:-1] vs tokens, CE(ignore_index=0, mean over kept targets).

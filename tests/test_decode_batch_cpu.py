@@ -1,5 +1,5 @@
-"""CPU: the batched beam-search entry points are declared in include/cclip_hip.h, the ctypes descriptor matches the C struct
-field for field, and generate_beam_batch / generate2_batch refuse embeddings that are not [N, S, D] with N >= 1."""
+"""CPU: the batched beam-search entry points are declared in include/cclip_hip.h, the ctypes descriptors of the three decode
+entry points match their C structs field for field, and generate_beam_batch / generate2_batch refuse embeddings that are not [N, S, D] with N >= 1."""
 import ctypes
 import os
 import re
@@ -35,18 +35,31 @@ def _c_fields(hdr, struct):
     return fields
 
 
-def test_ctypes_descriptor_matches_header_struct():
+def _check_struct(struct, cls_name):
     from cclip_hip import ops
-    fields = _c_fields(_header(), "cclip_beam_batch_desc")
-    kinds = {"int32_t": ctypes.c_int, "float": ctypes.c_float, "ptr": ctypes.c_void_p, "cclip_decode_desc": ops.DecodeDesc}
+    cls = getattr(ops, cls_name)
+    fields = _c_fields(_header(), struct)
+    kinds = {"int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "ptr": ctypes.c_void_p,
+             "cclip_decode_desc": ops.DecodeDesc}
     ref = type("Ref", (ctypes.Structure,), {"_fields_": [(n, kinds[k]) for n, k in fields]})
-    got = [f[0] for f in ops.BeamBatchDesc._fields_]
+    got = [f[0] for f in cls._fields_]
     assert got == [n for n, _ in fields]
     for n, _ in fields:
-        assert getattr(ops.BeamBatchDesc, n).offset == getattr(ref, n).offset, n
-        assert getattr(ops.BeamBatchDesc, n).size == getattr(ref, n).size, n
-    assert ctypes.sizeof(ops.BeamBatchDesc) == ctypes.sizeof(ref)
+        assert getattr(cls, n).offset == getattr(ref, n).offset, n
+        assert getattr(cls, n).size == getattr(ref, n).size, n
+    assert ctypes.sizeof(cls) == ctypes.sizeof(ref)
+
+
+def test_ctypes_descriptor_matches_header_struct():
+    from cclip_hip import ops
+    _check_struct("cclip_beam_batch_desc", "BeamBatchDesc")
     assert ops.BEAM_BATCH_MAX_ROWS == 64
+
+
+@pytest.mark.parametrize("struct, cls_name", [("cclip_beam_desc", "BeamDesc"), ("cclip_decode_desc", "DecodeDesc"),
+                                              ("cclip_block_ptrs", "BlockPtrs")])
+def test_step_and_one_caption_descriptors_match_header_structs(struct, cls_name):
+    _check_struct(struct, cls_name)
 
 
 @pytest.mark.parametrize("bad", [torch.zeros(8, 16), torch.zeros(0, 8, 16), torch.zeros(1, 2, 8, 16)])

@@ -8,7 +8,9 @@ One-caption kernel (cclip_gpt2_beam_search): fp16 and fp32 model (fp16 / bf16 ke
 grid_cap 0, 3, and one search from the prompt "5 9 11 3"; saved: tokens, raw scores, lengths, state[2..4] and the logits buffer
 as the last step left it.  Batched kernel (cclip_gpt2_beam_search_batch): N = 1, 7 x beams 1, 3, 5 with a stop token at which
 the captions stop at different steps, the same under grid_cap 3, and N = 23 x beam 3 (two launches); saved: tokens, scores,
-lengths, n_sel."""
+lengths, n_sel.  Host paths around the kernels: _cached_logits (prefill + two steps, CCLIP_DECODE_DRIVER native and python),
+_logits_from_embeds under a key-padding mask, attention_probs of layers [0, -1] at rows [-1, 0], and beam_batch_enqueue with
+positions_added=True followed by beam_batch_collect."""
 import argparse
 import os
 import sys
@@ -74,6 +76,43 @@ def batched(model, emb, beam, steps, stop, grid_cap=0):
     return {"tokens": t, "scores": s, "lengths": l, "n_sel": n, "stop": torch.tensor([stop])}
 
 
+def cached_steps(model, emb, driver):
+    """prefill of emb [B, S, D], then two decode steps that feed the argmax token back"""
+    old = os.environ.get("CCLIP_DECODE_DRIVER")
+    os.environ["CCLIP_DECODE_DRIVER"] = driver
+    try:
+        with torch.no_grad():
+            out = {}
+            logits, cache = model._cached_logits(emb, None)
+            out["prefill"] = logits
+            for step in (1, 2):
+                logits, cache = model._cached_logits(model.gpt.transformer.wte(logits[:, -1].argmax(-1, keepdim=True)), cache)
+                out[f"step{step}"] = logits
+            out["k"], out["v"] = cache.k[:, :, :cache.length], cache.v[:, :, :cache.length]
+            return out
+    finally:
+        if old is None:
+            del os.environ["CCLIP_DECODE_DRIVER"]
+        else:
+            os.environ["CCLIP_DECODE_DRIVER"] = old
+
+
+def host_paths(model, emb, tag):
+    """emb [3, S, D]: the entry points around the kernels that share host steps with the searches"""
+    for driver in ("native", "python"):
+        yield f"cached/{tag}/{driver}", cached_steps(model, emb, driver)
+    S = emb.shape[1]
+    mask = torch.ones(emb.shape[0], S, device="cuda")
+    mask[1, S - 3:] = 0
+    mask[2, S - 1:] = 0
+    with torch.no_grad():
+        yield f"masked/{tag}", {"logits": model._logits_from_embeds(emb, mask)}
+        yield f"probs/{tag}", {"probs": model.attention_probs(emb, mask, layers=[0, -1], q_rows=[-1, 0])}
+        wpe = model.gpt.transformer.wpe.weight.data[:S].float()
+        t, l, s, n = model.beam_batch_collect(model.beam_batch_enqueue(emb + wpe, 3, ENTRY, 0.5, 7, positions_added=True))
+        yield f"enqueue/{tag}/positions_added", {"tokens": t, "scores": s, "lengths": l, "n_sel": n}
+
+
 def cases():
     """(name, {tensor name: tensor}) of every search, in a fixed order"""
     for half in (True, False):
@@ -93,10 +132,12 @@ def cases():
                 yield f"batch/{tag}/n{n}/beam{beam}/split", batched(model, emb7[:n], beam, 40, stop)
             yield f"batch/{tag}/n{n}/beam3/split/cap3", batched(model, emb7[:n], 3, 40, stop, grid_cap=3)
         yield f"batch/{tag}/n23/beam3", batched(model, embeds(model, geo, 23, seed=44), 3, ENTRY, 7)
+        yield from host_paths(model, emb7[:3], tag)
 
 
 def same_bytes(a, b):
-    return a is not None and a.dtype == b.dtype and a.shape == b.shape and a.numpy().tobytes() == b.numpy().tobytes()
+    raw = lambda t: t.reshape(-1).view(torch.uint8)                     # noqa: E731  (numpy has no bfloat16)
+    return a is not None and a.dtype == b.dtype and a.shape == b.shape and torch.equal(raw(a), raw(b))
 
 
 def main():
