@@ -803,6 +803,122 @@ def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, 
     return tuple(outs)
 
 
+CACHE_AFFINITY_MAX_C = 256
+CACHE_AFFINITY_MAX_D = 1024
+
+
+def cache_layout(labels, num_classes: int):
+    """The class-grouped layout cclip_cache_affinity reads: labels (N integers in [0, num_classes), a tensor or a sequence) ->
+    (gather int64 [Np], class_off int32 [num_classes + 1], class_len int32 [num_classes]), all on the host.  Class c owns the
+    laid-out rows class_off[c] .. class_off[c + 1], a segment of ceil(class_len[c] / 16) * 16 rows (none for an empty class);
+    gather[j] is the original row that laid-out row j holds, -1 for padding.  A stable sort by class: the rows of a class keep
+    their original order.  Pure host code, needs no library."""
+    num_classes = int(num_classes)
+    if num_classes < 1:
+        raise ValueError(f"cache_layout: num_classes = {num_classes}")
+    lab = torch.as_tensor(labels).detach().cpu()
+    if lab.dim() != 1 or ((lab.is_floating_point() or lab.dtype == torch.bool) and lab.numel()):
+        raise ValueError(f"cache_layout: labels must be a 1-D integer vector, got {tuple(lab.shape)} {lab.dtype}")
+    lab = lab.long()
+    if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) >= num_classes):
+        raise ValueError(f"cache_layout: labels outside [0, {num_classes}): min {int(lab.min())}, max {int(lab.max())}")
+    count = torch.bincount(lab, minlength=num_classes)
+    seg = (count + 15) // 16 * 16
+    off = torch.zeros(num_classes + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(seg, 0)
+    if int(off[-1]) >= 2 ** 31:
+        raise ValueError(f"cache_layout: {int(off[-1])} laid-out rows; the kernel's row index is int32")
+    order = torch.sort(lab, stable=True).indices
+    start = torch.cumsum(count, 0) - count                      # first sorted position of each class
+    sl = lab[order]
+    gather = torch.full((int(off[-1]),), -1, dtype=torch.int64)
+    gather[off[:-1][sl] + torch.arange(lab.numel()) - start[sl]] = order
+    return gather, off.to(torch.int32), count.to(torch.int32)
+
+
+def _check_cache_segments(class_off, class_len, Np: int):
+    """The content contract of the two layout arrays (include/cclip_hip.h), checked here because the C entry only sees
+    device pointers.  Returns C."""
+    for t, n in ((class_off, "class_off"), (class_len, "class_len")):
+        if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != torch.int32:
+            raise TypeError(f"cache_affinity: {n}: expected a host int32 tensor (cache_layout's), got "
+                            f"{getattr(t, 'device', type(t))} {getattr(t, 'dtype', '')}")
+        if t.dim() != 1:
+            raise ValueError(f"cache_affinity: {n} must be 1-D, got {tuple(t.shape)}")
+    C = class_len.numel()
+    if class_off.numel() != C + 1:
+        raise ValueError(f"cache_affinity: class_off has {class_off.numel()} entries for {C} classes (expected C + 1)")
+    if not 1 <= C <= CACHE_AFFINITY_MAX_C:
+        raise NotImplementedError(f"cache_affinity: C = {C}; the kernel takes 1 .. {CACHE_AFFINITY_MAX_C} classes")
+    off, ln = class_off.long(), class_len.long()
+    width = off[1:] - off[:-1]
+    if int(off[0]) != 0 or int(off[-1]) != Np or bool((off % 16 != 0).any()) or bool((width < 0).any()):
+        raise ValueError(f"cache_affinity: class_off must start at 0, ascend in multiples of 16 and end at the {Np} stored rows")
+    if bool((ln < 0).any()) or bool((ln > width).any()):
+        raise ValueError("cache_affinity: class_len must lie in 0 .. the width of its segment")
+    return C
+
+
+_CACHE_SEGMENTS = {}       # (device, class_off bytes, class_len bytes) -> the two device copies (bounded; oldest evicted first)
+
+
+def _cache_segments_on(dev, class_off, class_len):
+    key = (str(dev), class_off.numpy().tobytes(), class_len.numpy().tobytes())
+    hit = _CACHE_SEGMENTS.get(key)
+    if hit is None:
+        if len(_CACHE_SEGMENTS) >= 16:
+            _CACHE_SEGMENTS.pop(next(iter(_CACHE_SEGMENTS)))
+        hit = _CACHE_SEGMENTS[key] = (class_off.contiguous().to(dev), class_len.contiguous().to(dev))
+    return hit
+
+
+def cache_affinity_workspace(Q: int, Np: int, C: int) -> int:
+    """bytes of per-split class sums cclip_cache_affinity needs (Q * splits(Np) * C * 4; 0 for a problem it would refuse)"""
+    fn = lib.cclip_cache_affinity_workspace
+    fn.restype = c_long
+    return int(fn(c_int(Q), c_long(Np), c_int(C)))
+
+
+def cache_affinity(q, g, class_off, class_len, beta: float, *, exclude=None, out=None):
+    """Class affinities A[i, c] = sum over the live rows n of class c, n != exclude[i], of exp(beta * (<q[i], g[n]> - 1)):
+    q [Q, D] and g [Np, D] 16-bit (same dtype), inner stride 1, row strides multiples of 8 elements, 16-byte aligned; g laid
+    out by class as cache_layout describes, padding rows allocated (their content is never used).  class_off / class_len:
+    cache_layout's HOST int32 vectors - their content is checked here, on the host, and their device copies are kept per
+    layout, so a call reads nothing back.  exclude: int32 [Q] on the device, a row of g per query to leave out (-1: none).
+    Returns fp32 [Q, C]; an empty class is exactly 0.  The Q x Np matrix is never formed: the only scratch is the per-split
+    workspace.  1 <= C <= 256, D % 32 == 0, 32 <= D <= 1024, Np < 2^31.  A query's row does not depend on Q.  Enqueues two
+    launches; no host read."""
+    Q, Np, D = _pair16("cache_affinity", q, "q", g, "g")
+    C = _check_cache_segments(class_off, class_len, Np)
+    if Q < 1 or Np < 1:
+        raise ValueError(f"cache_affinity: empty operand (Q = {Q}, Np = {Np})")
+    beta = float(beta)
+    if beta != beta or beta in (float("inf"), float("-inf")):
+        raise ValueError(f"cache_affinity: beta must be finite, got {beta}")
+    if D % 32 or not 32 <= D <= CACHE_AFFINITY_MAX_D:
+        raise NotImplementedError(f"cache_affinity: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {CACHE_AFFINITY_MAX_D}")
+    ldq, ldg = _ld16("cache_affinity", q, "q"), _ld16("cache_affinity", g, "g")
+    fn = _fn("cclip_cache_affinity", q, g)
+    dev = q.device
+    if g.device != dev:
+        raise TypeError(f"cache_affinity: q on {dev}, g on {g.device}")
+    if exclude is not None:
+        _req(exclude, torch.int32, "exclude")
+        if tuple(exclude.shape) != (Q,) or not exclude.is_contiguous() or exclude.device != dev:
+            raise ValueError(f"cache_affinity: exclude must be a contiguous int32 [{Q}] vector on {dev}, got {tuple(exclude.shape)}")
+    if out is None:
+        out = torch.empty(Q, C, device=dev, dtype=torch.float32)
+    _req(out, torch.float32, "out")
+    if tuple(out.shape) != (Q, C) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"cache_affinity: out must be a contiguous fp32 [{Q}, {C}] tensor on {dev}, got {tuple(out.shape)}")
+    off_d, len_d = _cache_segments_on(dev, class_off, class_len)
+    nbytes = cache_affinity_workspace(Q, Np, C)
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(Np), c_int(D), _p(off_d), _p(len_d), c_int(C),
+             c_float(beta), _p(exclude), _p(out), _p(ws), c_long(nbytes), _stream()), "cclip_cache_affinity")
+    return out
+
+
 SAMPLE_ROWS_MAX_V = 65536
 
 

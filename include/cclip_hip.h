@@ -334,6 +334,32 @@ int cclip_lm_head_score(const void* x, int64_t ldx, int32_t R, int32_t D, const 
                         const int32_t* labels, int32_t ignore_index, float* logp, float* lse, int32_t* pred,
                         float* pred_logit, void* workspace, hipStream_t stream);
 
+/* ---- class affinities of a few-shot cache model (csrc/embed_cache.hip) -------------------------------------------
+ * For queries q [Q, D] and stored rows g [Np, D], both bf16 (fp16 in the twin) with row strides ldq / ldg in elements and
+ * inner stride 1, with s[i, n] = sum_d q[i, d] g[n, d] accumulated in fp32 on the MFMA (one chain over d = 0, 32, ..):
+ *   out[i, c] = sum over the live rows n of class c with n != exclude[i] of exp(beta * (s[i, n] - 1))     fp32 [Q, C] contiguous
+ * The stored rows are grouped by class: class c owns the rows class_off[c] .. class_off[c + 1], of which the first
+ * class_len[c] are live and the rest is padding (allocated and loaded, but its content, NaN included, never reaches out).
+ * class_off int32 [C + 1] and class_len int32 [C] are DEVICE arrays with: class_off[0] == 0, every class_off[c] a multiple
+ * of 16, ascending, class_off[C] == Np, 0 <= class_len[c] <= class_off[c + 1] - class_off[c].  The entry cannot see their
+ * content without a host read, so that part of the contract is the caller's to check (cclip_hip/ops.py does, on the host
+ * copies it uploads); the kernels clamp every cursor they derive from the two arrays, so no content makes them read or
+ * write out of bounds.  exclude: int32 [Q] on the device, a row of g to leave out per query (-1: none), or NULL.
+ * An empty class gives exactly 0.0f, and so does a class whose only live row is excluded.  The Q x Np matrix is never
+ * written.  The stored rows are split by a rule that depends on Np alone and every sum runs in a fixed order without
+ * atomics: two launches are bitwise equal, and a query's row of out does not depend on Q or on the other queries.
+ * Two launches on `stream`: per-split class sums into `workspace`, then the merge.  workspace: at least
+ * cclip_cache_affinity_workspace(Q, Np, C) = Q * splits(Np) * C * 4 bytes (0 for arguments the call would refuse; splits(Np)
+ * <= min(512, ceil(Np / 256))), 4-byte aligned device memory the caller owns; its contents before and after are meaningless.
+ * Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched, out untouched): null q, g, class_off, class_len, out or workspace; Q <= 0; Np <= 0,
+ * Np >= 2^31 or Np % 16; C < 1 or C > 256; D < 32, D % 32 or D > 1024; ldq or ldg below D or not a multiple of 8; q or g not
+ * 16-byte aligned; a misaligned int32 / fp32 array; workspace too small. */
+int64_t cclip_cache_affinity_workspace(int32_t Q, int64_t Np, int32_t C);
+int cclip_cache_affinity(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t Np, int32_t D,
+                         const int32_t* class_off, const int32_t* class_len, int32_t C, float beta, const int32_t* exclude,
+                         float* out, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- row sampling: temperature, top-k, nucleus and the draw in one launch (csrc/sample_rows.hip, fp32 only) ----
  * One token per row of logits [n, V] (row stride ld >= V elements), for every row r with done[r] == 0:
  *   p        = softmax(row * inv_temperature)
@@ -702,6 +728,9 @@ int cclip_similarity_topk_f16(const void* q, int64_t ldq, int32_t Q, const void*
 int cclip_lm_head_score_f16(const void* x, int64_t ldx, int32_t R, int32_t D, const void* w, int64_t ldw, int32_t V,
                             const int32_t* labels, int32_t ignore_index, float* logp, float* lse, int32_t* pred,
                             float* pred_logit, void* workspace, hipStream_t stream);
+int cclip_cache_affinity_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t Np, int32_t D,
+                             const int32_t* class_off, const int32_t* class_len, int32_t C, float beta, const int32_t* exclude,
+                             float* out, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Classify photos from a few stored, labelled embeddings with no training - the step after scripts/extract_embeddings.py:
+load the support pickle into a `clip.CacheClassifier` (labels from the annotation dicts' `--key`), classify a query pickle
+or image files, print one JSON line per query: {file_name, predicted, probabilities}.
+
+    python scripts/fewshot_classify.py --support embeddings.pkl --key violation_type --queries new.pkl --tune
+    python scripts/fewshot_classify.py --support embeddings.pkl --key violation_type --weights models/clip.pt --prompts --images a.jpg b.jpg
+    python scripts/fewshot_classify.py --synthetic --tune                                       # offline smoke run
+
+--tune picks alpha and beta on the leave-one-out logits of the support set and prints them first; --prompts adds the
+zero-shot term of the prompts "a photo of <class>" (needs the model)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import tempfile
+
+import _common as C
+import torch
+
+ALPHAS = (0.5, 1.0, 2.0, 5.0, 10.0, 20.0, 50.0)
+BETAS = (1.0, 2.0, 5.5, 10.0, 20.0)
+
+
+def _embed_files(model, preprocess, paths, device, bs: int = 64) -> torch.Tensor:
+    from PIL import Image
+    feats = []
+    with torch.no_grad():
+        for s in range(0, len(paths), bs):
+            batch = torch.stack([preprocess(Image.open(p)) for p in paths[s:s + bs]]).to(device)
+            feats.append(model.encode_image(batch).float())
+    return torch.cat(feats)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--support", default=None, help="embedding pickle of scripts/extract_embeddings.py: the labelled photos")
+    ap.add_argument("--key", default="violation_type", help="annotation field that holds the label")
+    ap.add_argument("--queries", default=None, help="embedding pickle of the photos to classify")
+    ap.add_argument("--images", nargs="*", default=None, help="image files to classify (needs the model)")
+    ap.add_argument("--model", default="ViT-B/32")
+    ap.add_argument("--weights", default=None, help="fine-tuned state_dict (CLIP/train.py's clip.pt)")
+    ap.add_argument("--prompts", action="store_true", help="add the zero-shot term of 'a photo of <class>'")
+    ap.add_argument("--tune", action="store_true", help="choose alpha, beta on the support set's leave-one-out logits")
+    ap.add_argument("--alpha", type=float, default=1.0)
+    ap.add_argument("--beta", type=float, default=5.5)
+    ap.add_argument("--per_class", choices=("sum", "mean"), default="sum")
+    ap.add_argument("--synthetic", action="store_true")
+    args = ap.parse_args(argv)
+    import clip
+    from clip_caption.data import load_embeddings, save_embeddings
+    device = torch.device("cuda:0")
+    tmp = None
+    model = preprocess = None
+    if args.synthetic:
+        # generated photos of the nine classes through a seeded small CLIP: the first 9 of every class are the support set
+        tmp = tempfile.TemporaryDirectory()
+        anns = json.load(open(C.make_synthetic_annotations(tmp.name, per_class=12)))["annotations"]
+        args.model = "test-tiny"
+        model, preprocess = clip.load(args.model, device=device, jit=False)
+        model.eval()
+        feats = _embed_files(model, preprocess, [os.path.join(tmp.name, a["file_name"]) for a in anns], device).cpu()
+        sup = [i for i in range(len(anns)) if i % 12 < 9]
+        qry = [i for i in range(len(anns)) if i % 12 >= 9]
+        args.support = os.path.join(tmp.name, "support.pkl")
+        save_embeddings(args.support, feats[sup], [dict(anns[i], clip_embedding=j) for j, i in enumerate(sup)])
+        query_feats, names = feats[qry], [anns[i]["file_name"] for i in qry]
+    else:
+        if args.support is None or (args.queries is None) == (not args.images):
+            ap.error("--support and exactly one of --queries / --images are required (or --synthetic)")
+        if args.images or args.prompts:
+            model, preprocess = clip.load(args.model, device=device, jit=False)
+            if args.weights:
+                model.load_state_dict(torch.load(args.weights, map_location="cpu", weights_only=True))
+            model.eval()
+        if args.queries is not None:
+            data = load_embeddings(args.queries)
+            query_feats = data["clip_embedding"]
+            names = [c.get("file_name") if isinstance(c, dict) else None for c in data["captions"]]
+        else:
+            query_feats, names = _embed_files(model, preprocess, args.images, device), list(args.images)
+
+    dtype = model.compute_dtype if model is not None else None
+    clf = clip.CacheClassifier.from_pickle(args.support, args.key, dtype=dtype, alpha=args.alpha, beta=args.beta,
+                                           per_class=args.per_class)
+    if args.prompts:
+        tokens = C.get_tokenize(model)([f"a photo of {n}" for n in clf.class_names]).to(device)
+        with torch.no_grad():
+            text = model.encode_text(tokens).float()
+        clf = clip.CacheClassifier.from_pickle(args.support, args.key, dtype=dtype, alpha=args.alpha, beta=args.beta,
+                                               per_class=args.per_class, text_features=text,
+                                               logit_scale=float(model.logit_scale.exp()))
+    if args.tune:
+        clf.alpha, clf.beta, acc, _ = clf.tune(ALPHAS, BETAS)
+        C.log_line(tuned=True, alpha=clf.alpha, beta=clf.beta, leave_one_out_accuracy=acc, support=len(clf),
+                   classes=clf.class_names)
+    probs, idx, labels = clf(image_features=query_feats)
+    rows = []
+    for name, label, p in zip(names, labels, probs.tolist()):
+        row = dict(file_name=name, predicted=label, probabilities={n: round(v, 6) for n, v in zip(clf.class_names, p)})
+        C.log_line(**row)
+        rows.append(row)
+    if tmp is not None:
+        tmp.cleanup()
+    return rows
+
+
+if __name__ == "__main__":
+    main()
