@@ -919,6 +919,49 @@ def cache_affinity(q, g, class_off, class_len, beta: float, *, exclude=None, out
     return out
 
 
+def cache_affinity_backward(q, g, class_off, class_len, beta: float, dA, *, exclude=None, out=None):
+    """Gradient of cache_affinity's A with respect to the stored rows: operands, layout and limits as there; dA fp32 [Q, C]
+    contiguous on the device.  Returns dG fp32 [Np, D]:
+        dG[n] = beta * sum over the queries i with n != exclude[i] of dA[i, c(n)] * exp(beta * (<q[i], g[n]> - 1)) * q[i]
+    for the live rows and exactly +0.0 for the padding rows; every row is written (`out` needs no zero fill), a padding row's
+    content (NaN) never reaches it, and the Q x Np matrix is never formed.  No atomics: two launches are bitwise equal.
+    Enqueues two launches; no host read."""
+    Q, Np, D = _pair16("cache_affinity_backward", q, "q", g, "g")
+    C = _check_cache_segments(class_off, class_len, Np)
+    if Q < 1 or Np < 1:
+        raise ValueError(f"cache_affinity_backward: empty operand (Q = {Q}, Np = {Np})")
+    beta = float(beta)
+    if beta != beta or beta in (float("inf"), float("-inf")):
+        raise ValueError(f"cache_affinity_backward: beta must be finite, got {beta}")
+    if D % 32 or not 32 <= D <= CACHE_AFFINITY_MAX_D:
+        raise NotImplementedError(f"cache_affinity_backward: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {CACHE_AFFINITY_MAX_D}")
+    ldq, ldg = _ld16("cache_affinity_backward", q, "q"), _ld16("cache_affinity_backward", g, "g")
+    fn = _fn("cclip_cache_affinity_bwd", q, g)
+    dev = q.device
+    if g.device != dev:
+        raise TypeError(f"cache_affinity_backward: q on {dev}, g on {g.device}")
+    if exclude is not None:
+        _req(exclude, torch.int32, "exclude")
+        if tuple(exclude.shape) != (Q,) or not exclude.is_contiguous() or exclude.device != dev:
+            raise ValueError(f"cache_affinity_backward: exclude must be a contiguous int32 [{Q}] vector on {dev}, got {tuple(exclude.shape)}")
+    _req(dA, torch.float32, "dA")
+    if tuple(dA.shape) != (Q, C) or not dA.is_contiguous() or dA.device != dev:
+        raise ValueError(f"cache_affinity_backward: dA must be a contiguous fp32 [{Q}, {C}] tensor on {dev}, got {tuple(dA.shape)}")
+    if out is None:
+        out = torch.empty(Np, D, device=dev, dtype=torch.float32)
+    _req(out, torch.float32, "out")
+    if tuple(out.shape) != (Np, D) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"cache_affinity_backward: out must be a contiguous fp32 [{Np}, {D}] tensor on {dev}, got {tuple(out.shape)}")
+    off_d, len_d = _cache_segments_on(dev, class_off, class_len)
+    wfn = lib.cclip_cache_affinity_bwd_workspace
+    wfn.restype = c_long
+    nbytes = int(wfn(c_int(Q), c_int(C)))
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(Np), c_int(D), _p(off_d), _p(len_d), c_int(C),
+             c_float(beta), _p(exclude), _p(dA), _p(out), _p(ws), c_long(nbytes), _stream()), "cclip_cache_affinity_bwd")
+    return out
+
+
 SAMPLE_ROWS_MAX_V = 65536
 
 

@@ -10,6 +10,11 @@ The stored rows live on the device in the 16-bit type the towers compute in, gro
 from the fused kernel pair of csrc/embed_cache.hip: the Q x N similarity matrix is never formed, and a query's row does not
 depend on the batch it is scored in.  `alpha` and `beta` are tuned without training, on validation data or - the case that
 matters with a few hundred photos - on the leave-one-out logits of the stored set itself.
+
+`fit()` is the method's second half, Tip-Adapter-F: the stored keys become an fp32 parameter and are trained on the cross-entropy
+of those logits with the towers frozen (CacheAffinityFunction: the gradient of A with respect to the keys comes from
+csrc/embed_cache_bwd.hip, again without the Q x N matrix and with the leave-one-out mask).  `state_dict()` /
+`load_state_dict()` keep a trained cache.
 """
 from __future__ import annotations
 
@@ -48,6 +53,42 @@ def _labels_from_metadata(metadata: Sequence, key: str, class_names: Optional[Se
     if unknown:
         raise ValueError(f"{key!r} values {unknown} are not among class_names {names}")
     return torch.tensor([where[v] for v in values], dtype=torch.long), names
+
+
+class CacheAffinityFunction(torch.autograd.Function):
+    """A = ops.cache_affinity(q16, round16(laid32), ..) with the gradient of the laid-out keys from ops.cache_affinity_backward
+    (csrc/embed_cache_bwd.hip).  `laid32` is the fp32 [Np, E] laid-out key matrix (padding rows NaN); its rounding to the
+    16-bit type of `q16` is passed straight through.  The queries get no gradient: the towers are frozen."""
+
+    @staticmethod
+    def forward(ctx, laid32, q16, class_off, class_len, beta, exclude):
+        if ctx.needs_input_grad[1]:
+            raise NotImplementedError("cache affinity: no gradient for the queries - the towers are frozen, that path is not built")
+        laid16 = laid32.detach().to(q16.dtype)
+        ctx.save_for_backward(laid16, q16.detach(), exclude)
+        ctx.segments = (class_off, class_len, float(beta))
+        return ops.cache_affinity(q16.detach(), laid16, class_off, class_len, float(beta), exclude=exclude)
+
+    @staticmethod
+    def backward(ctx, dA):
+        laid16, q16, exclude = ctx.saved_tensors
+        class_off, class_len, beta = ctx.segments
+        dG = ops.cache_affinity_backward(q16, laid16, class_off, class_len, beta, dA.float().contiguous(), exclude=exclude)
+        return dG, None, None, None, None, None
+
+
+def fit_batches(M: int, batch_size: Optional[int], epochs: int, seed: int):
+    """The batches of CacheClassifier.fit: per epoch a seeded permutation of the M training rows cut into batches of
+    `batch_size` (the last may be shorter); one batch of all rows in their own order when batch_size is None.  Yields
+    (epoch, host int64 index vector)."""
+    gen = torch.Generator().manual_seed(int(seed))
+    for ep in range(epochs):
+        if batch_size is None or batch_size >= M:
+            yield ep, torch.arange(M)
+        else:
+            perm = torch.randperm(M, generator=gen)
+            for s in range(0, M, batch_size):
+                yield ep, perm[s:s + batch_size]
 
 
 class CacheClassifier:
@@ -252,3 +293,90 @@ class CacheClassifier:
         grid = counts.double() / q16.shape[0]
         ia, ib = divmod(best, len(betas))
         return alphas[ia], betas[ib], float(grid[ia, ib]), grid
+
+    # ---- training the keys (Tip-Adapter-F) and persistence --------------------------------------------------------------
+    def fit(self, train_features: Optional[torch.Tensor] = None, train_labels=None, *, epochs: int = 20, lr: float = 1e-3,
+            weight_decay: float = 0.0, batch_size: Optional[int] = None, seed: int = 0) -> List[float]:
+        """Train the stored keys with the towers frozen (Tip-Adapter-F): the keys become an fp32 [N, E] parameter that starts
+        from the normalised rows; each step rebuilds the 16-bit laid-out shadow from it, takes the cross-entropy of
+        zero-shot + alpha * A and sends dA through the fused backward kernel (CacheAffinityFunction); torch.optim.AdamW with a
+        cosine schedule to 0 updates the parameter.  alpha and beta stay fixed (call tune() afterwards) and the keys are not
+        renormalised, as in the paper.  Without train_features the stored rows (as they are now) are the queries, each with
+        its own row excluded - the leave-one-out objective; with train_features [M, E] and train_labels [M] (augmented views,
+        for example) nothing is excluded.  Returns the per-epoch mean loss as a host list, read back once at the end."""
+        if (train_features is None) != (train_labels is None):
+            raise ValueError("fit: give both train_features and train_labels, or neither")
+        epochs = int(epochs)
+        if epochs < 1:
+            raise ValueError(f"fit: epochs = {epochs}")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError(f"fit: batch_size = {batch_size}")
+        if len(self) == 0:
+            raise ValueError("CacheClassifier: no stored rows")
+        dev = self.features.device
+        if train_features is None:
+            q16, excl, target = self.features.clone(), self._pos.to(torch.int32), self._labels_dev
+        else:
+            q16, excl = self._queries(train_features), None
+            target = torch.as_tensor(train_labels).to(dev).long()
+            if tuple(target.shape) != (q16.shape[0],):
+                raise ValueError(f"fit: expected {q16.shape[0]} train_labels, got {tuple(target.shape)}")
+        M = q16.shape[0]
+        if M == 0:
+            raise ValueError("fit: nothing to train on")
+        with torch.no_grad():
+            zs = self._zero_shot16(q16)
+        batches = list(fit_batches(M, None if batch_size is None else int(batch_size), epochs, seed))
+        keys = torch.nn.Parameter(self.features.float())
+        opt = torch.optim.AdamW([keys], lr=float(lr), weight_decay=float(weight_decay))
+        sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, T_max=len(batches))
+        Np = self._laid.shape[0]
+        sums = torch.zeros(epochs, device=dev, dtype=torch.float32)
+        with torch.enable_grad():
+            for ep, idx in batches:
+                idx = idx.to(dev)
+                laid32 = torch.full((Np, self.dim), float("nan"), device=dev, dtype=torch.float32).index_put((self._pos,), keys)
+                A = CacheAffinityFunction.apply(laid32, q16[idx], self.class_off, self.class_len, self.beta,
+                                                None if excl is None else excl[idx].contiguous())
+                if self.per_class == "mean":
+                    A = A / self._count
+                logits = A * self.alpha if zs is None else zs[idx] + A * self.alpha
+                loss = torch.nn.functional.cross_entropy(logits, target[idx])
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                opt.step()
+                sched.step()
+                sums[ep] += loss.detach() * (idx.numel() / M)
+        self._set_rows(keys.detach().to(self.dtype), self.labels)
+        return sums.cpu().tolist()
+
+    def state_dict(self) -> dict:
+        """Plain tensors and lists (torch.save takes it): the keys as they are stored (16-bit, original order, trained or not),
+        labels, class names, alpha, beta, per_class, text features and logit_scale."""
+        return dict(keys=self.features.detach().cpu(), labels=self.labels.clone(), num_classes=self.num_classes,
+                    class_names=None if self.class_names is None else list(self.class_names), alpha=self.alpha, beta=self.beta,
+                    per_class=self.per_class, logit_scale=self.logit_scale,
+                    text_features=None if self.text_features is None else self.text_features.detach().cpu())
+
+    _STATE_KEYS = ("keys", "labels", "num_classes", "class_names", "alpha", "beta", "per_class", "logit_scale", "text_features")
+
+    def load_state_dict(self, state: dict, device: Optional[torch.device] = None) -> "CacheClassifier":
+        """Replace this classifier's content by a state_dict()'s; the keys are taken as they are (not renormalised), so the
+        logits are those of the classifier that was saved, bit for bit."""
+        missing = [k for k in self._STATE_KEYS if k not in state]
+        extra = sorted(k for k in state if k not in self._STATE_KEYS)
+        if missing or extra:
+            raise KeyError(f"load_state_dict: missing {missing}, unexpected {extra}")
+        keys = state["keys"]
+        if not isinstance(keys, torch.Tensor) or keys.dim() != 2 or keys.dtype not in HALF_TYPES:
+            raise ValueError("load_state_dict: keys must be a 2-D bfloat16 / float16 tensor")
+        dev = torch.device(device) if device is not None else (self.features.device if hasattr(self, "features") else _device())
+        self.dtype = keys.dtype
+        text = state["text_features"]
+        self._init(keys.detach().to(dev).contiguous(), state["labels"], state["num_classes"], state["class_names"],
+                   None if text is None else text.to(dev), state["logit_scale"], state["alpha"], state["beta"], state["per_class"])
+        return self
+
+    @classmethod
+    def from_state_dict(cls, state: dict, device: Optional[torch.device] = None) -> "CacheClassifier":
+        return cls.__new__(cls).load_state_dict(state, device)

@@ -360,6 +360,24 @@ int cclip_cache_affinity(const void* q, int64_t ldq, int32_t Q, const void* g, i
                          const int32_t* class_off, const int32_t* class_len, int32_t C, float beta, const int32_t* exclude,
                          float* out, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- gradient of the class affinities with respect to the stored rows (csrc/embed_cache_bwd.hip) -------------------
+ * Operands, layout contract and limits of cclip_cache_affinity; dA fp32 [Q, C] contiguous, dG fp32 [Np, D] contiguous and
+ * 16-byte aligned.  With s as above and c(n) the class whose segment holds row n:
+ *   dG[n, :] = beta * sum over the queries i with n != exclude[i] of dA[i, c(n)] * exp(beta * (s[i, n] - 1)) * q[i, :]   live rows n
+ *   dG[n, :] = +0.0f                                                                                         padding rows n
+ * Every row of dG is written; the content of the padding rows of g, NaN included, never reaches it.  The Q x Np matrix is
+ * never written.  The weights dA * exp(..) enter the second MFMA product as a 16-bit hi + lo pair after a power-of-two scale
+ * taken from max|dA| on the device (relative error 2^-16 per term in bf16, 2^-22 in fp16).  No atomics, one fixed order:
+ * two launches are bitwise equal.  Two launches on `stream`: the partial maxima of |dA| into `workspace`, then the gradient.
+ * workspace: at least cclip_cache_affinity_bwd_workspace(Q, C) = 256 bytes (0 for arguments the call would refuse), 4-byte
+ * aligned device memory the caller owns.  Nothing is read on the host.  The kernels clamp every cursor they derive from
+ * class_off / class_len: no content makes them read or write out of bounds.
+ * CCLIP_ERR_ARG (nothing launched, dG untouched): the cases of cclip_cache_affinity; null dA or dG; dG not 16-byte aligned. */
+int64_t cclip_cache_affinity_bwd_workspace(int32_t Q, int32_t C);
+int cclip_cache_affinity_bwd(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t Np, int32_t D,
+                             const int32_t* class_off, const int32_t* class_len, int32_t C, float beta, const int32_t* exclude,
+                             const float* dA, float* dG, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- row sampling: temperature, top-k, nucleus and the draw in one launch (csrc/sample_rows.hip, fp32 only) ----
  * One token per row of logits [n, V] (row stride ld >= V elements), for every row r with done[r] == 0:
  *   p        = softmax(row * inv_temperature)
@@ -731,6 +749,10 @@ int cclip_lm_head_score_f16(const void* x, int64_t ldx, int32_t R, int32_t D, co
 int cclip_cache_affinity_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t Np, int32_t D,
                              const int32_t* class_off, const int32_t* class_len, int32_t C, float beta, const int32_t* exclude,
                              float* out, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cclip_cache_affinity_bwd_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t Np, int32_t D,
+                                 const int32_t* class_off, const int32_t* class_len, int32_t C, float beta,
+                                 const int32_t* exclude, const float* dA, float* dG, void* workspace, int64_t workspace_bytes,
+                                 hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -6,9 +6,13 @@ or image files, print one JSON line per query: {file_name, predicted, probabilit
     python scripts/fewshot_classify.py --support embeddings.pkl --key violation_type --queries new.pkl --tune
     python scripts/fewshot_classify.py --support embeddings.pkl --key violation_type --weights models/clip.pt --prompts --images a.jpg b.jpg
     python scripts/fewshot_classify.py --synthetic --tune                                       # offline smoke run
+    python scripts/fewshot_classify.py --support embeddings.pkl --queries new.pkl --fit 20 --tune --save-cache cache.pt
+    python scripts/fewshot_classify.py --load-cache cache.pt --queries new.pkl
 
 --tune picks alpha and beta on the leave-one-out logits of the support set and prints them first; --prompts adds the
-zero-shot term of the prompts "a photo of <class>" (needs the model)."""
+zero-shot term of the prompts "a photo of <class>" (needs the model).  --fit EPOCHS trains the stored keys on the support
+set's leave-one-out cross-entropy first (Tip-Adapter-F, towers frozen; --tune then tunes on the trained keys); --save-cache
+writes the classifier's state_dict with torch.save and --load-cache classifies with a saved one instead of --support."""
 from __future__ import annotations
 
 import argparse
@@ -47,6 +51,11 @@ def main(argv=None):
     ap.add_argument("--beta", type=float, default=5.5)
     ap.add_argument("--per_class", choices=("sum", "mean"), default="sum")
     ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--fit", type=int, default=0, metavar="EPOCHS", help="train the stored keys for EPOCHS epochs (leave-one-out)")
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--save-cache", default=None, metavar="PATH", help="write the classifier's state_dict here")
+    ap.add_argument("--load-cache", default=None, metavar="PATH", help="classify with a saved state_dict instead of --support")
     args = ap.parse_args(argv)
     import clip
     from clip_caption.data import load_embeddings, save_embeddings
@@ -67,7 +76,7 @@ def main(argv=None):
         save_embeddings(args.support, feats[sup], [dict(anns[i], clip_embedding=j) for j, i in enumerate(sup)])
         query_feats, names = feats[qry], [anns[i]["file_name"] for i in qry]
     else:
-        if args.support is None or (args.queries is None) == (not args.images):
+        if (args.support is None and args.load_cache is None) or (args.queries is None) == (not args.images):
             ap.error("--support and exactly one of --queries / --images are required (or --synthetic)")
         if args.images or args.prompts:
             model, preprocess = clip.load(args.model, device=device, jit=False)
@@ -82,8 +91,14 @@ def main(argv=None):
             query_feats, names = _embed_files(model, preprocess, args.images, device), list(args.images)
 
     dtype = model.compute_dtype if model is not None else None
-    clf = clip.CacheClassifier.from_pickle(args.support, args.key, dtype=dtype, alpha=args.alpha, beta=args.beta,
-                                           per_class=args.per_class)
+    if args.load_cache is not None:
+        if args.prompts:
+            ap.error("--load-cache brings its own text features; drop --prompts")
+        clf = clip.CacheClassifier.from_state_dict(torch.load(args.load_cache, map_location="cpu", weights_only=True), device)
+        C.log_line(loaded=args.load_cache, support=len(clf), classes=clf.class_names, alpha=clf.alpha, beta=clf.beta)
+    else:
+        clf = clip.CacheClassifier.from_pickle(args.support, args.key, dtype=dtype, alpha=args.alpha, beta=args.beta,
+                                               per_class=args.per_class)
     if args.prompts:
         tokens = C.get_tokenize(model)([f"a photo of {n}" for n in clf.class_names]).to(device)
         with torch.no_grad():
@@ -91,10 +106,15 @@ def main(argv=None):
         clf = clip.CacheClassifier.from_pickle(args.support, args.key, dtype=dtype, alpha=args.alpha, beta=args.beta,
                                                per_class=args.per_class, text_features=text,
                                                logit_scale=float(model.logit_scale.exp()))
+    if args.fit > 0:
+        losses = clf.fit(epochs=args.fit, lr=args.lr, seed=args.seed)
+        C.log_line(fit=True, epochs=args.fit, lr=args.lr, seed=args.seed, first_loss=losses[0], last_loss=losses[-1])
     if args.tune:
         clf.alpha, clf.beta, acc, _ = clf.tune(ALPHAS, BETAS)
         C.log_line(tuned=True, alpha=clf.alpha, beta=clf.beta, leave_one_out_accuracy=acc, support=len(clf),
                    classes=clf.class_names)
+    if args.save_cache is not None:
+        torch.save(clf.state_dict(), args.save_cache)
     probs, idx, labels = clf(image_features=query_feats)
     rows = []
     for name, label, p in zip(names, labels, probs.tolist()):
