@@ -757,6 +757,52 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
     return out_scores, out_index
 
 
+def similarity_range_workspace(Q: int, N: int) -> int:
+    """bytes of per-(query row, gallery split) hit counts cclip_similarity_range_count fills (Q * splits * 4)"""
+    fn = lib.cclip_similarity_range_workspace
+    fn.restype = c_long
+    return int(fn(c_int(Q), c_long(N)))
+
+
+def similarity_range(q, g, threshold: float, self_join: bool = False):
+    """Every pair with s[i, n] = <q[i], g[n]> >= threshold, as CSR: q [Q, D] and g [N, D] as for similarity_topk (16-bit, same
+    dtype, inner stride 1, row strides multiples of 8 elements, 16-byte aligned; D % 32 == 0, D <= 1024, N < 2^31).  Returns
+    (offsets int64 [Q+1], index int32 [H], scores fp32 [H]): the gallery rows of query i, ascending, at offsets[i] ..
+    offsets[i+1], with the score bits similarity_topk returns for the pair.  A NaN score is never a hit; threshold = -inf
+    returns every other pair.  self_join (g must be q itself) keeps only the pairs n > i at about half the work.  The Q x N
+    matrix is never formed.  Count launch, a cumsum over the Q * splits counts on the device, ONE host read of the total H to
+    size the outputs (the only synchronisation), emit launch; H == 0 returns empty tensors and launches no emit."""
+    Q, N, D = _pair16("similarity_range", q, "q", g, "g")
+    if Q < 1 or N < 1:
+        raise ValueError(f"similarity_range: empty operand (Q = {Q}, N = {N})")
+    if D % 32 or D > SIMILARITY_TOPK_MAX_D:
+        raise NotImplementedError(f"similarity_range: D = {D}; the kernel needs D % 32 == 0 and D <= {SIMILARITY_TOPK_MAX_D}")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"similarity_range: N = {N}; the kernel's gallery index is int32 (N < 2^31)")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("similarity_range: threshold is NaN")
+    ldq, ldg = _ld16("similarity_range", q, "q"), _ld16("similarity_range", g, "g")
+    if self_join and (q.data_ptr() != g.data_ptr() or Q != N or ldq != ldg):
+        raise ValueError(f"similarity_range: self_join needs g to be q itself (same memory, same rows), got Q = {Q}, N = {N}")
+    count = _fn("cclip_similarity_range_count", q, g)
+    emit = _fn("cclip_similarity_range_emit", q, g)
+    nbytes = similarity_range_workspace(Q, N)
+    splits = nbytes // (4 * Q)
+    counts = torch.empty(Q * splits, device=q.device, dtype=torch.int32)
+    head = (_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(N), c_int(D), c_float(threshold), c_int(int(bool(self_join))))
+    check(count(*head, _p(counts), c_long(nbytes), _stream()), "cclip_similarity_range_count")
+    starts = torch.zeros(Q * splits + 1, device=q.device, dtype=torch.int64)   # exclusive scan, the total last
+    torch.cumsum(counts, 0, dtype=torch.int64, out=starts[1:])
+    offsets = starts[::splits].contiguous()
+    H = int(starts[-1].item())                                                  # the one host read
+    index = torch.empty(H, device=q.device, dtype=torch.int32)
+    scores = torch.empty(H, device=q.device, dtype=torch.float32)
+    if H > 0:
+        check(emit(*head, _p(starts), c_long(H), c_long(H), _p(index), _p(scores), _stream()), "cclip_similarity_range_emit")
+    return offsets, index, scores
+
+
 LM_HEAD_SCORE_MAX_D = 1024
 
 

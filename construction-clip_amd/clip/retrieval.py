@@ -4,6 +4,10 @@ The reference stops at the embedding pickle (CLIP_prefix_caption/parse_coco.py) 
 (CLIP/train_caption.py:124-136).  `EmbeddingIndex` keeps the L2-normalised rows on the device in the 16-bit type the towers
 compute in and answers a batch of queries with the fused similarity top-k kernel (csrc/embed_topk.hip): exact, the Q x N
 score matrix is never formed, no host read.  `retrieval_recall` is the usual image <-> text R@k on top of it.
+
+The fixed-radius query (csrc/embed_range.hip) is the other half: `range_search` returns every stored row above a similarity,
+`duplicate_pairs` / `duplicate_groups` find the repeated photos of a set (the reference's monthly reports re-use them), and
+`group_split` holds out whole groups, so that no validation row has a twin on the training side.
 """
 from __future__ import annotations
 
@@ -117,12 +121,99 @@ class EmbeddingIndex:
         return scores, index.long()
 
     @torch.no_grad()
+    def range_search(self, queries: torch.Tensor, threshold: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """queries [Q, E] (normalised exactly as `search` does) -> (offsets int64 [Q+1], indices int64 [H], scores fp32 [H]) on
+        the device: every stored row with cosine similarity >= threshold, the rows of query i in ascending index order at
+        offsets[i] .. offsets[i+1].  The fixed-radius query (csrc/embed_range.hip); the Q x N matrix is never formed.  One
+        host read (the total H sizes the outputs)."""
+        if self._n == 0:
+            raise ValueError("range_search: the index is empty")
+        if queries.dim() == 1:
+            queries = queries[None]
+        if queries.dim() != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"range_search: expected [*, {self.dim}] queries, got {tuple(queries.shape)}")
+        q = normalize_rows(queries, self.dtype, self._buf.device)
+        offsets, index, scores = ops.similarity_range(q, self.features, float(threshold))
+        return offsets, index.long(), scores
+
+    @torch.no_grad()
+    def duplicate_pairs(self, threshold: float = 0.95) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Near-duplicates among the stored rows: (pairs int64 [P, 2], scores fp32 [P]) on the device, every i < j with cosine
+        similarity >= threshold, sorted by i, then j (the kernel's self-join order: nothing is sorted here).  An empty index
+        has no pairs."""
+        dev = self._buf.device
+        if self._n == 0:
+            return torch.empty(0, 2, device=dev, dtype=torch.int64), torch.empty(0, device=dev, dtype=torch.float32)
+        rows = self.features
+        offsets, index, scores = ops.similarity_range(rows, rows, float(threshold), self_join=True)
+        first = torch.repeat_interleave(torch.arange(self._n, device=dev), offsets.diff(), output_size=index.numel())
+        return torch.stack([first, index.long()], dim=1), scores
+
+    @torch.no_grad()
+    def duplicate_groups(self, threshold: float = 0.95) -> torch.Tensor:
+        """Single-linkage groups of near-duplicates: int64 [N] (host), the connected components of the `duplicate_pairs`
+        graph, every row labelled by the smallest row index of its group - a row without a duplicate by itself."""
+        pairs, _ = self.duplicate_pairs(threshold)
+        return connected_components(self._n, pairs)
+
+    @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)
 
     @torch.no_grad()
     def search_image(self, model, images: torch.Tensor, k: int = 10):
         return self.search(model.encode_image(images.to(self._buf.device)), k)
+
+
+def connected_components(n: int, pairs: torch.Tensor) -> torch.Tensor:
+    """Labels int64 [n] (host) of the graph on rows 0 .. n-1 with the edges pairs [P, 2]: every row carries the smallest row
+    index of its component.  Union-find on the host: the smaller root always wins, so a root is its component's minimum."""
+    parent = list(range(n))
+
+    def find(x: int) -> int:
+        root = x
+        while parent[root] != root:
+            root = parent[root]
+        while parent[x] != root:                 # path compression
+            parent[x], x = root, parent[x]
+        return root
+
+    for a, b in pairs.cpu().tolist():
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)
+    return torch.tensor([find(x) for x in range(n)], dtype=torch.int64)
+
+
+def group_split(groups: torch.Tensor, val_fraction: float, seed: int) -> Tuple[list, list]:
+    """Split rows into (train_idx, val_idx), both sorted lists, without cutting a group: groups int64 [N] gives every row's
+    group label (`EmbeddingIndex.duplicate_groups`).  The groups, in ascending label order, are drawn in the order of
+    torch.randperm(number of groups) seeded with `seed`, and moved whole to the validation side until it holds at least
+    max(1, round(val_fraction N)) rows; the last group always stays on the training side.  With every group of size 1
+    (labels 0 .. N-1) and the same seed this is exactly the split scripts/train_caption.py --val-fraction makes without
+    groups: the first min(N - 1, max(1, round(val_fraction N))) rows of the seeded row permutation."""
+    groups = torch.as_tensor(groups).cpu()
+    if groups.dim() != 1 or groups.numel() == 0 or groups.is_floating_point():
+        raise ValueError(f"group_split: expected one integer group label per row, got {tuple(groups.shape)} {groups.dtype}")
+    if not val_fraction > 0:
+        raise ValueError(f"group_split: val_fraction = {val_fraction} must be positive")
+    N = groups.numel()
+    labels, member = torch.unique(groups, sorted=True, return_inverse=True)
+    G = labels.numel()
+    if G < 2:
+        raise ValueError("group_split: all rows form one group; nothing can be held out")
+    rows_of = [[] for _ in range(G)]
+    for row, grp in enumerate(member.tolist()):
+        rows_of[grp].append(row)
+    perm = torch.randperm(G, generator=torch.Generator().manual_seed(int(seed))).tolist()
+    want = max(1, int(round(val_fraction * N)))
+    val = []
+    for grp in perm[:G - 1]:
+        if len(val) >= want:
+            break
+        val.extend(rows_of[grp])
+    held = set(val)
+    return [r for r in range(N) if r not in held], sorted(val)
 
 
 def recall_from_indices(indices: torch.Tensor, query_labels: torch.Tensor, gallery_labels: torch.Tensor,

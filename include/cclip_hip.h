@@ -313,6 +313,31 @@ int cclip_similarity_topk(const void* q, int64_t ldq, int32_t Q, const void* g, 
                           int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
                           hipStream_t stream);
 
+/* ---- fixed-radius search over stored embeddings (csrc/embed_range.hip) --------------------------------------
+ * For the operands of cclip_similarity_topk (same contract, same score bits per pair): every pair (i, n) with
+ * s[i, n] >= threshold, in CSR form.  A NaN score is never a hit, +inf is one; threshold = -inf returns every non-NaN pair.
+ *   index[offsets[i] .. offsets[i+1])   int32: the gallery rows of query i, ASCENDING        scores: fp32 alongside
+ * self_join = 1 (needs q == g, ldq == ldg, Q == N) keeps only the pairs n > i and skips the tiles that hold none.
+ * The Q x N matrix is never written; no atomics: two launches are bitwise equal.  Three steps, the middle one the caller's:
+ *   1. cclip_similarity_range_count fills counts, int32 [Q][splits] with splits = cclip_similarity_range_workspace(Q, N) /
+ *      (4 Q): the hits of every (query row, gallery split).  counts: that many bytes of device memory, 4-byte aligned.
+ *   2. The caller scans: starts[j] = counts[0] + .. + counts[j-1] over the Q * splits counts in memory order, int64 on the
+ *      device, and total = their sum, read to the host to size the outputs.  offsets[i] = starts[i * splits],
+ *      offsets[Q] = total.
+ *   3. cclip_similarity_range_emit (same q, g, threshold, self_join) recomputes the tiles and writes every segment at its
+ *      start.  H: the entries index and scores hold; total > H is refused, and no entry at or beyond H is ever written.
+ *      total == 0 launches nothing.
+ * CCLIP_ERR_ARG (nothing launched): a null pointer; Q <= 0; N <= 0 or N >= 2^31; D <= 0, D % 32 or D > 1024; ldq or ldg
+ * below D or not a multiple of 8; q or g not 16-byte aligned; self_join not 0 / 1, or 1 with q != g, ldq != ldg or Q != N;
+ * counts too small or misaligned; starts not 8-byte aligned; total < 0, H < 0 or total > H. */
+int64_t cclip_similarity_range_workspace(int32_t Q, int64_t N);
+int cclip_similarity_range_count(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                                 float threshold, int32_t self_join, int32_t* counts, int64_t workspace_bytes,
+                                 hipStream_t stream);
+int cclip_similarity_range_emit(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                                float threshold, int32_t self_join, const int64_t* starts, int64_t total, int64_t H,
+                                int32_t* index, float* scores, hipStream_t stream);
+
 /* ---- lm_head scoring without the logits (csrc/lm_score.hip) ----------------------------------------------------
  * For hidden rows x [R, D] (the ln_f output) and the vocabulary matrix w [V, D] (the tied wte), both bf16 (fp16 in the twin)
  * with row strides ldx / ldw in elements and inner stride 1, with z[r, j] = sum_d x[r, d] w[j, d] accumulated in fp32 on the MFMA:
@@ -743,6 +768,12 @@ int cclip_cast_f32_to_f16(const float* in, void* out, int64_t n, hipStream_t str
 int cclip_similarity_topk_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
                               int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
                               hipStream_t stream);
+int cclip_similarity_range_count_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                                     float threshold, int32_t self_join, int32_t* counts, int64_t workspace_bytes,
+                                     hipStream_t stream);
+int cclip_similarity_range_emit_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                                    float threshold, int32_t self_join, const int64_t* starts, int64_t total, int64_t H,
+                                    int32_t* index, float* scores, hipStream_t stream);
 int cclip_lm_head_score_f16(const void* x, int64_t ldx, int32_t R, int32_t D, const void* w, int64_t ldw, int32_t V,
                             const int32_t* labels, int32_t ignore_index, float* logp, float* lse, int32_t* pred,
                             float* pred_logit, void* workspace, hipStream_t stream);

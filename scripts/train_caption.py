@@ -57,6 +57,8 @@ def main(argv=None):
                     "val_token_accuracy after every epoch")
     ap.add_argument("--val-fraction", type=float, default=0.0, help="hold this share of --data out (seeded permutation) for the same")
     ap.add_argument("--val-seed", type=int, default=567)
+    ap.add_argument("--dedup-threshold", type=float, default=None, help="with --val-fraction: keep near-duplicate embeddings "
+                    "(cosine >= this, single linkage) on one side of the split; default off")
     args = ap.parse_args(argv)
 
     from clip import optim as coptim
@@ -77,7 +79,16 @@ def main(argv=None):
     dataset = ClipCocoDataset(args.data, P, A, gpt2_type=args.tokenizer, normalize_prefix=args.normalize_prefix,
                               tokenizer=tokenizer)                                        # train.py:406
     val_sets = []
-    if args.val_fraction > 0:                                                             # seeded split of --data
+    if args.val_fraction > 0 and args.dedup_threshold is not None:                        # seeded split of whole duplicate groups
+        import clip
+        groups = clip.EmbeddingIndex(dataset.prefixes[dataset.caption2embedding]).duplicate_groups(args.dedup_threshold)
+        sizes = torch.bincount(groups)
+        train_idx, val_idx = clip.group_split(groups, args.val_fraction, args.val_seed)
+        C.log_line(dedup_threshold=args.dedup_threshold, groups=int((sizes > 0).sum()), duplicate_groups=int((sizes > 1).sum()),
+                   rows_kept_together=int(sizes[sizes > 1].sum()), train_rows=len(train_idx), val_rows=len(val_idx))
+        val_sets.append(torch.utils.data.Subset(dataset, val_idx))
+        dataset = torch.utils.data.Subset(dataset, train_idx)
+    elif args.val_fraction > 0:                                                           # seeded split of --data
         perm = torch.randperm(len(dataset), generator=torch.Generator().manual_seed(args.val_seed)).tolist()
         n_val = min(len(dataset) - 1, max(1, int(round(args.val_fraction * len(dataset)))))
         val_sets.append(torch.utils.data.Subset(dataset, sorted(perm[:n_val])))
