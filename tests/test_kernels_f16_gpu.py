@@ -28,6 +28,7 @@ import torch
 
 from gemm_refs_f64 import (C_ACC, FLOOR, SENT, U, WORST, _acc_bound, _act64, _assert_sensitive, _mats, _worst_report, canvas,  # noqa: F401
                            check_canvas, rnd, within)
+from attn_refs_f64 import _attn64, _attn_bounds, _split_heads
 
 pytestmark = pytest.mark.gpu
 
@@ -307,41 +308,7 @@ def test_gemm_f16_subnormal_range(cfg, akc, bkc, sub_operands):
 # ---------------------------------------------------------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------------------------------------------------------
-def _split_heads(x, B, T, H, dh=64):
-    return x.double().view(B, T, H, dh).permute(0, 2, 1, 3)
-
-
-def _attn64(q, k, v, dO, causal, keep, scale):
-    """fp64 attention fwd / bwd of [B,H,T,dh] operands; returns o, lse, dq, dk, dv and the per-element magnitude scales"""
-    T = q.shape[2]
-    s = (q @ k.transpose(-1, -2)) * scale
-    if causal:
-        s = s + torch.full((T, T), float("-inf"), device=q.device, dtype=torch.float64).triu_(1)
-    if keep is not None:
-        s = s.masked_fill(keep[:, None, None, :] == 0, float("-inf"))
-    lse = torch.logsumexp(s, -1)
-    P = torch.exp(s - lse[..., None])
-    o = P @ v
-    dP = dO @ v.transpose(-1, -2)
-    delta = (dO * o).sum(-1, keepdim=True)
-    dS = P * (dP - delta)
-    dq = scale * dS @ k
-    dk = scale * dS.transpose(-1, -2) @ q
-    dv = P.transpose(-1, -2) @ dO
-    Pv = P @ v.abs()
-    dSm = P * (dO.abs() @ v.abs().transpose(-1, -2) + (dO.abs() * Pv).sum(-1, keepdim=True))
-    mag = dict(o=Pv, dv=P.transpose(-1, -2) @ dO.abs(), dq=scale * dSm @ k.abs(), dk=scale * dSm.transpose(-1, -2) @ q.abs(),
-               P=P, kabs=k.abs(), qabs=q.abs(), vabs=v.abs(), dOabs=dO.abs())
-    return o, lse, dq, dk, dv, mag
-
-
-def _attn_bounds(mag, scale, dt):
-    """4u * magnitude + the subnormal floors of the rounded 16-bit P (o, dv) and dS (dq, dk)"""
-    u, fl = U(dt), FLOOR(dt)
-    return dict(o=4 * u * mag["o"] + fl * mag["vabs"].sum(-2, keepdim=True) + fl,
-                dv=4 * u * mag["dv"] + fl * mag["dOabs"].sum(-2, keepdim=True) + fl,
-                dq=4 * u * mag["dq"] + 2 * fl * scale * mag["kabs"].sum(-2, keepdim=True) + fl,
-                dk=4 * u * mag["dk"] + 2 * fl * scale * mag["qabs"].sum(-2, keepdim=True) + fl)
+# _split_heads, _attn64 and _attn_bounds live in tests/attn_refs_f64.py, shared with the BlockStack tests (tests/stack_ref_f64.py)
 
 
 def _run_attention(dt, B, T, H, causal, keep, g, qs=1.0, ks=1.0, vs=1.0, ds=1.0, q_zero=False):
