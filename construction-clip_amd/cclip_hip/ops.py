@@ -1008,6 +1008,107 @@ def cache_affinity_backward(q, g, class_off, class_len, beta: float, dA, *, excl
     return out
 
 
+KMEANS_MAX_D = 1024
+
+
+def _kmeans_operands(fname: str, x, c, cn: str):
+    """The argument checks kmeans_assign and kmeans_update share (those of similarity_topk).  Returns (N, K, D, ldx, ldc)."""
+    N, K, D = _pair16(fname, x, "x", c, cn)
+    if N < 1 or K < 1:
+        raise ValueError(f"{fname}: empty operand (N = {N}, K = {K})")
+    if D % 32 or not 32 <= D <= KMEANS_MAX_D:
+        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {KMEANS_MAX_D}")
+    if N >= 2 ** 31 or K >= 2 ** 31:
+        raise NotImplementedError(f"{fname}: N = {N}, K = {K}; the kernel's row and centroid indices are int32 (< 2^31)")
+    if c.device != x.device:
+        raise TypeError(f"{fname}: x on {x.device}, {cn} on {c.device}")
+    if c.dtype != x.dtype:
+        raise TypeError(f"{fname}: mixed bfloat16 / float16 operands")
+    return N, K, D, _ld16(fname, x, "x"), _ld16(fname, c, cn)
+
+
+def _kmeans_out(fname: str, t, n: str, shape, dtype, dev):
+    if t is None:
+        return torch.empty(*shape, device=dev, dtype=dtype)
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{fname}: {n} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return t
+
+
+def kmeans_assign(x, c, *, want_second: bool = False, out_assign=None, out_best=None, out_second=None):
+    """The assignment step of k-means: for every row of x [N, D] the centroid of c [K, D] with the largest <x[n], c[k]>.  Both
+    16-bit (same dtype), inner stride 1, row strides multiples of 8 elements, 16-byte aligned.  Returns (assign int32 [N], best
+    fp32 [N], second fp32 [N] or None): the centroid, its score and - with want_second or out_second - the row's second-largest
+    score (NaN if K == 1).  Equal scores go to the lower centroid, NaN ranks below every number; the three are bit for bit what
+    similarity_topk(x, c, min(2, K)) returns.  The N x K matrix is never formed and there is no workspace.  D % 32 == 0,
+    32 <= D <= 1024, N and K < 2^31.  A row's outputs do not depend on N.  Enqueues one launch; no host read."""
+    N, K, D, ldx, ldc = _kmeans_operands("kmeans_assign", x, c, "c")
+    dev = x.device
+    out_assign = _kmeans_out("kmeans_assign", out_assign, "out_assign", (N,), torch.int32, dev)
+    out_best = _kmeans_out("kmeans_assign", out_best, "out_best", (N,), torch.float32, dev)
+    if want_second or out_second is not None:
+        out_second = _kmeans_out("kmeans_assign", out_second, "out_second", (N,), torch.float32, dev)
+    fn = _fn("cclip_kmeans_assign", x, c)
+    check(fn(_p(x), c_long(ldx), c_long(N), _p(c), c_long(ldc), c_long(K), c_int(D), _p(out_assign), _p(out_best), _p(out_second),
+             _stream()), "cclip_kmeans_assign")
+    return out_assign, out_best, out_second
+
+
+def kmeans_update_workspace(N: int, K: int, D: int) -> int:
+    """bytes of per-slab partial sums cclip_kmeans_update needs ((ceil(N / 256) + K) * D * 4; 0 for a problem it would refuse)"""
+    fn = lib.cclip_kmeans_update_workspace
+    fn.restype = c_long
+    return int(fn(c_long(N), c_long(K), c_int(D)))
+
+
+def kmeans_update(x, assign, K: int, prev_c, *, out_c=None, out_norm=None, check_range: bool = True):
+    """The centroid step of spherical k-means: x [N, D] 16-bit as for kmeans_assign, assign an int32 / int64 [N] device vector
+    of cluster ids in [0, K), prev_c [K, D] of x's dtype (inner stride 1).  Returns (c16 [K, D], norm fp32 [K], counts int64
+    [K]): with S = the fp32 sum of the rows of cluster k, norm[k] = |S| and c16[k] = S / |S| rounded once to the 16-bit type;
+    an empty cluster, and one whose rows cancel to zero or whose sum is not finite, keeps prev_c[k] bit for bit with norm 0.
+    out_c may be prev_c.  The grouping is plumbing in torch on the device: a stable sort of assign (`order`: the rows by
+    cluster, ascending inside a cluster - a permutation by construction) and the boundaries seg_off[k] = the number of entries
+    below k, found in the sorted ids (monotone, from 0 to N, by construction); counts are their differences, the exact
+    bincount, without bincount's hidden host read.  What the construction needs is ids inside [0, K): an id outside is a
+    ValueError, caught by ONE device-side min / max read back together and nothing else; check_range=False skips that read for
+    an assign that comes straight from kmeans_assign against K centroids.  No float atomics: two calls are bitwise equal.
+    Enqueues two launches."""
+    N, Kp, D, ldx, ldp = _kmeans_operands("kmeans_update", x, prev_c, "prev_c")
+    K = int(K)
+    if Kp != K:
+        raise ValueError(f"kmeans_update: prev_c has {Kp} rows for K = {K}")
+    dev = x.device
+    if not isinstance(assign, torch.Tensor) or not assign.is_cuda:
+        raise TypeError(f"kmeans_update: assign: expected a cuda tensor, got {getattr(assign, 'device', type(assign))} (no CPU path)")
+    if assign.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"kmeans_update: assign must be int32 or int64, got {assign.dtype}")
+    if assign.dim() != 1 or assign.numel() != N or assign.device != dev:
+        raise ValueError(f"kmeans_update: assign must be a [{N}] vector on {dev}, got {tuple(assign.shape)} on {assign.device}")
+    if out_c is not None and (not isinstance(out_c, torch.Tensor) or out_c.dtype != x.dtype or out_c.device != dev or
+                              tuple(out_c.shape) != (K, D) or out_c.stride(1) != 1 or (K > 1 and out_c.stride(0) < D)):
+        raise ValueError(f"kmeans_update: out_c must be a {x.dtype} [{K}, {D}] tensor on {dev} with inner stride 1, got "
+                         f"{getattr(out_c, 'dtype', type(out_c))} {tuple(getattr(out_c, 'shape', ()))}")
+    out_norm = _kmeans_out("kmeans_update", out_norm, "out_norm", (K,), torch.float32, dev)
+    if check_range:
+        lo, hi = torch.stack([assign.min(), assign.max()]).tolist()             # the one host read
+        if lo < 0 or hi >= K:
+            raise ValueError(f"kmeans_update: assign outside [0, {K}): min {lo}, max {hi}")
+    if out_c is None:
+        out_c = torch.empty(K, D, device=dev, dtype=x.dtype)
+    ids, order = torch.sort(assign, stable=True)
+    seg_off = torch.searchsorted(ids, torch.arange(K + 1, device=dev, dtype=ids.dtype)).to(torch.int32)
+    counts = seg_off.diff().long()
+    order = order.to(torch.int32)
+    nbytes = kmeans_update_workspace(N, K, D)
+    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    fn = _fn("cclip_kmeans_update", x, prev_c)
+    ldo = out_c.stride(0) if K > 1 else max(D, out_c.stride(0))
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(order), _p(seg_off), c_long(K), _p(prev_c), c_long(ldp), _p(out_c),
+             c_long(ldo), _p(out_norm), _p(ws), c_long(nbytes), _stream()), "cclip_kmeans_update")
+    return out_c, out_norm, counts
+
+
 SAMPLE_ROWS_MAX_V = 65536
 
 

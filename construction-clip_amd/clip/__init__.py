@@ -11,6 +11,7 @@ from .explain import interpret_rows, text_row_scores  # noqa: F401  (the same ro
 from .explain import jet_table, relevance_overlay, text_heat_html  # noqa: F401  (attention.py:77-96, 113-143: the overlay picture)
 from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)
 from .retrieval import connected_components, group_split  # noqa: F401  (near-duplicate groups and leak-free held-out splits)
+from .cluster import kmeans, KMeansResult, cluster_purity, name_clusters  # noqa: F401  (spherical k-means of the unlabelled photos)
 from .fewshot import CacheClassifier, confusion_matrix  # noqa: F401  (few-shot classification from the stored, labelled embeddings)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

@@ -156,6 +156,25 @@ class EmbeddingIndex:
         pairs, _ = self.duplicate_pairs(threshold)
         return connected_components(self._n, pairs)
 
+    def kmeans(self, k: int, **kw):
+        """Spherical k-means of the stored rows (clip/cluster.py: csrc/embed_kmeans.hip): a `KMeansResult`.  The rows are used
+        as stored, not copied."""
+        from .cluster import kmeans
+        return kmeans(self, k, **kw)
+
+    @torch.no_grad()
+    def assign(self, centroids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Place the stored rows into existing clusters: centroids [k, E] (a `KMeansResult.centroids`, or any float rows, which
+        are normalised as `search` normalises queries) -> (labels int64 [N], scores fp32 [N]) on the device, the nearest
+        centroid of every row by cosine similarity, equal scores by the lower centroid."""
+        if self._n == 0:
+            raise ValueError("assign: the index is empty")
+        if centroids.dim() != 2 or centroids.shape[1] != self.dim or centroids.shape[0] < 1:
+            raise ValueError(f"assign: expected [k >= 1, {self.dim}] centroids, got {tuple(centroids.shape)}")
+        from .cluster import _rows16
+        labels, scores, _ = ops.kmeans_assign(self.features, _rows16(centroids, self.dtype, self._buf.device))
+        return labels.long(), scores
+
     @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)

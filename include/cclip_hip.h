@@ -403,6 +403,46 @@ int cclip_cache_affinity_bwd(const void* q, int64_t ldq, int32_t Q, const void* 
                              const int32_t* class_off, const int32_t* class_len, int32_t C, float beta, const int32_t* exclude,
                              const float* dA, float* dG, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- spherical k-means over stored embeddings: the assignment step (csrc/embed_kmeans.hip) ----------------------------
+ * For rows x [N, D] and centroids c [K, D], both bf16 (fp16 in the twin) with row strides ldx / ldc in elements and inner
+ * stride 1, with s[n, k] = sum_d x[n, d] c[k, d] accumulated in fp32 on the MFMA (one chain over d = 0, 32, ..: the score
+ * bits cclip_similarity_topk returns for the pair):
+ *   assign[n] int32: the centroid with the largest s[n, .]        best[n] fp32: that score
+ *   second[n] fp32 (may be NULL): the second-largest score of the row, NaN if K == 1
+ * Order as in cclip_similarity_topk: equal fp32 scores (-0 == +0) go to the LOWER centroid index, a NaN score ranks below
+ * every number (a row whose scores are all NaN gets centroid 0 and best = NaN).  (assign, best, second) are the first two
+ * entries cclip_similarity_topk(x, c, min(2, K)) returns, bit for bit.  The N x K matrix is never written and there is no
+ * workspace: one launch on `stream` whose grid runs over blocks of rows while all K centroids stream through LDS.  No
+ * atomics: two launches are bitwise equal, and a row's outputs do not depend on N or on the other rows.  Nothing is read on
+ * the host.
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): null x, c, assign or best; N <= 0 or N >= 2^31; K <= 0 or K >= 2^31;
+ * D < 32, D % 32 or D > 1024; ldx or ldc below D or not a multiple of 8; x or c not 16-byte aligned; a misaligned output. */
+int cclip_kmeans_assign(const void* x, int64_t ldx, int64_t N, const void* c, int64_t ldc, int64_t K, int32_t D,
+                        int32_t* assign, float* best, float* second, hipStream_t stream);
+
+/* ---- spherical k-means: the centroid step (csrc/embed_kmeans.hip) ---------------------------------------------------
+ * x as above.  order int32 [N] and seg_off int32 [K + 1] are DEVICE arrays: order lists the rows of x grouped by cluster,
+ * ascending row index inside a cluster, and cluster k owns the positions seg_off[k] .. seg_off[k + 1] of it (seg_off[0] == 0,
+ * ascending, seg_off[K] == N).  For cluster k with S = the sum of its rows in fp32:
+ *   out_norm[k] = |S|_2  fp32 [K]        out_c[k, :] = S / |S|, rounded once to the 16-bit type   [K, D], row stride ldo
+ * An empty cluster, and one whose |S| is 0 or not finite, gets prev_c[k, :] (row stride ldp) bit for bit and out_norm[k] = 0;
+ * out_c may be prev_c itself.  The sums run in one fixed order that depends on (N, D, order, seg_off) alone - slabs of 256
+ * positions of `order`, no atomics, no fused multiply-add: the outputs are a pure function of (x, order, seg_off, prev_c) and
+ * two launches are bitwise equal.  A lopsided clustering costs what a balanced one costs.
+ * The entry cannot see the content of order / seg_off without a host read, so that they are a permutation and its monotone
+ * boundaries is the caller's to ensure (cclip_hip/ops.py builds both with a stable sort); the kernels clamp every value they
+ * take from the two arrays, so no content makes them read or write outside x, the workspace or the outputs.
+ * Two launches on `stream`: per-slab partial sums into `workspace`, then one work-group per cluster.  workspace: at least
+ * cclip_kmeans_update_workspace(N, K, D) = (ceil(N / 256) + K) * D * 4 bytes (0 for arguments the call would refuse), 4-byte
+ * aligned device memory the caller owns; its contents before and after are meaningless.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): a null pointer; N <= 0 or N >= 2^31; K <= 0 or K >= 2^31; D < 32,
+ * D % 32 or D > 1024; ldx below D or not a multiple of 8; x not 16-byte aligned; ldp or ldo below D; a misaligned int32 /
+ * fp32 / 16-bit array; workspace too small. */
+int64_t cclip_kmeans_update_workspace(int64_t N, int64_t K, int32_t D);
+int cclip_kmeans_update(const void* x, int64_t ldx, int64_t N, int32_t D, const int32_t* order, const int32_t* seg_off,
+                        int64_t K, const void* prev_c, int64_t ldp, void* out_c, int64_t ldo, float* out_norm,
+                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- row sampling: temperature, top-k, nucleus and the draw in one launch (csrc/sample_rows.hip, fp32 only) ----
  * One token per row of logits [n, V] (row stride ld >= V elements), for every row r with done[r] == 0:
  *   p        = softmax(row * inv_temperature)
@@ -784,6 +824,11 @@ int cclip_cache_affinity_bwd_f16(const void* q, int64_t ldq, int32_t Q, const vo
                                  const int32_t* class_off, const int32_t* class_len, int32_t C, float beta,
                                  const int32_t* exclude, const float* dA, float* dG, void* workspace, int64_t workspace_bytes,
                                  hipStream_t stream);
+int cclip_kmeans_assign_f16(const void* x, int64_t ldx, int64_t N, const void* c, int64_t ldc, int64_t K, int32_t D,
+                            int32_t* assign, float* best, float* second, hipStream_t stream);
+int cclip_kmeans_update_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const int32_t* order, const int32_t* seg_off,
+                            int64_t K, const void* prev_c, int64_t ldp, void* out_c, int64_t ldo, float* out_norm,
+                            void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
