@@ -1109,6 +1109,124 @@ def kmeans_update(x, assign, K: int, prev_c, *, out_c=None, out_norm=None, check
     return out_c, out_norm, counts
 
 
+PROBE_MAX_C = 256
+PROBE_MAX_D = 1024
+
+
+def probe_workspace(N: int, C: int, D: int) -> int:
+    """bytes of workspace cclip_probe_forward / cclip_probe_backward need (the hi + lo image of W, the per-slot partials of dW
+    and db, the reduction tree: include/cclip_hip.h states the closed form; 0 for a problem they would refuse)"""
+    fn = lib.cclip_probe_workspace
+    fn.restype = c_long
+    return int(fn(c_long(N), c_int(C), c_int(D)))
+
+
+def probe_parts(N: int, C: int, D: int) -> int:
+    """the number of partial slots the backward's rows are split into: a function of (N, C, D) alone"""
+    return int(lib.cclip_probe_parts(c_long(N), c_int(C), c_int(D)))
+
+
+def _probe_operands(fname: str, x, W, bias, labels, row_weight):
+    """The argument checks probe_forward and probe_backward share.  Returns (N, C, D, ldx)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise TypeError(f"{fname}: x: expected a cuda tensor, got {getattr(x, 'device', type(x))} (no CPU path)")
+    _req16(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"{fname}: x must be a 2-D view with inner stride 1, got {tuple(x.shape)} / {x.stride()}")
+    N, D = x.shape
+    dev = x.device
+    if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.device != dev:
+        raise TypeError(f"{fname}: W: expected fp32 on {dev}, got {getattr(W, 'device', type(W))} {getattr(W, 'dtype', '')}")
+    if W.dim() != 2 or W.shape[1] != D or not W.is_contiguous():
+        raise ValueError(f"{fname}: W must be a contiguous [C, {D}] matrix, got {tuple(W.shape)}")
+    C = W.shape[0]
+    if N < 1:
+        raise ValueError(f"{fname}: empty operand (N = {N})")
+    if not 2 <= C <= PROBE_MAX_C:
+        raise NotImplementedError(f"{fname}: C = {C}; the kernel takes 2 .. {PROBE_MAX_C} classes")
+    if D % 32 or not 32 <= D <= PROBE_MAX_D:
+        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {PROBE_MAX_D}")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    for t, n, shape, dtype in ((bias, "bias", (C,), torch.float32), (labels, "labels", (N,), torch.int32),
+                               (row_weight, "row_weight", (N,), torch.float32)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{fname}: {n} must be a contiguous {dtype} {list(shape)} vector on {dev}, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+    return N, C, D, _ld16(fname, x, "x")
+
+
+def _probe_ws(N: int, C: int, D: int, dev):
+    nbytes = probe_workspace(N, C, D)
+    return torch.empty(nbytes // 4, device=dev, dtype=torch.float32), nbytes
+
+
+def probe_forward(x, W, bias, labels, row_weight=None, logits: bool = False, out=None):
+    """One pass of a linear probe over x [N, D] (16-bit, inner stride 1, row stride a multiple of 8 elements, 16-byte aligned)
+    with W fp32 [C, D], bias fp32 [C] or None, labels int32 [N] or None (a label outside [0, C): the row is ignored) and
+    row_weight fp32 [N] or None (clamped into [0, 1], NaN -> 0).  Returns (lse fp32 [N], loss fp32 [N], pred int32 [N], logits
+    fp32 [N, C] or None): the logits are those of the 16-bit pair hi + lo of W (include/cclip_hip.h), loss[n] =
+    row_weight[n] * (lse[n] - z[n, labels[n]]) and exactly +0.0 for an ignored or zero-weight row, pred the argmax (ties to the
+    lower class, NaN lowest).  `out`: a tuple of tensors to write those into.  The N x C matrix is written only with logits=True.
+    A row's outputs do not depend on N.  2 <= C <= 256, D % 32 == 0, 32 <= D <= 1024.  Enqueues two launches; no host read."""
+    N, C, D, ldx = _probe_operands("probe_forward", x, W, bias, labels, row_weight)
+    dev = x.device
+    o = tuple(out) if out is not None else (None, None, None, None)
+    if len(o) not in (3, 4):
+        raise ValueError("probe_forward: out must be (lse, loss, pred) or (lse, loss, pred, logits)")
+    lse = _kmeans_out("probe_forward", o[0], "lse", (N,), torch.float32, dev)
+    loss = _kmeans_out("probe_forward", o[1], "loss", (N,), torch.float32, dev)
+    pred = _kmeans_out("probe_forward", o[2], "pred", (N,), torch.int32, dev)
+    z = None
+    if logits or (len(o) == 4 and o[3] is not None):
+        z = _kmeans_out("probe_forward", o[3] if len(o) == 4 else None, "logits", (N, C), torch.float32, dev)
+    ws, nbytes = _probe_ws(N, C, D, dev)
+    fn = _fn("cclip_probe_forward", x)
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(W), _p(bias), c_int(C), _p(labels), _p(row_weight), _p(lse), _p(loss),
+             _p(pred), _p(z), _p(ws), c_long(nbytes), _stream()), "cclip_probe_forward")
+    return lse, loss, pred, z
+
+
+def probe_backward(x, W, bias, labels, lse, scale: float, l2: float, row_weight=None, loss=None, out=None):
+    """Gradient of the probe's objective at the operands of probe_forward, whose `lse` (and `loss`, for the scalar) it takes.
+    Returns (dW fp32 [C, D], db fp32 [C], objective fp32 [1] or None):
+        dW = scale * sum_n g[n, :]^T x[n, :] + l2 * W,  db = scale * sum_n g[n, :],  g[n, c] = rw[n] (softmax(z[n])[c] - [c == y_n])
+        objective = scale * sum(loss) + l2 / 2 * sum(W^2)       (with `loss`)
+    of the function of hi + lo the forward evaluates; ignored rows contribute exactly nothing.  `scale` is 1 / (sum of the live
+    rows' weights), the caller's.  `out`: (dW, db) or (dW, db, objective) to write into.  The rows are split over the grid and
+    the partial sums merged in a fixed order: no atomics, two calls are bitwise equal.  Enqueues three launches, four with the
+    objective; no host read."""
+    N, C, D, ldx = _probe_operands("probe_backward", x, W, bias, labels, row_weight)
+    dev = x.device
+    scale, l2 = float(scale), float(l2)
+    for v, n in ((scale, "scale"), (l2, "l2")):
+        if v != v or v in (float("inf"), float("-inf")) or v < 0:
+            raise ValueError(f"probe_backward: {n} must be finite and >= 0, got {v}")
+    for t, n in ((lse, "lse"), (loss, "loss")):
+        if t is None and n == "loss":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (N,) or not t.is_contiguous():
+            raise ValueError(f"probe_backward: {n} must be probe_forward's contiguous fp32 [{N}] vector on {dev}, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    o = tuple(out) if out is not None else (None, None, None)
+    if len(o) not in (2, 3):
+        raise ValueError("probe_backward: out must be (dW, db) or (dW, db, objective)")
+    dW = _kmeans_out("probe_backward", o[0], "dW", (C, D), torch.float32, dev)
+    db = _kmeans_out("probe_backward", o[1], "db", (C,), torch.float32, dev)
+    obj = None
+    if loss is not None:
+        obj = _kmeans_out("probe_backward", o[2] if len(o) == 3 else None, "objective", (1,), torch.float32, dev)
+    elif len(o) == 3 and o[2] is not None:
+        raise ValueError("probe_backward: an objective output needs `loss`")
+    ws, nbytes = _probe_ws(N, C, D, dev)
+    fn = _fn("cclip_probe_backward", x)
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(W), _p(bias), c_int(C), _p(labels), _p(row_weight), _p(lse), _p(loss),
+             c_float(scale), c_float(l2), _p(dW), _p(db), _p(obj), _p(ws), c_long(nbytes), _stream()), "cclip_probe_backward")
+    return dW, db, obj
+
+
 SAMPLE_ROWS_MAX_V = 65536
 
 

@@ -13,5 +13,6 @@ from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search o
 from .retrieval import connected_components, group_split  # noqa: F401  (near-duplicate groups and leak-free held-out splits)
 from .cluster import kmeans, KMeansResult, cluster_purity, name_clusters  # noqa: F401  (spherical k-means of the unlabelled photos)
 from .fewshot import CacheClassifier, confusion_matrix  # noqa: F401  (few-shot classification from the stored, labelled embeddings)
+from .probe import LinearProbe, ProbeLossFunction, ProbeFitResult  # noqa: F401  (linear probe: logistic regression on the stored embeddings)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

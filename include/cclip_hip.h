@@ -443,6 +443,56 @@ int cclip_kmeans_update(const void* x, int64_t ldx, int64_t N, int32_t D, const 
                         int64_t K, const void* prev_c, int64_t ldp, void* out_c, int64_t ldo, float* out_norm,
                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- linear probe: logistic regression on stored embeddings (csrc/embed_probe.hip) -------------------------------------
+ * x [N, D] bf16 (fp16 in the twin), row stride ldx in elements, inner stride 1; W fp32 [C, D] contiguous; bias fp32 [C] or NULL
+ * (= 0); labels int32 [N] or NULL (= every row ignored), a label < 0 or >= C means the row is ignored; row_weight fp32 [N] or
+ * NULL (= 1), clamped into [0, 1] by the kernel, NaN -> 0.  2 <= C <= 256, 32 <= D <= 1024, D % 32 == 0, N < 2^31.
+ * THE OBJECTIVE OF hi + lo.  W enters the MFMA as the 16-bit pair hi = round16(W), lo = round16(W - hi), written by a small
+ * launch into the workspace, and both entries compute functions of that pair:
+ *   z[n, c]   = (bias[c] + H[n, c]) + L[n, c], H = sum_d x[n, d] hi[c, d], L = sum_d x[n, d] lo[c, d]: each ONE fp32 accumulator
+ *               chain over d = 0, 32, .. on the MFMA, the two adds in the order written
+ *   rw[n]     = the clamped row_weight;  live(n) = 0 <= labels[n] < C and rw[n] > 0
+ * cclip_probe_forward, per row (all [N] contiguous; a row's outputs depend on neither N nor the row's position):
+ *   lse[n]    = log sum_c exp z[n, c], by a running maximum (logits of the order of 100 do not overflow)
+ *   loss[n]   = rw[n] (lse[n] - z[n, labels[n]]) for a live row, exactly +0.0f otherwise - SELECTED, never multiplied: an
+ *               ignored row of NaN leaves no trace
+ *   pred[n]   = argmax_c z[n, c] int32: equal fp32 logits (-0 == +0) go to the LOWER class, a NaN logit ranks below every number
+ *   logits    = NULL, or fp32 [N, C] contiguous that receives z; the N x C matrix is written in no other case
+ * cclip_probe_backward takes the forward's lse (and loss, for the objective) of the SAME operands:
+ *   g[n, c]   = rw[n] (exp(z[n, c] - lse[n]) - [c == labels[n]]) for a live row, 0 otherwise (selected); |g| <= 1, and g enters
+ *               the second MFMA product as a 16-bit hi + lo pair (what is dropped: 2^-16 relative in bf16, 2^-22 in fp16, plus
+ *               2^-25 absolute in fp16)
+ *   dW[c, :]  = scale * sum_n g[n, c] x[n, :] + l2 * W[c, :]   fp32 [C, D]        db[c] = scale * sum_n g[n, c]   fp32 [C]
+ *   objective = scale * sum_n loss[n] + l2 / 2 * sum W^2   fp32 [1]; loss and objective are both given or both NULL
+ * dW is the gradient of the objective as a function of the pair (hi + lo differs from W by less than 2^-16 |W| in bf16,
+ * 2^-22 |W| in fp16): loss and gradient belong to one function.  The bias is not regularised.  `scale` is the caller's
+ * 1 / (sum of the live rows' weights).
+ * Order.  The rows are split over the grid in parts of cclip_probe_parts-many slots: a wave adds its row tiles of 32 in
+ * ascending order in registers and writes one fp32 partial per slot; the merge adds the slots in ascending order; loss and W^2
+ * are reduced by a fixed tree.  The slot count and every other choice depend on (N, C, D) alone, there are no atomics and no
+ * fused multiply-add: two calls are bitwise equal.  Every value taken from labels is compared, never used as an address.
+ * Launches on `stream`: forward 2 (pair image, rows); backward 3, or 4 with the objective (pair image, partials, merge,
+ * objective).  Nothing is read on the host.
+ * workspace: at least cclip_probe_workspace(N, C, D) bytes for either entry (0 for arguments they would refuse), 16-byte
+ * aligned device memory the caller owns, contents meaningless before and after.  With Cp = 16 ceil(C / 16),
+ * rs = 4, 2, 1 for Cp = 16, 32, >= 48, T = ceil(N / 32), Pmax = clamp(2^25 / (4 rs Cp D), 1, 1024), tpp = max(8, ceil(T / Pmax))
+ * and S = rs ceil(T / tpp) = cclip_probe_parts(N, C, D):
+ *   bytes = 4 Cp D  (the pair image)  +  4 S Cp (D + 1)  (the partials of dW and db, at most 32 MB + 4 S Cp)
+ *         + 4 (ceil(C D / 256) + 256)  (the reduction tree)
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): null x, W or workspace; forward: null lse, loss or pred; backward: null
+ * lse, dW or db, loss without objective or objective without loss, scale or l2 negative or not finite; N <= 0 or N >= 2^31;
+ * C < 2 or C > 256; D < 32, D % 32 or D > 1024; ldx below D or not a multiple of 8; x or workspace not 16-byte aligned; a
+ * misaligned int32 / fp32 array; workspace too small. */
+int64_t cclip_probe_workspace(int64_t N, int32_t C, int32_t D);
+int32_t cclip_probe_parts(int64_t N, int32_t C, int32_t D);
+int cclip_probe_forward(const void* x, int64_t ldx, int64_t N, int32_t D, const float* W, const float* bias, int32_t C,
+                        const int32_t* labels, const float* row_weight, float* lse, float* loss, int32_t* pred, float* logits,
+                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cclip_probe_backward(const void* x, int64_t ldx, int64_t N, int32_t D, const float* W, const float* bias, int32_t C,
+                         const int32_t* labels, const float* row_weight, const float* lse, const float* loss, float scale,
+                         float l2, float* dW, float* db, float* objective, void* workspace, int64_t workspace_bytes,
+                         hipStream_t stream);
+
 /* ---- row sampling: temperature, top-k, nucleus and the draw in one launch (csrc/sample_rows.hip, fp32 only) ----
  * One token per row of logits [n, V] (row stride ld >= V elements), for every row r with done[r] == 0:
  *   p        = softmax(row * inv_temperature)
@@ -829,6 +879,13 @@ int cclip_kmeans_assign_f16(const void* x, int64_t ldx, int64_t N, const void* c
 int cclip_kmeans_update_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const int32_t* order, const int32_t* seg_off,
                             int64_t K, const void* prev_c, int64_t ldp, void* out_c, int64_t ldo, float* out_norm,
                             void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cclip_probe_forward_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* W, const float* bias, int32_t C,
+                            const int32_t* labels, const float* row_weight, float* lse, float* loss, int32_t* pred,
+                            float* logits, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cclip_probe_backward_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* W, const float* bias, int32_t C,
+                             const int32_t* labels, const float* row_weight, const float* lse, const float* loss, float scale,
+                             float l2, float* dW, float* db, float* objective, void* workspace, int64_t workspace_bytes,
+                             hipStream_t stream);
 
 #ifdef __cplusplus
 }
