@@ -1227,6 +1227,143 @@ def probe_backward(x, W, bias, labels, lse, scale: float, l2: float, row_weight=
     return dW, db, obj
 
 
+TSNE_MAX_K = 63            # one less than similarity_topk's 64: the kNN graph asks for k + 1 and drops the row itself
+TSNE_TILE = 512            # points of y per LDS tile of the repulsion kernel
+TSNE_SPLIT_MAX = 16        # the most splits of its j range
+TSNE_BISECT_STEPS = 100
+
+
+def _tsne_f32(fname: str, t, n: str, shape, dev=None):
+    """A contiguous fp32 device tensor of the given shape (None in shape = any size)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{fname}: {n} must be float32, got {t.dtype}")
+    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)) or not t.is_contiguous() or \
+            (dev is not None and t.device != dev):
+        raise ValueError(f"{fname}: {n} must be a contiguous float32 {list(shape)} tensor on {dev or 'the device'}, got "
+                         f"{tuple(t.shape)} / {t.stride()} on {t.device}")
+    return t
+
+
+def tsne_affinities(scores, perplexity: float, *, out_P=None, out_beta=None):
+    """The conditional neighbour probabilities of t-SNE (include/cclip_hip.h, cclip_tsne_affinities): scores fp32 [N, k], the
+    similarities of every row's k nearest other unit rows (inner stride 1; a row-strided view is fine), 1 <= k <= 63,
+    1 < perplexity < k.  Returns (P fp32 [N, k] with rows summing to 1, beta fp32 [N]): beta by 100 fixed bisection steps so
+    that the row's entropy is log(perplexity).  One launch; no host read."""
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise TypeError(f"tsne_affinities: scores: expected a cuda tensor, got {getattr(scores, 'device', type(scores))} (no CPU path)")
+    if scores.dtype != torch.float32:
+        raise TypeError(f"tsne_affinities: scores must be float32, got {scores.dtype}")
+    if scores.dim() != 2 or scores.stride(1) != 1:
+        raise ValueError(f"tsne_affinities: scores must be a 2-D view with inner stride 1, got {tuple(scores.shape)} / {scores.stride()}")
+    N, k = scores.shape
+    if N < 1:
+        raise ValueError("tsne_affinities: empty operand (N = 0)")
+    if not 1 <= k <= TSNE_MAX_K:
+        raise ValueError(f"tsne_affinities: k = {k} outside the kernel's range 1 .. {TSNE_MAX_K}")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"tsne_affinities: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    perplexity = float(perplexity)
+    if not 1.0 < perplexity < k:
+        raise ValueError(f"tsne_affinities: perplexity = {perplexity} must lie inside (1, k = {k})")
+    ld = scores.stride(0) if N > 1 else max(k, scores.stride(0))
+    if ld < k:
+        raise ValueError(f"tsne_affinities: row stride {ld} below k = {k}")
+    dev = scores.device
+    out_P = _kmeans_out("tsne_affinities", out_P, "out_P", (N, k), torch.float32, dev)
+    out_beta = _kmeans_out("tsne_affinities", out_beta, "out_beta", (N,), torch.float32, dev)
+    check(lib.cclip_tsne_affinities(_p(scores), c_long(ld), c_long(N), c_int(k), c_float(perplexity), _p(out_P), _p(out_beta),
+                                    _stream()), "cclip_tsne_affinities")
+    return out_P, out_beta
+
+
+def tsne_repulsion_splits(N: int) -> int:
+    """the number of runs the repulsion kernel cuts its j range into: a function of N alone (0 for an N it would refuse)"""
+    return int(lib.cclip_tsne_repulsion_splits(c_long(N)))
+
+
+def tsne_repulsion_workspace(N: int) -> int:
+    """bytes of per-(split, row) partials cclip_tsne_repulsion needs ((3 N splits + ceil(N / 256)) * 4; 0 for an N it would refuse)"""
+    fn = lib.cclip_tsne_repulsion_workspace
+    fn.restype = c_long
+    return int(fn(c_long(N)))
+
+
+def tsne_repulsion(y, *, out_zrow=None, out_rep=None, out_z=None, workspace=None):
+    """The N-body sums of t-SNE (include/cclip_hip.h, cclip_tsne_repulsion): y fp32 [N, 2] contiguous.  With
+    w_ij = 1 / (1 + |y_i - y_j|^2) over all j != i, returns (zrow fp32 [N] = sum_j w_ij, rep fp32 [N, 2] = sum_j w_ij^2
+    (y_i - y_j), z fp32 [1] = sum_i zrow[i]).  No N x N matrix, no float atomics: two calls are bitwise equal.  `workspace`: a
+    float32 device vector of at least tsne_repulsion_workspace(N) bytes to reuse.  Three launches; no host read."""
+    _tsne_f32("tsne_repulsion", y, "y", (None, 2))
+    N = y.shape[0]
+    if N < 1:
+        raise ValueError("tsne_repulsion: empty operand (N = 0)")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"tsne_repulsion: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    dev = y.device
+    out_zrow = _kmeans_out("tsne_repulsion", out_zrow, "out_zrow", (N,), torch.float32, dev)
+    out_rep = _kmeans_out("tsne_repulsion", out_rep, "out_rep", (N, 2), torch.float32, dev)
+    out_z = _kmeans_out("tsne_repulsion", out_z, "out_z", (1,), torch.float32, dev)
+    nbytes = tsne_repulsion_workspace(N)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    else:
+        _tsne_f32("tsne_repulsion", workspace, "workspace", (None,), dev)
+        if workspace.numel() * 4 < nbytes:
+            raise ValueError(f"tsne_repulsion: workspace has {workspace.numel() * 4} bytes, {nbytes} needed")
+    check(lib.cclip_tsne_repulsion(_p(y), c_long(N), _p(out_zrow), _p(out_rep), _p(out_z), _p(workspace),
+                                   c_long(workspace.numel() * 4), _stream()), "cclip_tsne_repulsion")
+    return out_zrow, out_rep, out_z
+
+
+def tsne_step(y, vel, gains, offsets, cols, vals, rep, z, *, exaggeration: float = 1.0, momentum: float = 0.8,
+              learning_rate: float = 200.0, min_gain: float = 0.01, out_y=None, out_kl=None, update: bool = True):
+    """One gradient-descent update of t-SNE (include/cclip_hip.h, cclip_tsne_step): y, vel, gains, rep fp32 [N, 2], the joint
+    probabilities as CSR (offsets int64 [N + 1], cols int32 [nnz], vals fp32 [nnz]), z the fp32 [1] device scalar of
+    tsne_repulsion for this y.  vel and gains are updated in place; returns (y_out, kl_row): y_out = y + vel in a buffer other
+    than y, kl_row fp32 [N] the rows' KL terms with the un-exaggerated P.  update=False only evaluates kl_row (vel, gains and
+    rep may be None; y_out is None).  One launch; no host read."""
+    fname = "tsne_step"
+    _tsne_f32(fname, y, "y", (None, 2))
+    N, dev = y.shape[0], y.device
+    if N < 1:
+        raise ValueError("tsne_step: empty operand (N = 0)")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"tsne_step: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    for t, n, dt, shape in ((offsets, "offsets", torch.int64, (N + 1,)), (cols, "cols", torch.int32, (None,)),
+                            (vals, "vals", torch.float32, (None,))):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != dt:
+            raise TypeError(f"{fname}: {n} must be {dt}, got {t.dtype}")
+        if t.dim() != 1 or (shape[0] is not None and t.numel() != shape[0]) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{fname}: {n} must be a contiguous {dt} {list(shape)} vector on {dev}, got {tuple(t.shape)} on {t.device}")
+    nnz = cols.numel()
+    if vals.numel() != nnz:
+        raise ValueError(f"{fname}: cols has {nnz} entries, vals {vals.numel()}")
+    _tsne_f32(fname, z, "z", (1,), dev)
+    for v, n in ((exaggeration, "exaggeration"), (momentum, "momentum"), (learning_rate, "learning_rate"), (min_gain, "min_gain")):
+        v = float(v)
+        if v != v or v in (float("inf"), float("-inf")) or v < 0:
+            raise ValueError(f"{fname}: {n} must be finite and >= 0, got {v}")
+    if update:
+        for t, n in ((vel, "vel"), (gains, "gains"), (rep, "rep")):
+            _tsne_f32(fname, t, n, (N, 2), dev)
+        out_y = _kmeans_out(fname, out_y, "out_y", (N, 2), torch.float32, dev)
+        if out_y.data_ptr() == y.data_ptr():
+            raise ValueError(f"{fname}: out_y must not be y: other rows still read y")
+    else:
+        if out_y is not None:
+            raise ValueError(f"{fname}: update=False writes no out_y")
+        vel = gains = rep = None
+    out_kl = _kmeans_out(fname, out_kl, "out_kl", (N,), torch.float32, dev)
+    check(lib.cclip_tsne_step(_p(y), _p(vel), _p(gains), c_long(N), _p(offsets), _p(cols), _p(vals), c_long(nnz), _p(rep), _p(z),
+                              c_float(exaggeration), c_float(momentum), c_float(learning_rate), c_float(min_gain), _p(out_y),
+                              _p(out_kl), _stream()), "cclip_tsne_step")
+    return out_y, out_kl
+
+
 SAMPLE_ROWS_MAX_V = 65536
 
 

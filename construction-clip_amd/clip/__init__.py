@@ -12,6 +12,7 @@ from .explain import jet_table, relevance_overlay, text_heat_html  # noqa: F401 
 from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)
 from .retrieval import connected_components, group_split  # noqa: F401  (near-duplicate groups and leak-free held-out splits)
 from .cluster import kmeans, KMeansResult, cluster_purity, name_clusters  # noqa: F401  (spherical k-means of the unlabelled photos)
+from .tsne import tsne, TSNEResult  # noqa: F401  (a 2-D map of the stored embeddings on the kNN graph)
 from .fewshot import CacheClassifier, confusion_matrix  # noqa: F401  (few-shot classification from the stored, labelled embeddings)
 from .probe import LinearProbe, ProbeLossFunction, ProbeFitResult  # noqa: F401  (linear probe: logistic regression on the stored embeddings)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)

@@ -176,6 +176,20 @@ class EmbeddingIndex:
         return labels.long(), scores
 
     @torch.no_grad()
+    def knn_graph(self, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores fp32 [N, k], index int32 [N, k]) on the device: the k most similar OTHER stored rows of every stored row,
+        best first (clip/tsne.py: the top k + 1 of the self-join without the row itself, hence k <= 63).  No host read."""
+        if self._n == 0:
+            raise ValueError("knn_graph: the index is empty")
+        from .tsne import knn_graph
+        return knn_graph(self.features, k)
+
+    def tsne(self, **kw):
+        """A 2-D t-SNE map of the stored rows (clip/tsne.py: csrc/tsne.hip): a `TSNEResult`."""
+        from .tsne import tsne
+        return tsne(self, **kw)
+
+    @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)
 

@@ -493,6 +493,58 @@ int cclip_probe_backward(const void* x, int64_t ldx, int64_t N, int32_t D, const
                          float l2, float* dW, float* db, float* objective, void* workspace, int64_t workspace_bytes,
                          hipStream_t stream);
 
+/* ---- t-SNE of stored embeddings: neighbour probabilities (csrc/tsne.hip, fp32 only) -------------------------------------
+ * scores fp32 [N, k] (row stride ld >= k elements): the similarities of every row's k nearest OTHER unit rows, in any order.
+ * Per row, with d2_j = 2 - 2 s_j (a negative value taken as 0) and diff_j = d2_j - min_j d2_j, all in fp32:
+ *   p_j ~ exp(-beta diff_j), normalised;   H(beta) = log sum_j e_j + beta sum_j diff_j e_j / sum_j e_j   (nats)
+ * beta is found by exactly 100 entropy evaluations and no data-dependent exit: beta = 1, lo = 0, no upper bound; H > log
+ * perplexity sets lo = beta, then beta = (lo + hi) / 2 if an upper bound is known, else 2 beta; otherwise hi = beta and
+ * beta = (lo + hi) / 2.  The beta after the last step is written, and P from it:
+ *   P fp32 [N, k] contiguous, every row summing to 1 within k 2^-24;   beta fp32 [N]
+ * A row whose k distances are equal gets P = 1 / k (beta ends as 2^100); where the m >= perplexity smallest distances are
+ * equal the target cannot be met and P tends to 1 / m on them.  d2 = 0 is legal.  A NaN score makes its row's P and beta NaN
+ * and touches no other row.  One launch, one thread per row, no workspace; nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): a null or misaligned pointer; N <= 0 or N >= 2^31; k < 1 or k > 63; ld < k; perplexity
+ * not inside (1, k). */
+int cclip_tsne_affinities(const float* scores, int64_t ld, int64_t N, int32_t k, float perplexity, float* P, float* beta,
+                          hipStream_t stream);
+
+/* ---- t-SNE: the N-body sums (csrc/tsne.hip) ----------------------------------------------------------------------------
+ * y fp32 [N, 2] contiguous.  With w_ij = 1 / (1 + |y_i - y_j|^2), over ALL j != i (the diagonal adds nothing, to Z included;
+ * a coincident point j != i adds 1 to zrow and 0 to rep):
+ *   zrow[i] = sum_j w_ij  fp32 [N]      rep[i, :] = sum_j w_ij^2 (y_i - y_j)  fp32 [N, 2]      z_sum[0] = sum_i zrow[i]
+ * Order.  Work-groups of 256 rows stream y through LDS in tiles of 512 points; the j range is cut into
+ * cclip_tsne_repulsion_splits(N) <= 16 runs of whole tiles (enough that N = 20 000 fills the machine).  Inside a split four
+ * chains take j = 0, 1, 2, 3 mod 4 of every tile (the last j mod 4 points of a short tile join chain 0) and are added
+ * (c0 + c1) + (c2 + c3); a row's splits are added in ascending order; z_sum is a fixed tree over blocks of 256 rows.  1 / x
+ * is v_rcp_f32 (1 ulp).  No atomics, every choice a function of N alone: two calls on the same y are bitwise equal.
+ * Three launches on `stream`; nothing is read on the host.  workspace: at least cclip_tsne_repulsion_workspace(N) =
+ * (3 N splits + ceil(N / 256)) * 4 bytes (0 for an N the call would refuse), 4-byte aligned, contents meaningless.
+ * CCLIP_ERR_ARG (nothing launched): a null pointer; N <= 0 or N >= 2^31; y or rep not 8-byte aligned, another pointer not
+ * 4-byte aligned; workspace too small. */
+int32_t cclip_tsne_repulsion_splits(int64_t N);
+int64_t cclip_tsne_repulsion_workspace(int64_t N);
+int cclip_tsne_repulsion(const float* y, int64_t N, float* zrow, float* rep, float* z_sum, void* workspace,
+                         int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- t-SNE: one gradient-descent update (csrc/tsne.hip) ----------------------------------------------------------------
+ * y, vel, gains, rep, y_out fp32 [N, 2] contiguous; the symmetric joint probabilities as CSR: offsets int64 [N + 1], cols
+ * int32 [nnz], vals fp32 [nnz] (an empty row is legal); z_sum the device scalar of cclip_tsne_repulsion for the same y.
+ * Per row i, its entries in ascending position, q_ij = 1 + |y_i - y_j|^2:
+ *   att_i  = sum_j (exaggeration P_ij / q_ij) (y_i - y_j)            grad_i = 4 (att_i - rep_i / Z)
+ *   gains  : + 0.2 where (vel > 0) != (grad > 0), else * 0.8; then max(gains, min_gain)       (in place)
+ *   vel    = momentum vel - learning_rate gains grad                                           (in place)
+ *   y_out  = y + vel      - a SECOND buffer: other rows still read y
+ *   kl_row[i] = sum_j P_ij ((log P_ij + log q_ij) + log Z) over the entries with P_ij > 0, P NOT exaggerated   (may be NULL)
+ * With y_out NULL only kl_row is written (vel, gains and rep are not touched and may be NULL).  One launch, one thread per
+ * row, no atomics: bitwise repeatable.  offsets and cols are clamped before use, so no content makes the kernel leave its
+ * arrays.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): null y, offsets or z_sum; null cols / vals with nnz > 0; y_out and kl_row both null;
+ * y_out given with a null vel, gains or rep, or y_out == y; N <= 0 or N >= 2^31; nnz < 0; a misaligned pointer. */
+int cclip_tsne_step(const float* y, float* vel, float* gains, int64_t N, const int64_t* offsets, const int32_t* cols,
+                    const float* vals, int64_t nnz, const float* rep, const float* z_sum, float exaggeration, float momentum,
+                    float learning_rate, float min_gain, float* y_out, float* kl_row, hipStream_t stream);
+
 /* ---- row sampling: temperature, top-k, nucleus and the draw in one launch (csrc/sample_rows.hip, fp32 only) ----
  * One token per row of logits [n, V] (row stride ld >= V elements), for every row r with done[r] == 0:
  *   p        = softmax(row * inv_temperature)
