@@ -1364,6 +1364,117 @@ def tsne_step(y, vel, gains, offsets, cols, vals, rep, z, *, exaggeration: float
     return out_y, out_kl
 
 
+LABEL_SPREAD_MAX_C = 1024
+
+
+def label_spread_groups(C: int) -> int:
+    """the number of edge groups a row's entries are dealt over in label_spread_step: a function of C alone (0 for a C it would refuse)"""
+    return int(lib.cclip_label_spread_groups(c_int(C)))
+
+
+def _label_csr(fname: str, N: int, dev, offsets, cols, vals) -> int:
+    """offsets int64 [N + 1], cols int32 [nnz], vals fp32 [nnz], contiguous on dev; returns nnz"""
+    for t, n, dt, shape in ((offsets, "offsets", torch.int64, (N + 1,)), (cols, "cols", torch.int32, (None,)),
+                            (vals, "vals", torch.float32, (None,))):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != dt:
+            raise TypeError(f"{fname}: {n} must be {dt}, got {t.dtype}")
+        if t.dim() != 1 or (shape[0] is not None and t.numel() != shape[0]) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{fname}: {n} must be a contiguous {dt} {list(shape)} vector on {dev}, got {tuple(t.shape)} on {t.device}")
+    nnz = cols.numel()
+    if vals.numel() != nnz:
+        raise ValueError(f"{fname}: cols has {nnz} entries, vals {vals.numel()}")
+    if N >= 2 ** 31 or nnz >= 2 ** 31:
+        raise NotImplementedError(f"{fname}: N = {N}, nnz = {nnz}; the kernel's indices are int32 (both < 2^31)")
+    return nnz
+
+
+def label_graph_normalize(offsets, cols, vals, *, out_deg=None, out_vals=None):
+    """The normalised graph operator of label spreading (include/cclip_hip.h, cclip_label_graph_normalize): a symmetric
+    non-negative graph as CSR (offsets int64 [N + 1], cols int32 [nnz], vals fp32 [nnz]).  Returns (deg fp32 [N], the row
+    sums; vals_out fp32 [nnz] = (vals r_i) r_j with r = 1 / sqrt(deg), 0 where deg is not > 0).  out_vals may be `vals`.
+    Two launches; no host read."""
+    fname = "label_graph_normalize"
+    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda:
+        raise TypeError(f"{fname}: offsets: expected a cuda tensor, got {getattr(offsets, 'device', type(offsets))} (no CPU path)")
+    N, dev = offsets.numel() - 1, offsets.device
+    if N < 1:
+        raise ValueError(f"{fname}: empty operand (N = {N})")
+    nnz = _label_csr(fname, N, dev, offsets, cols, vals)
+    out_deg = _kmeans_out(fname, out_deg, "out_deg", (N,), torch.float32, dev)
+    out_vals = _kmeans_out(fname, out_vals, "out_vals", (nnz,), torch.float32, dev)
+    check(lib.cclip_label_graph_normalize(_p(offsets), _p(cols), _p(vals), c_long(N), c_long(nnz), _p(out_deg), _p(out_vals),
+                                          _stream()), "cclip_label_graph_normalize")
+    return out_deg, out_vals
+
+
+def _label_F(fname: str, F, n: str = "F"):
+    _tsne_f32(fname, F, n, (None, None))
+    N, C = F.shape
+    if N < 1:
+        raise ValueError(f"{fname}: empty operand (N = 0)")
+    if not 2 <= C <= LABEL_SPREAD_MAX_C:
+        raise ValueError(f"{fname}: C = {C} outside the kernel's range 2 .. {LABEL_SPREAD_MAX_C}")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    return N, C
+
+
+def label_spread_step(F, labels, offsets, cols, vals, alpha: float, class_weight=None, *, out_F=None, out_delta=None,
+                      delta: bool = True):
+    """One iteration of label spreading (include/cclip_hip.h, cclip_label_spread_step): F fp32 [N, C] contiguous, labels int32
+    [N] (< 0 or >= C: unlabelled), S as CSR (label_graph_normalize's vals), class_weight fp32 [C] or None.  Returns (F_out,
+    delta_row): F_out = alpha S F + (1 - alpha) Y in a buffer other than F, delta_row fp32 [N] = max_c |F_out - F| (None with
+    delta=False).  No float atomics, one fixed order: two calls are bitwise equal.  One launch; no host read."""
+    fname = "label_spread_step"
+    N, C = _label_F(fname, F)
+    dev = F.device
+    nnz = _label_csr(fname, N, dev, offsets, cols, vals)
+    for t, n, dt, shape in ((labels, "labels", torch.int32, (N,)), (class_weight, "class_weight", torch.float32, (C,))):
+        if t is None and n == "class_weight":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != dt:
+            raise TypeError(f"{fname}: {n} must be {dt}, got {t.dtype}")
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{fname}: {n} must be a contiguous {dt} {list(shape)} vector on {dev}, got {tuple(t.shape)} on {t.device}")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"{fname}: alpha = {alpha} outside [0, 1]")
+    out_F = _kmeans_out(fname, out_F, "out_F", (N, C), torch.float32, dev)
+    if out_F.data_ptr() == F.data_ptr():
+        raise ValueError(f"{fname}: out_F must not be F: other rows still read F")
+    if delta:
+        out_delta = _kmeans_out(fname, out_delta, "out_delta", (N,), torch.float32, dev)
+    elif out_delta is not None:
+        raise ValueError(f"{fname}: delta=False writes no out_delta")
+    check(lib.cclip_label_spread_step(_p(F), _p(out_F), c_long(N), c_int(C), _p(labels), _p(class_weight), _p(offsets), _p(cols),
+                                      _p(vals), c_long(nnz), c_float(alpha), _p(out_delta), _stream()), "cclip_label_spread_step")
+    return out_F, out_delta
+
+
+def label_spread_finish(F, *, out_dist=None, out_pred=None, out_conf=None, out_cert=None, dist: bool = True):
+    """The read-out of label spreading (include/cclip_hip.h, cclip_label_spread_finish): F fp32 [N, C] contiguous.  Returns
+    (dist fp32 [N, C] = F / row sum, None with dist=False; pred int32 [N], the argmax of F, ties to the lowest class; conf fp32
+    [N] = max of the dist row; cert fp32 [N] = 1 - H(dist row) / log C).  A row that sums to 0: pred -1, conf = cert = 0, dist
+    row 0.  One launch; no host read."""
+    fname = "label_spread_finish"
+    N, C = _label_F(fname, F)
+    dev = F.device
+    if dist:
+        out_dist = _kmeans_out(fname, out_dist, "out_dist", (N, C), torch.float32, dev)
+    elif out_dist is not None:
+        raise ValueError(f"{fname}: dist=False writes no out_dist")
+    out_pred = _kmeans_out(fname, out_pred, "out_pred", (N,), torch.int32, dev)
+    out_conf = _kmeans_out(fname, out_conf, "out_conf", (N,), torch.float32, dev)
+    out_cert = _kmeans_out(fname, out_cert, "out_cert", (N,), torch.float32, dev)
+    check(lib.cclip_label_spread_finish(_p(F), c_long(N), c_int(C), _p(out_dist), _p(out_pred), _p(out_conf), _p(out_cert),
+                                        _stream()), "cclip_label_spread_finish")
+    return out_dist, out_pred, out_conf, out_cert
+
+
 SAMPLE_ROWS_MAX_V = 65536
 
 

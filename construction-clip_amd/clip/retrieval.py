@@ -189,6 +189,12 @@ class EmbeddingIndex:
         from .tsne import tsne
         return tsne(self, **kw)
 
+    def spread_labels(self, labels, **kw):
+        """Spread the labels of a few stored rows over the kNN graph (clip/propagate.py: csrc/label_spread.hip): labels, N
+        integers with a value below 0 for an unlabelled row -> a `LabelSpreadResult`."""
+        from .propagate import spread_labels
+        return spread_labels(self, labels, **kw)
+
     @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)

@@ -79,12 +79,18 @@ def joint_csr(P: torch.Tensor, index: torch.Tensor) -> Tuple[torch.Tensor, torch
     [N, k] (distinct inside a row, never the row itself), as CSR with ascending columns: (offsets int64 [N + 1], cols int32
     [nnz], vals fp32 [nnz]).  Both directions of every edge are keyed row * N + col and sorted; a key occurs at most twice, so
     its sum has one order.  Pure torch on the operands' device; ONE host read, of nnz."""
-    N, k = P.shape
-    dev = P.device
+    return symmetric_csr(P.reshape(-1) / (2.0 * P.shape[0]), index)
+
+
+def symmetric_csr(val: torch.Tensor, index: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A + A^T as CSR with ascending columns, for the directed edges row -> index [N, k] with the weights val [N * k] (row
+    major): the sort `joint_csr` describes, shared with clip/propagate.py.  ONE host read, of nnz."""
+    N, k = index.shape
+    dev = index.device
     row = torch.arange(N, device=dev, dtype=torch.int64)[:, None].expand(N, k).reshape(-1)
     col = index.reshape(-1).to(torch.int64)
     key = torch.cat([row * N + col, col * N + row])
-    val = (P.reshape(-1) / (2.0 * N)).repeat(2)
+    val = val.repeat(2)
     key, order = torch.sort(key, stable=True)
     val = val[order]
     first = torch.ones_like(key, dtype=torch.bool)

@@ -545,6 +545,54 @@ int cclip_tsne_step(const float* y, float* vel, float* gains, int64_t N, const i
                     const float* vals, int64_t nnz, const float* rep, const float* z_sum, float exaggeration, float momentum,
                     float learning_rate, float min_gain, float* y_out, float* kl_row, hipStream_t stream);
 
+/* ---- label spreading: the normalised graph operator (csrc/label_spread.hip, fp32 only) -----------------------------------
+ * A symmetric non-negative graph W as CSR: offsets int64 [N + 1], cols int32 [nnz], vals fp32 [nnz]; an empty row is legal.
+ *   deg[i]      = d_i, the sum of row i's entries in ascending position                                   fp32 [N]
+ *   r_i         = 1.0f / sqrtf(d_i), and 0 where d_i is not > 0 (an empty row, a row of zero weights, a NaN)
+ *   vals_out[e] = (vals[e] * r_i) * r_j  for the entry e of row i with column j: D^-1/2 W D^-1/2           fp32 [nnz]
+ * A row of zero weights gives zeros, never NaN or inf.  vals_out == vals is legal.  offsets are clamped into [0, nnz] and
+ * made non-decreasing per row, cols into [0, N - 1], before use: no content makes a kernel leave its arrays (rows that such
+ * offsets make overlap are written once per row, in no defined order).  Two launches, one thread per row, no atomics:
+ * bitwise repeatable.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): null offsets or deg; null cols, vals or vals_out with nnz > 0; N <= 0, N or nnz >= 2^31,
+ * nnz < 0; a misaligned pointer. */
+int cclip_label_graph_normalize(const int64_t* offsets, const int32_t* cols, const float* vals, int64_t N, int64_t nnz,
+                                float* deg, float* vals_out, hipStream_t stream);
+
+/* ---- label spreading: one iteration (csrc/label_spread.hip) --------------------------------------------------------------
+ * F_in, F_out fp32 [N, C] contiguous, S as CSR (the vals_out above), labels int32 [N], class_weight fp32 [C] or NULL:
+ *   F_out[i, c]  = alpha * sum_j S_ij F_in[j, c] + (1 - alpha) * y_ic
+ *   y_ic         = (class_weight ? class_weight[c] : 1) where labels[i] == c, else 0
+ *   delta_row[i] = max_c |F_out[i, c] - F_in[i, c]|   (may be NULL; NaN if any of the row's differences is)     fp32 [N]
+ * labels[i] < 0 marks an unlabelled row; labels[i] >= C is taken as unlabelled too and indexes nothing.
+ * Order.  A row belongs to a team of G * CW lanes, CW = the power of two >= min(C, 64), G = cclip_label_spread_groups(C) =
+ * min(8, 64 / CW); 256 / (G CW) rows share a work-group.  Edge group g adds the row's entries at positions g, g + G, .. in
+ * ascending order as one fma chain from 0; the G chains are added in the tree ((g0 + g1) + (g2 + g3)) + ((g4 + g5) +
+ * (g6 + g7)).  For C > 64 a lane holds 2 (C <= 128) or 4 classes, 64 apart, and C > 256 takes one pass over the row per 256
+ * classes.  The label term is fma(-alpha, w, w), the result fma(alpha, sum, label term).  The order depends on C and on the
+ * row's length alone; no atomics: two launches are bitwise equal.  offsets and cols are clamped as above.
+ * One launch; nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): null F_in, F_out, labels or offsets; F_out == F_in (other rows still read F_in); null
+ * cols or vals with nnz > 0; N <= 0, N or nnz >= 2^31, nnz < 0; C < 2 or C > 1024; alpha outside [0, 1] or NaN; a misaligned
+ * pointer. */
+int32_t cclip_label_spread_groups(int32_t C);
+int cclip_label_spread_step(const float* F_in, float* F_out, int64_t N, int32_t C, const int32_t* labels,
+                            const float* class_weight, const int64_t* offsets, const int32_t* cols, const float* vals,
+                            int64_t nnz, float alpha, float* delta_row, hipStream_t stream);
+
+/* ---- label spreading: the read-out (csrc/label_spread.hip) -----------------------------------------------------------------
+ * F fp32 [N, C] contiguous, non-negative.  Per row, z = sum_c F_ic (lane c of CW adds classes c, c + CW, .. ascending, then a
+ * fixed tree):
+ *   z > 0:   dist[i, :] = p = F / z;  pred[i] = the argmax of F itself, the lowest class among equal values;  conf[i] = max p;
+ *            cert[i] = 1 - H(p) / log C,  H = -sum_c p log p  with 0 log 0 = 0
+ *   z == 0:  (no labelled row reaches the row) pred = -1, conf = cert = 0, dist row 0: no division, no NaN.  A z below 0
+ *            (F is not non-negative) is treated the same.
+ *   a NaN in the row: pred = -1, conf, cert and the dist row NaN; no other row is touched.
+ * dist fp32 [N, C] may be NULL; pred int32 [N], conf, cert fp32 [N].  One launch, no atomics; nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched): null F, pred, conf or cert; N <= 0 or N >= 2^31; C < 2 or C > 1024; a misaligned pointer. */
+int cclip_label_spread_finish(const float* F, int64_t N, int32_t C, float* dist, int32_t* pred, float* conf, float* cert,
+                              hipStream_t stream);
+
 /* ---- row sampling: temperature, top-k, nucleus and the draw in one launch (csrc/sample_rows.hip, fp32 only) ----
  * One token per row of logits [n, V] (row stride ld >= V elements), for every row r with done[r] == 0:
  *   p        = softmax(row * inv_temperature)
