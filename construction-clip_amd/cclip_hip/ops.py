@@ -1109,6 +1109,127 @@ def kmeans_update(x, assign, K: int, prev_c, *, out_c=None, out_norm=None, check
     return out_c, out_norm, counts
 
 
+CORESET_FROM_PARTIALS, CORESET_SCAN_ONLY = -1, -2        # the `centre` modes of cclip_coreset_step (include/cclip_hip.h)
+
+
+def coreset_blocks(N: int) -> int:
+    """work-groups of one cclip_coreset_step launch = keys per partial buffer: min(1024, ceil(N / 64)); 0 for an N it would refuse"""
+    fn = lib.cclip_coreset_blocks
+    fn.restype = c_int
+    return int(fn(c_long(N)))
+
+
+def coreset_workspace(N: int) -> int:
+    """bytes of the two partial-key buffers cclip_coreset_greedy alternates between (2 * coreset_blocks(N) * 8)"""
+    fn = lib.cclip_coreset_workspace
+    fn.restype = c_long
+    return int(fn(c_long(N)))
+
+
+def _coreset_state(fname: str, x, mind, owner, weight):
+    """The argument checks coreset_step and coreset_greedy share: x as for kmeans_assign, mind fp32 [N], owner int32 [N] and
+    weight fp32 [N] or None, contiguous on x's device.  Returns (N, D, ldx)."""
+    _req16(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"{fname}: x must be a 2-D view with inner stride 1, got {tuple(x.shape)} / {x.stride()}")
+    N, D = x.shape
+    if N < 1:
+        raise ValueError(f"{fname}: empty operand (N = {N})")
+    if D % 32 or not 32 <= D <= KMEANS_MAX_D:
+        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {KMEANS_MAX_D}")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    for t, n, dt in ((mind, "mind", torch.float32), (owner, "owner", torch.int32), (weight, "weight", torch.float32)):
+        if t is None and n == "weight":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != dt or t.device != x.device or tuple(t.shape) != (N,) or not t.is_contiguous():
+            raise ValueError(f"{fname}: {n} must be a contiguous {dt} [{N}] tensor on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return N, D, _ld16(fname, x, "x")
+
+
+def _coreset_keys(fname: str, t, n: str, shape, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != dev or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{fname}: {n} must be a contiguous torch.int64 {list(shape)} tensor on {dev}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    return t
+
+
+def coreset_step(x, mind, owner, partial_out, *, centre: Optional[int] = None, partial_in=None, scan_only: bool = False, weight=None,
+                 out_pick=None, out_radius=None):
+    """One k-centre greedy pick over the unit 16-bit rows x [N, D] (inner stride 1, row stride a multiple of 8 elements, 16-byte
+    aligned), in place on the state mind fp32 [N] (cosine distance to the nearest centre so far, +inf = none) and owner int32 [N]
+    (that centre's row, -1 = none, owner[i] == i = the row is a centre).  partial_in / partial_out: two different int64
+    [coreset_blocks(N)] key buffers (a key: the order image of weight * mind above ~row; 0 = no eligible row).  The centre c is
+    `centre` (an int in [0, N)), or - centre None - the row of the largest key of partial_in; scan_only=True takes no centre and
+    updates nothing.  With a centre: pick = c, radius = mind[c] before the update, mind[c] = 0, owner[c] = c, and every other
+    non-centre row with 1 - <x_i, x_c> strictly below mind[i] takes that distance and owner c.  partial_out then holds every
+    work-group's best eligible key: owner[i] != i and weight[i] > 0 where weight fp32 [N] is given (a NaN weight is never
+    eligible), larger weight * mind first, equal values to the lower row.  Returns (pick int32 [1], radius fp32 [1]) - pick -1
+    and radius NaN when partial_in holds no eligible row - or (None, None) for scan_only.  D % 32 == 0, 32 <= D <= 1024,
+    N < 2^31.  No atomics: two calls from equal states are bitwise equal.  Enqueues one launch; no host read."""
+    N, D, ldx = _coreset_state("coreset_step", x, mind, owner, weight)
+    dev, P = x.device, coreset_blocks(N)
+    _coreset_keys("coreset_step", partial_out, "partial_out", (P,), dev)
+    if scan_only:
+        if centre is not None:
+            raise ValueError("coreset_step: scan_only takes no centre")
+        mode = CORESET_SCAN_ONLY
+    elif centre is None:
+        if partial_in is None:
+            raise ValueError("coreset_step: without a centre the pick comes from partial_in")
+        mode = CORESET_FROM_PARTIALS
+    else:
+        mode = int(centre)
+        if not 0 <= mode < N:
+            raise ValueError(f"coreset_step: centre = {centre} outside [0, {N})")
+    if partial_in is not None:
+        _coreset_keys("coreset_step", partial_in, "partial_in", (P,), dev)
+        if partial_in.data_ptr() == partial_out.data_ptr():
+            raise ValueError("coreset_step: partial_in and partial_out must be different buffers (other work-groups still read the old keys)")
+    if not scan_only:
+        out_pick = _kmeans_out("coreset_step", out_pick, "out_pick", (1,), torch.int32, dev)
+        out_radius = _kmeans_out("coreset_step", out_radius, "out_radius", (1,), torch.float32, dev)
+    else:
+        out_pick = out_radius = None
+    fn = _fn("cclip_coreset_step", x)
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(weight), _p(mind), _p(owner), c_int(mode), _p(partial_in), _p(partial_out),
+             _p(out_pick), _p(out_radius), _stream()), "cclip_coreset_step")
+    return out_pick, out_radius
+
+
+def coreset_greedy(x, mind, owner, m: int, *, first: Optional[int] = None, workspace=None, weight=None, out_picks=None,
+                   out_radius=None):
+    """m k-centre greedy picks (m launches of `coreset_step`, enqueued by one native call) on the state of `coreset_step`.
+    workspace: int64 [2, coreset_blocks(N)], the two key buffers; pick t reads workspace[t % 2] and writes the other.  first an
+    int in [0, N): pick 0 takes that row; first None: workspace[0] already holds the keys of the state (a scan_only step into
+    it).  Returns (picks int32 [m], radius fp32 [m], workspace): bit for bit what m single steps give; the state's keys end in
+    workspace[m % 2].  Once no eligible row is left the picks are -1 with radius NaN.  m == 0 launches nothing.  No host read."""
+    N, D, ldx = _coreset_state("coreset_greedy", x, mind, owner, weight)
+    dev, P = x.device, coreset_blocks(N)
+    m = int(m)
+    if not 0 <= m <= N:
+        raise ValueError(f"coreset_greedy: m = {m} outside [0, {N}]")
+    if first is None:
+        if workspace is None:
+            raise ValueError("coreset_greedy: without a first row workspace[0] must hold the keys of the state")
+        mode = CORESET_FROM_PARTIALS
+    else:
+        mode = int(first)
+        if not 0 <= mode < N:
+            raise ValueError(f"coreset_greedy: first = {first} outside [0, {N})")
+    if workspace is None:
+        workspace = torch.zeros(2, P, device=dev, dtype=torch.int64)
+    _coreset_keys("coreset_greedy", workspace, "workspace", (2, P), dev)
+    out_picks = _kmeans_out("coreset_greedy", out_picks, "out_picks", (m,), torch.int32, dev)
+    out_radius = _kmeans_out("coreset_greedy", out_radius, "out_radius", (m,), torch.float32, dev)
+    fn = _fn("cclip_coreset_greedy", x)
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(weight), _p(mind), _p(owner), c_int(mode), c_long(m), _p(out_picks),
+             _p(out_radius), _p(workspace), c_long(workspace.numel() * 8), _stream()), "cclip_coreset_greedy")
+    return out_picks, out_radius, workspace
+
+
 PROBE_MAX_C = 256
 PROBE_MAX_D = 1024
 

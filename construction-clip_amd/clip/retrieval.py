@@ -195,6 +195,12 @@ class EmbeddingIndex:
         from .propagate import spread_labels
         return spread_labels(self, labels, **kw)
 
+    def coreset(self, m: int, **kw):
+        """k-centre greedy selection of m stored rows, from the labelled ones if any (clip/coreset.py: csrc/coreset.hip): a
+        `CoresetResult`.  The rows are used as stored, not copied."""
+        from .coreset import select_coreset
+        return select_coreset(self, m, **kw)
+
     @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)

@@ -443,6 +443,61 @@ int cclip_kmeans_update(const void* x, int64_t ldx, int64_t N, int32_t D, const 
                         int64_t K, const void* prev_c, int64_t ldp, void* out_c, int64_t ldo, float* out_norm,
                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- coreset selection: one k-centre greedy pick per launch (csrc/coreset.hip) ------------------------------------------
+ * State, all on the device: x [N, D] unit bf16 rows (fp16 in the twin) under the contract of cclip_kmeans_assign (row stride
+ * ldx in elements, inner stride 1, 16-byte aligned); weight fp32 [N] or NULL (= 1); mind fp32 [N], the row's cosine distance
+ * 1 - <x_i, x_c> to its nearest centre so far, +inf = none yet; owner int32 [N], that centre's row, -1 = none, owner[i] == i
+ * marks a row that is itself a centre; partial_in / partial_out, two DIFFERENT buffers of P = cclip_coreset_blocks(N) 64-bit
+ * keys each (8-byte aligned).  A key holds the order-preserving image of weight[i] * mind[i] in the high word and ~i in the
+ * low one.  Order as in cclip_similarity_topk: larger = better, equal fp32 values (-0 == +0) go to the LOWER row, a NaN value
+ * ranks below every number; key 0 = no eligible row.  A row is eligible if owner[i] != i and its weight, where given, is > 0
+ * (a NaN weight is not); its value may be +inf.
+ * `centre` picks the mode:
+ *   centre >= 0                        that row is the centre c (the first pick without seeds); partial_in is not read
+ *   CCLIP_CORESET_FROM_PARTIALS (-1)   c = the row of the largest of the P keys of partial_in, clamped into [0, N - 1] before
+ *                                      use.  All keys 0: pick_out[0] = -1, radius_out[0] = NaN, mind and owner untouched.
+ *   CCLIP_CORESET_SCAN_ONLY (-2)       no centre and no update (after seeding); pick_out / radius_out are not written
+ * With a centre: pick_out[0] = c and radius_out[0] = mind[c] as it was BEFORE this launch (the covering radius of everything
+ * chosen before this pick), then mind[c] = 0, owner[c] = c; every other row that is not a centre with d = 1 - s < mind[i]
+ * takes mind[i] = d, owner[i] = c - strictly smaller, so an equal distance keeps the earlier centre, and a NaN d changes
+ * nothing.  In every mode partial_out[b] then receives the best key among the eligible rows of work-group b (0 if none).
+ * The dot.  s is ONE fixed fp32 order that depends on D alone: a row belongs to a team of T lanes, T = the power of two
+ * >= D / 8 capped at 64; lane l adds the exact products of elements 8 l .. 8 l + 7 in ascending order from the first, for
+ * D > 512 the products of elements 512 + 8 l .. likewise and that sum to the first; the team then adds by an xor butterfly
+ * over lane distances 1, 2, .. T / 2.  No fused multiply-add.  A row's new mind and owner are a function of (x_i, x_c, old
+ * mind, old owner) alone - not of N, of the row's position or of the grid.
+ * One launch of cclip_coreset_blocks(N) = min(1024, ceil(N / 64)) work-groups (0 for an N the call would refuse), rows dealt
+ * by a grid stride.  The work-groups agree on c without talking, because the maximum of distinct keys has no order: no
+ * atomics, no spin-wait, no cross-work-group barrier; two launches are bitwise equal.  c is the only index taken from device
+ * memory.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): null x, mind, owner or partial_out; N <= 0 or N >= 2^31; D < 32, D % 32
+ * or D > 1024; ldx below D or not a multiple of 8; x not 16-byte aligned; centre < -2 or >= N; null partial_in with
+ * CCLIP_CORESET_FROM_PARTIALS; partial_in == partial_out; null pick_out or radius_out unless CCLIP_CORESET_SCAN_ONLY; a
+ * misaligned fp32 / int32 array or a partial buffer not 8-byte aligned. */
+#define CCLIP_CORESET_FROM_PARTIALS (-1)
+#define CCLIP_CORESET_SCAN_ONLY (-2)
+int32_t cclip_coreset_blocks(int64_t N);
+int cclip_coreset_step(const void* x, int64_t ldx, int64_t N, int32_t D, const float* weight, float* mind, int32_t* owner,
+                       int32_t centre, const void* partial_in, void* partial_out, int32_t* pick_out, float* radius_out,
+                       hipStream_t stream);
+
+/* ---- coreset selection: m picks from one call (csrc/coreset.hip) -----------------------------------------------------------
+ * The m launches of cclip_coreset_step enqueued from one C loop: pick t reads the keys of partial[t & 1] and writes
+ * partial[(t + 1) & 1], partial[j] = workspace + j * P keys; picks int32 [m] and radius fp32 [m] receive pick_out /
+ * radius_out of launch t at position t.  first >= 0: launch 0 takes that row as its centre; first ==
+ * CCLIP_CORESET_FROM_PARTIALS: partial[0] already holds the keys of the state (a CCLIP_CORESET_SCAN_ONLY step into it, or
+ * partial_out of an earlier pick).  The outputs and the state equal those of m single steps bit for bit; after the call the
+ * keys of the state are in partial[m & 1].  Once no eligible row is left the remaining picks are -1 with radius NaN.  m == 0
+ * launches nothing.  workspace: at least cclip_coreset_workspace(N) = 2 * cclip_coreset_blocks(N) * 8 bytes (0 for an N the
+ * call would refuse), 8-byte aligned device memory the caller owns.  Nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): the cases of cclip_coreset_step for x, ldx, N, D, weight, mind and
+ * owner; m < 0 or m > N; first < -1 or >= N; null, misaligned or too small workspace; null picks or radius with m > 0; a
+ * misaligned picks or radius. */
+int64_t cclip_coreset_workspace(int64_t N);
+int cclip_coreset_greedy(const void* x, int64_t ldx, int64_t N, int32_t D, const float* weight, float* mind, int32_t* owner,
+                         int32_t first, int64_t m, int32_t* picks, float* radius, void* workspace, int64_t workspace_bytes,
+                         hipStream_t stream);
+
 /* ---- linear probe: logistic regression on stored embeddings (csrc/embed_probe.hip) -------------------------------------
  * x [N, D] bf16 (fp16 in the twin), row stride ldx in elements, inner stride 1; W fp32 [C, D] contiguous; bias fp32 [C] or NULL
  * (= 0); labels int32 [N] or NULL (= every row ignored), a label < 0 or >= C means the row is ignored; row_weight fp32 [N] or
@@ -979,6 +1034,12 @@ int cclip_kmeans_assign_f16(const void* x, int64_t ldx, int64_t N, const void* c
 int cclip_kmeans_update_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const int32_t* order, const int32_t* seg_off,
                             int64_t K, const void* prev_c, int64_t ldp, void* out_c, int64_t ldo, float* out_norm,
                             void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cclip_coreset_step_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* weight, float* mind, int32_t* owner,
+                           int32_t centre, const void* partial_in, void* partial_out, int32_t* pick_out, float* radius_out,
+                           hipStream_t stream);
+int cclip_coreset_greedy_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* weight, float* mind, int32_t* owner,
+                             int32_t first, int64_t m, int32_t* picks, float* radius, void* workspace, int64_t workspace_bytes,
+                             hipStream_t stream);
 int cclip_probe_forward_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* W, const float* bias, int32_t C,
                             const int32_t* labels, const float* row_weight, float* lse, float* loss, int32_t* pred,
                             float* logits, void* workspace, int64_t workspace_bytes, hipStream_t stream);
