@@ -1230,6 +1230,88 @@ def coreset_greedy(x, mind, owner, m: int, *, first: Optional[int] = None, works
     return out_picks, out_radius, workspace
 
 
+def mst_workspace(N: int) -> int:
+    """bytes of scratch cclip_mst_boruvka needs (32 N + 256: the row keys, the component keys, the parents, two label buffers,
+    the round flags); 0 for an N it would refuse"""
+    fn = lib.cclip_mst_workspace
+    fn.restype = c_long
+    return int(fn(c_long(N)))
+
+
+def mreach_nearest_splits(N: int) -> int:
+    """gallery splits of one cclip_mreach_nearest launch (a function of N alone); 0 for an N it would refuse"""
+    fn = lib.cclip_mreach_nearest_splits
+    fn.restype = c_int
+    return int(fn(c_long(N)))
+
+
+def _mreach_operands(fname: str, x, core):
+    """The argument checks mreach_nearest and mst_boruvka share: x as for kmeans_assign, core fp32 [N] contiguous on x's device.
+    Returns (N, D, ldx)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise TypeError(f"{fname}: x: expected a cuda tensor, got {getattr(x, 'device', type(x))} (no CPU path)")
+    _req16(x, "x")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"{fname}: x must be a 2-D view with inner stride 1, got {tuple(x.shape)} / {x.stride()}")
+    N, D = x.shape
+    if N < 1:
+        raise ValueError(f"{fname}: empty operand (N = {N})")
+    if D % 32 or not 32 <= D <= KMEANS_MAX_D:
+        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {KMEANS_MAX_D}")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    if not isinstance(core, torch.Tensor) or not core.is_cuda:
+        raise TypeError(f"{fname}: core: expected a cuda tensor, got {getattr(core, 'device', type(core))} (no CPU path)")
+    if core.dtype != torch.float32 or core.device != x.device or tuple(core.shape) != (N,) or not core.is_contiguous():
+        raise ValueError(f"{fname}: core must be a contiguous torch.float32 [{N}] tensor on {x.device}, got {core.dtype} "
+                         f"{tuple(core.shape)} on {core.device}")
+    return N, D, _ld16(fname, x, "x")
+
+
+def mreach_nearest(x, core, comp, *, out=None):
+    """For every row i of the unit 16-bit rows x [N, D] (inner stride 1, row stride a multiple of 8 elements, 16-byte aligned)
+    the closest row j outside i's component under mutual-reachability similarity m = min(<x_i, x_j>, core[i], core[j]): core
+    fp32 [N], comp int32 [N] (any values: only compared).  Returns keys int64 [N]: the order image of m in the high word above
+    ~j, the largest over the rows j with comp[j] != comp[i] - larger m first, equal m to the lower j, a NaN m below every
+    number - or 0 where no such row exists.  The score carries the bits similarity_topk returns for the pair; the N x N matrix
+    is never formed.  Integer atomics only where the gallery is split: two calls are bitwise equal.  D % 32 == 0,
+    32 <= D <= 1024, N < 2^31.  No host read."""
+    N, D, ldx = _mreach_operands("mreach_nearest", x, core)
+    if not isinstance(comp, torch.Tensor) or not comp.is_cuda:
+        raise TypeError(f"mreach_nearest: comp: expected a cuda tensor, got {getattr(comp, 'device', type(comp))} (no CPU path)")
+    if comp.dtype != torch.int32 or comp.device != x.device or tuple(comp.shape) != (N,) or not comp.is_contiguous():
+        raise ValueError(f"mreach_nearest: comp must be a contiguous torch.int32 [{N}] tensor on {x.device}, got {comp.dtype} "
+                         f"{tuple(comp.shape)} on {comp.device}")
+    out = _kmeans_out("mreach_nearest", out, "out", (N,), torch.int64, x.device)
+    fn = _fn("cclip_mreach_nearest", x)
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(core), _p(comp), _p(out), _stream()), "cclip_mreach_nearest")
+    return out
+
+
+def mst_boruvka(x, core, *, workspace=None):
+    """The maximum spanning tree of the complete graph on the rows of x under mutual-reachability similarity (x, core as for
+    `mreach_nearest`), unique under the strict total order "larger m, then smaller min(i, j), then smaller max(i, j)".
+    Returns (u int32 [N], v int32 [N], m fp32 [N]): N - 1 slots hold an edge with its m, exactly one holds u = v = -1 and
+    m = NaN (N == 1: that slot alone).  ceil(log2 N) Boruvka rounds are enqueued by one native call; a device flag ends the
+    work once one component is left.  workspace: an int64 tensor of at least mst_workspace(N) bytes.  Two calls are bitwise
+    equal.  No host read."""
+    N, D, ldx = _mreach_operands("mst_boruvka", x, core)
+    dev = x.device
+    nbytes = mst_workspace(N)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
+    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int64 or workspace.device != dev or
+            not workspace.is_contiguous() or workspace.numel() * 8 < nbytes):
+        raise ValueError(f"mst_boruvka: workspace must be a contiguous torch.int64 tensor of at least {nbytes} bytes on {dev}")
+    u = torch.empty(N, device=dev, dtype=torch.int32)
+    v = torch.empty(N, device=dev, dtype=torch.int32)
+    m = torch.empty(N, device=dev, dtype=torch.float32)
+    fn = _fn("cclip_mst_boruvka", x)
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(core), _p(u), _p(v), _p(m), _p(workspace), c_long(workspace.numel() * 8),
+             _stream()), "cclip_mst_boruvka")
+    return u, v, m
+
+
 PROBE_MAX_C = 256
 PROBE_MAX_D = 1024
 

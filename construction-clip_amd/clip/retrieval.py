@@ -201,6 +201,17 @@ class EmbeddingIndex:
         from .coreset import select_coreset
         return select_coreset(self, m, **kw)
 
+    def mst(self, min_samples: int = 5):
+        """The maximum spanning tree of the stored rows under mutual-reachability similarity (clip/hdbscan.py: csrc/mst.hip):
+        an `MSTResult`.  The rows are used as stored, not copied."""
+        from .hdbscan import mutual_reachability_mst
+        return mutual_reachability_mst(self, min_samples)
+
+    def hdbscan(self, **kw):
+        """HDBSCAN of the stored rows: density clusters without a k, noise labelled -1 (clip/hdbscan.py): an `HDBSCANResult`."""
+        from .hdbscan import hdbscan
+        return hdbscan(self, **kw)
+
     @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)

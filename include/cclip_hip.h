@@ -498,6 +498,42 @@ int cclip_coreset_greedy(const void* x, int64_t ldx, int64_t N, int32_t D, const
                          int32_t first, int64_t m, int32_t* picks, float* radius, void* workspace, int64_t workspace_bytes,
                          hipStream_t stream);
 
+/* ---- mutual-reachability nearest row outside the own component (csrc/mst.hip) -------------------------------------------
+ * x [N, D] unit bf16 rows (fp16 in the twin) under the contract of cclip_kmeans_assign (row stride ldx in elements, inner
+ * stride 1, 16-byte aligned); core fp32 [N]; comp int32 [N]; keys 64-bit [N], 8-byte aligned.  With s[i, j] the fp32 MFMA
+ * score (one chain over d = 0, 32, ..: the bits cclip_similarity_topk returns for the pair) and
+ *   m[i, j] = min(s[i, j], core[i], core[j])     taken on the order images: -0 == +0, a NaN operand gives NaN, the lowest
+ * keys[i] = the largest key over the rows j with comp[j] != comp[i], a key being the order image of m in the high word and ~j
+ * in the low one: larger m first, equal m to the LOWER j (the order of cclip_similarity_topk); 0 = no such row.  comp is
+ * only compared, never used as an index: any int32 value is legal.  core = +inf leaves the plain similarity.
+ * The N x N matrix is never written.  The grid runs over blocks of rows x cclip_mreach_nearest_splits(N) gallery splits; with
+ * more than one split keys is zeroed on `stream` first and the splits meet in a 64-bit integer atomicMax, whose result has
+ * no order: the output is a pure function of (x, core, comp), two launches are bitwise equal.  No workspace, no float
+ * atomics, nothing is read on the host.
+ * CCLIP_ERR_ARG (nothing launched, keys untouched): null x, core, comp or keys; N <= 0 or N >= 2^31; D < 32, D % 32 or
+ * D > 1024; ldx below D or not a multiple of 8; x not 16-byte aligned; a misaligned core, comp or keys. */
+int32_t cclip_mreach_nearest_splits(int64_t N);
+int cclip_mreach_nearest(const void* x, int64_t ldx, int64_t N, int32_t D, const float* core, const int32_t* comp, void* keys,
+                         hipStream_t stream);
+
+/* ---- maximum spanning tree under mutual-reachability similarity: Boruvka, one call (csrc/mst.hip) ------------------------
+ * x, core as above.  The tree is the maximum spanning tree of the complete graph on the rows under the strict total order
+ *   {i, j} before {k, l}:  larger m (order images);  equal m: smaller min(i, j);  then smaller max(i, j)
+ * which is unique - a pure function of the score bits and core, not of the grid, the splits or the launch order.
+ * u, v int32 [N], m fp32 [N]: N - 1 slots hold an edge (u[k] != v[k], both in [0, N), m[k] = m[u[k], v[k]]) and exactly one
+ * slot holds u = v = -1, m = NaN.  Which slot an edge lands in is fixed too (the name of the component that chose it).
+ * ceil(log2 N) rounds are enqueued from one C loop: the nearest kernel above, two integer-atomic reductions to every
+ * component's best outgoing edge, the hooks, the relabelling.  A device flag marks "one component left"; the kernels of
+ * later rounds return at once.  Rounds alternate between two label buffers.  Every index a kernel takes from memory is
+ * clamped.  Nothing is read on the host; N == 1 only writes the empty slot.
+ * workspace: at least cclip_mst_workspace(N) = 32 N + 256 bytes (0 for an N the call would refuse), 8-byte aligned device
+ * memory the caller owns; its contents before and after are meaningless.
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): the cases of cclip_mreach_nearest for x, ldx, N, D and core; null or
+ * misaligned u, v or m; null, misaligned or too small workspace. */
+int64_t cclip_mst_workspace(int64_t N);
+int cclip_mst_boruvka(const void* x, int64_t ldx, int64_t N, int32_t D, const float* core, int32_t* u, int32_t* v, float* m,
+                      void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- linear probe: logistic regression on stored embeddings (csrc/embed_probe.hip) -------------------------------------
  * x [N, D] bf16 (fp16 in the twin), row stride ldx in elements, inner stride 1; W fp32 [C, D] contiguous; bias fp32 [C] or NULL
  * (= 0); labels int32 [N] or NULL (= every row ignored), a label < 0 or >= C means the row is ignored; row_weight fp32 [N] or
@@ -1040,6 +1076,10 @@ int cclip_coreset_step_f16(const void* x, int64_t ldx, int64_t N, int32_t D, con
 int cclip_coreset_greedy_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* weight, float* mind, int32_t* owner,
                              int32_t first, int64_t m, int32_t* picks, float* radius, void* workspace, int64_t workspace_bytes,
                              hipStream_t stream);
+int cclip_mreach_nearest_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* core, const int32_t* comp,
+                             void* keys, hipStream_t stream);
+int cclip_mst_boruvka_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* core, int32_t* u, int32_t* v, float* m,
+                          void* workspace, int64_t workspace_bytes, hipStream_t stream);
 int cclip_probe_forward_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const float* W, const float* bias, int32_t C,
                             const int32_t* labels, const float* row_weight, float* lse, float* loss, int32_t* pred,
                             float* logits, void* workspace, int64_t workspace_bytes, hipStream_t stream);
