@@ -47,8 +47,6 @@
 
 namespace CCLIP_NS {
 
-typedef unsigned long long u64;
-
 struct CoresetArgs {
   const bf16* x; long ldx;
   int N, D;
@@ -59,16 +57,12 @@ struct CoresetArgs {
   int* pick; float* radius;
 };
 
-__device__ __forceinline__ u64 cs_shfl_xor64(u64 v, int o) {
-  const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
-  return ((u64)hi << 32) | lo;
-}
 __device__ __forceinline__ u64 cs_max(u64 a, u64 b) { return a > b ? a : b; }
 
 // the maximum of one key per thread over the work-group, in every thread (red: 4 entries of LDS, free again on return)
 __device__ __forceinline__ u64 cs_block_max(u64 v, u64* red, int tid) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = cs_max(v, cs_shfl_xor64(v, o));
+  for (int o = 32; o > 0; o >>= 1) v = cs_max(v, shfl_xor64(v, o));
   if ((tid & 63) == 0) red[tid >> 6] = v;
   __syncthreads();
   v = cs_max(cs_max(red[0], red[1]), cs_max(red[2], red[3]));

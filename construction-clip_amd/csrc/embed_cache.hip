@@ -10,8 +10,8 @@
 //
 // Score independent of position.  Every score is ONE accumulator chain over d = 0, 32, 64 .. in that order (the tile multiply
 // of score_tiles.h), whichever tile, split, lane or kernel variant its rows land on.
-// Sum independent of Q.  The stored rows are cut into splits by a rule that depends on Np alone (topk_splits' rule of
-// embed_topk.hip at one query block; rows per split a multiple of 64).  Inside a split, lane li of a 16-lane group meets the
+// Sum independent of Q.  The stored rows are cut into splits by a rule that depends on Np alone (gallery_splits of
+// score_sweep.h at one query block; rows per split a multiple of 64).  Inside a split, lane li of a 16-lane group meets the
 // rows n0 + li, n0 + li + 16, .. of a class in ascending order and adds their terms to one register per query row; when the
 // class ends the 16 lanes are combined by a fixed xor butterfly (both partners compute the same bits) and phase 2 adds the
 // splits that hold live rows of the class in ascending order.  None of this depends on how many queries are scored, on which
@@ -26,7 +26,7 @@
 // Phase 2 (cache_merge_kernel): one thread per (query, class).
 // The kernels index class_off / class_len with clamped cursors only: whatever the two arrays hold, no access leaves g, the
 // workspace or out.  That their content is a legal layout is checked where they are still host data (cclip_hip/ops.py).
-#include "score_tiles.h"
+#include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
 // the sums below are written out operation by operation: no fused multiply-add may be formed from them, so that every
@@ -46,16 +46,6 @@ struct CacheArgs {
   float beta;
   float* ws;                                      // [Q][splits][C]
 };
-
-// the class whose segment holds stored row n: the last c with class_off[c] <= n (c < C whatever the array holds)
-__device__ __forceinline__ int class_of_row(const int* __restrict__ off, int C, int n) {
-  int lo = 1, hi = C;                             // the smallest j in 1 .. C with off[j] > n
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] > n) hi = mid; else lo = mid + 1;
-  }
-  return lo - 1;
-}
 
 // <KSMAX, MT, GT> as in score_tiles.h: MT query tiles of 16 rows per wave, GT stored rows per tile
 template <int KSMAX, int MT, int GT>
@@ -90,7 +80,7 @@ __global__ __launch_bounds__(256) void cache_partial_kernel(const CacheArgs a) {
     }
 
   // (all wave-uniform) the class cursor: segment [.., seg_end), live rows [.., live_end); open = rs holds terms of class c
-  int c = class_of_row(a.class_off, C, n0);
+  int c = segment_of(a.class_off, C, n0);
   int seg_end = a.class_off[c + 1], live_end = a.class_off[c] + a.class_len[c];
   bool open = false;
 
@@ -166,31 +156,16 @@ __global__ __launch_bounds__(256) void cache_merge_kernel(const float* __restric
   out[i] = s;
 }
 
-// splits from Np alone (a query's sums must not depend on Q): topk_splits' rule of embed_topk.hip at one query block, i.e.
-// up to 512 work-groups per query block while a split keeps at least 256 rows
-static inline void cache_splits(int64_t Np, int* splits, int* rows_per_split) {
-  int64_t s = (Np + 255) / 256;
-  if (s > 512) s = 512;
-  if (s < 1) s = 1;
-  const int64_t rows = ((Np + s - 1) / s + 63) / 64 * 64;
-  s = (Np + rows - 1) / rows;                     // no empty split
-  *splits = (int)s; *rows_per_split = (int)rows;
-}
-
-template <int KSMAX, int MT, int GT>
-static int cache_launch(const CacheArgs& a, hipStream_t stream) {
-  const long nqb = ((long)a.Q + 64 * MT - 1) / (64 * MT);
-  if (nqb * a.splits > 0x7fffffffL) return CCLIP_ERR_ARG;
-  const size_t lds = (size_t)2 * GT * a.D * 2;    // two tiles; the class sums live in registers, so C costs no LDS
-  return score_launch(cache_partial_kernel<KSMAX, MT, GT>, (unsigned)(nqb * a.splits), lds, a, stream);
-}
+// splits from Np alone (a query's sums must not depend on Q): the rule of cclip_similarity_topk at one query block, i.e. up to
+// 512 work-groups per query block while a split keeps at least 256 rows
+static inline void cache_splits(int64_t Np, int* splits, int* rows_per_split) { gallery_splits(Np, 1, 512, 256, splits, rows_per_split); }
 
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
 
 #ifndef CCLIP_F16
 extern "C" int64_t cclip_cache_affinity_workspace(int32_t Q, int64_t Np, int32_t C) {
-  if (Q <= 0 || Np <= 0 || Np > 0x7fffffffLL || (Np & 15) || C < 1 || C > CACHE_MAX_C) return 0;
+  if (Q <= 0 || !score_rows_ok(Np) || (Np & 15) || C < 1 || C > CACHE_MAX_C) return 0;
   int splits, rows;
   cache_splits(Np, &splits, &rows);
   return (int64_t)Q * splits * C * 4;
@@ -202,8 +177,8 @@ extern "C" int CCLIP_FN(cclip_cache_affinity)(const void* q, int64_t ldq, int32_
                                                const int32_t* exclude, float* out, void* workspace, int64_t workspace_bytes,
                                                hipStream_t stream) {
   if (!q || !g || !class_off || !class_len || !out || !workspace) return CCLIP_ERR_ARG;
-  if (Q <= 0 || Np <= 0 || Np > 0x7fffffffLL || (Np & 15) || C < 1 || C > CACHE_MAX_C) return CCLIP_ERR_ARG;
-  if (D < 32 || !score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
+  if (Q <= 0 || !score_rows_ok(Np) || (Np & 15) || C < 1 || C > CACHE_MAX_C) return CCLIP_ERR_ARG;
+  if (!score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
   if (((uintptr_t)workspace & 3) || ((uintptr_t)out & 3) || ((uintptr_t)class_off & 3) || ((uintptr_t)class_len & 3) ||
       ((uintptr_t)exclude & 3))
     return CCLIP_ERR_ARG;
@@ -215,12 +190,10 @@ extern "C" int CCLIP_FN(cclip_cache_affinity)(const void* q, int64_t ldq, int32_
   a.beta = beta;
   a.ws = (float*)workspace;
   if (workspace_bytes < (int64_t)Q * a.splits * C * 4) return CCLIP_ERR_ARG;
-  const bool wide = Q > 64;                       // two query tiles per wave halve the LDS reads per MFMA (same bits either way)
-  int st;
-  if (D <= 128) st = wide ? cache_launch<4, 2, 64>(a, stream) : cache_launch<4, 1, 64>(a, stream);
-  else if (D <= 512) st = wide ? cache_launch<16, 2, 64>(a, stream) : cache_launch<16, 1, 64>(a, stream);
-  else if (D <= 768) st = wide ? cache_launch<24, 2, 32>(a, stream) : cache_launch<24, 1, 32>(a, stream);
-  else st = cache_launch<32, 1, 32>(a, stream);
+  const int st = score_dispatch<true>(D, Q > 64, [&](auto s) {
+    using S = decltype(s);                        // two tiles; the class sums live in registers, so C costs no LDS
+    return sweep_launch(cache_partial_kernel<S::KSMAX, S::MT, S::GT>, a, Q, S::MT, S::GT, D, a.splits, 2, 0, stream);
+  });
   if (st != CCLIP_OK) return st;
   const long cells = (long)Q * C;
   hipLaunchKernelGGL(cache_merge_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, (const float*)a.ws, Q, C,

@@ -35,7 +35,7 @@
 // the variant depends on anything but Np and D: two launches are bitwise equal.
 // The kernels index class_off / class_len with clamped cursors only: whatever the two arrays hold, no access leaves q, g, dA,
 // the workspace or dG.
-#include "score_tiles.h"
+#include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
 // the sums below are written out operation by operation: no fused multiply-add may be formed from them, so that every
@@ -58,16 +58,6 @@ struct CacheBwdArgs {
   const float* amax; int nparts;                  // partial maxima of |dA|
   float* dG;                                      // [Np][D]
 };
-
-// the class whose segment holds stored row n: the last c with class_off[c] <= n (c < C whatever the array holds)
-__device__ __forceinline__ int bwd_class_of_row(const int* __restrict__ off, int C, int n) {
-  int lo = 1, hi = C;                             // the smallest j in 1 .. C with off[j] > n
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] > n) hi = mid; else lo = mid + 1;
-  }
-  return lo - 1;
-}
 
 // A-operand fragment of X^T (columns 16 dt .. 16 dt + 15 of the tile image as MFMA rows) over 8 tile rows given as two 4-row
 // blocks: attention_tiles.h's frag_tr on score_tiles.h's image.  Needs EXEC all ones.
@@ -117,7 +107,7 @@ __global__ __launch_bounds__(256) void cache_bwd_kernel(const CacheBwdArgs a) {
   // (all wave-uniform) the class of the wave's rows and its live end; a wave without live rows only helps to load
   int c = 0, live_end = 0;
   if (n0 < Np) {
-    c = bwd_class_of_row(a.class_off, C, n0);
+    c = segment_of(a.class_off, C, n0);
     const int first = a.class_off[c];
     live_end = (n0 >= first) ? first + a.class_len[c] : 0;
   }
@@ -239,8 +229,8 @@ extern "C" int CCLIP_FN(cclip_cache_affinity_bwd)(const void* q, int64_t ldq, in
                                                    float beta, const int32_t* exclude, const float* dA, float* dG, void* workspace,
                                                    int64_t workspace_bytes, hipStream_t stream) {
   if (!q || !g || !class_off || !class_len || !dA || !dG || !workspace) return CCLIP_ERR_ARG;
-  if (Q <= 0 || Np <= 0 || Np > 0x7fffffffLL || (Np & 15) || C < 1 || C > CACHE_MAX_C) return CCLIP_ERR_ARG;
-  if (D < 32 || !score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
+  if (Q <= 0 || !score_rows_ok(Np) || (Np & 15) || C < 1 || C > CACHE_MAX_C) return CCLIP_ERR_ARG;
+  if (!score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
   if (((uintptr_t)workspace & 3) || ((uintptr_t)dA & 3) || ((uintptr_t)dG & 15) || ((uintptr_t)class_off & 3) ||
       ((uintptr_t)class_len & 3) || ((uintptr_t)exclude & 3))
     return CCLIP_ERR_ARG;

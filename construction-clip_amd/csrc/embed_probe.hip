@@ -20,7 +20,8 @@
 // tile of score_tiles.h whose two sub-tiles are the two chains.
 //
 // Forward (probe_fwd_kernel): the geometry of kmeans_assign_kernel.  Grid = blocks of 64 * MT rows of x, a work-group keeps its
-// rows as A fragments and streams all class tiles through two LDS buffers (one barrier per tile).  Lane (li, g) meets class
+// rows as A fragments and streams all class tiles through two LDS buffers (one barrier per tile; its own loop, see
+// score_sweep.h).  Lane (li, g) meets class
 // 16 t + li of every tile and keeps per row a running (max, sum) pair, the label's logit and the best (score_key, ~class) key;
 // the 16 lanes of a group are combined by a fixed xor butterfly whose two partners compute the same bits.  So a row's outputs
 // depend on neither N nor the row's position nor MT.  Ties in pred go to the LOWER class, NaN ranks lowest (score_key.h).
@@ -38,7 +39,7 @@
 // further blocks reduce loss[] and W^2 by a fixed tree; probe_objective_kernel finishes the scalar.
 // Slots, tiles per part and every other choice are functions of (N, C, D) alone (probe_geom); no atomics, no fused
 // multiply-add: two calls are bitwise equal.  Every index taken from labels is compared, never used as an address.
-#include "score_tiles.h"
+#include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
 // the sums below are written out operation by operation: no fused multiply-add may be formed from them
@@ -60,7 +61,7 @@ struct ProbeGeom {
 };
 
 static inline bool probe_geom(int64_t N, int64_t C, int32_t D, ProbeGeom& g) {
-  if (N <= 0 || N > 0x7fffffffLL || C < 2 || C > PROBE_MAX_C || D < 32 || (D & 31) || D > 1024) return false;
+  if (!score_rows_ok(N) || C < 2 || C > PROBE_MAX_C || D < 32 || (D & 31) || D > 1024) return false;
   g.cpad = (int)((C + 15) / 16 * 16);
   const int nb = g.cpad / 16;
   g.cbw = nb >= 3 ? 4 : nb;                       // class blocks of 16 per work-group
@@ -92,11 +93,6 @@ __global__ __launch_bounds__(256) void probe_prep_kernel(const float* __restrict
   const long row = (long)(c >> 4) * 32 + (c & 15);
   img[row * D + d] = hi;
   img[(row + 16) * D + d] = lo;
-}
-
-__device__ __forceinline__ u64 probe_shfl64(u64 v, int o) {
-  const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
-  return ((u64)hi << 32) | lo;
 }
 
 // row_weight into [0, 1]; NaN fails the comparison and becomes 0
@@ -191,7 +187,7 @@ __global__ __launch_bounds__(256) void probe_fwd_kernel(const ProbeFwdArgs a) {
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) {
         const float pm = __shfl_xor(mm, o, 64), ps = __shfl_xor(ss, o, 64), pz = __shfl_xor(zz, o, 64);
-        const u64 pk = probe_shfl64(k1, o);
+        const u64 pk = shfl_xor64(k1, o);
         const float mn = fmaxf(mm, pm);
         const float ta = ss * expf(mm - mn), tb = ps * expf(pm - mn);
         ss = ta + tb;                             // commutative: the partner adds the same two numbers
@@ -427,13 +423,6 @@ static void probe_prep_launch(const float* W, int C, int D, const ProbeGeom& g, 
   hipLaunchKernelGGL(probe_prep_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, W, C, D, g.cpad, (bf16*)ws);
 }
 
-template <int KSMAX, int MT>
-static int probe_fwd_launch(const ProbeFwdArgs& a, hipStream_t stream) {
-  const long nblk = ((long)a.N + 64 * MT - 1) / (64 * MT);        // < 2^26
-  const size_t lds = (size_t)2 * 32 * a.D * 2;                    // two tiles
-  return score_launch(probe_fwd_kernel<KSMAX, MT>, (unsigned)nblk, lds, a, stream);
-}
-
 template <int KSMAX, int DS, bool PRE>
 static int probe_bwd_launch(const ProbeBwdArgs& a, const ProbeGeom& g, hipStream_t stream) {
   const size_t lds = (size_t)2 * PROBE_RT * a.D * 2;
@@ -485,11 +474,10 @@ extern "C" int CCLIP_FN(cclip_probe_forward)(const void* x, int64_t ldx, int64_t
   a.N = (int)N; a.C = C; a.D = D;
   a.bias = bias; a.labels = labels; a.rw = row_weight;
   a.lse = lse; a.loss = loss; a.pred = pred; a.logits = logits;
-  const bool wide = N > 64;                       // two row tiles per wave halve the LDS reads per MFMA (same bits either way)
-  int st;
-  if (D <= 128) st = wide ? probe_fwd_launch<4, 2>(a, stream) : probe_fwd_launch<4, 1>(a, stream);
-  else if (D <= 512) st = wide ? probe_fwd_launch<16, 2>(a, stream) : probe_fwd_launch<16, 1>(a, stream);
-  else st = probe_fwd_launch<32, 1>(a, stream);
+  const int st = score_dispatch<false>(D, N > 64, [&](auto s) {                  // (tiles of 32 image rows on every rung)
+    using S = decltype(s);
+    return sweep_launch(probe_fwd_kernel<S::KSMAX, S::MT>, a, N, S::MT, 32, D, 1, 2, 0, stream);
+  });
   if (st != CCLIP_OK) return st;
   return cclip_launch_status();
 }

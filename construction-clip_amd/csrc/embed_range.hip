@@ -3,10 +3,10 @@
 // is >= threshold, as CSR: the gallery rows of query i (ascending) and their scores at offsets[i] .. offsets[i+1].
 // The Q x N matrix is never written.  A NaN score is never a hit (s >= t is false); +inf is one.
 //
-// Score.  The streamed-tile core of score_tiles.h with the instantiations of embed_topk.hip: ONE accumulator chain over
-// d = 0, 32, 64 .. per pair, so a pair's score bits equal those cclip_similarity_topk returns for it.
+// Score.  The tile loop, the instantiations and the split rule of embed_topk.hip on the parts of score_tiles.h: ONE
+// accumulator chain over d = 0, 32, 64 .. per pair, so a pair's score bits equal those cclip_similarity_topk returns for it.
 //
-// Two passes over one grid (query blocks x gallery splits, topk_splits' rule), no atomics, no LDS lists:
+// Two passes over one grid (query blocks x gallery splits), no atomics, no LDS lists:
 //   count: every (query row, split) counts its hits into counts[Q][splits]           (range_kernel<.., false>)
 //   scan:  the caller's exclusive scan over the Q * splits counts, row-major: a row's splits are adjacent, so the scanned
 //          value of (row, split) is where that segment starts and that of (row, 0) is offsets[row]
@@ -18,7 +18,7 @@
 //
 // Self-join (q == g, Q == N): only pairs n > i.  A tile whose rows all lie at or below the work-group's first query row
 // is not loaded; a work-group whose whole split does writes zero counts and leaves.
-#include "score_tiles.h"
+#include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
@@ -138,32 +138,17 @@ __global__ __launch_bounds__(256) void range_kernel(const RangeArgs a) {
   }
 }
 
-// gallery splits from (Q, N) alone: topk_splits' rule of embed_topk.hip (two work-groups per CU while a split keeps at
-// least 256 rows; rows per split a multiple of 64; no empty split)
+// gallery splits from (Q, N) alone: the rule of cclip_similarity_topk
 static inline void range_splits(int64_t Q, int64_t N, int* splits, int* rows_per_split) {
-  const int64_t nqb = (Q + 63) / 64;
-  int64_t want = (512 + nqb - 1) / nqb, most = (N + 255) / 256;
-  int64_t s = want < most ? want : most;
-  if (s < 1) s = 1;
-  int64_t rows = ((N + s - 1) / s + 63) / 64 * 64;
-  s = (N + rows - 1) / rows;
-  *splits = (int)s; *rows_per_split = (int)rows;
-}
-
-template <int KSMAX, int MT, int GT, bool EMIT>
-static int range_launch(const RangeArgs& a, hipStream_t stream) {
-  const int nqb = (a.Q + 64 * MT - 1) / (64 * MT);
-  const size_t lds = (size_t)GT * a.D * 2;        // one tile
-  return score_launch(range_kernel<KSMAX, MT, GT, EMIT>, (unsigned)(nqb * a.splits), lds, a, stream);
+  gallery_splits(N, (Q + 63) / 64, 512, 256, splits, rows_per_split);
 }
 
 template <bool EMIT>
 static int range_dispatch(const RangeArgs& a, hipStream_t stream) {
-  const bool wide = a.Q > 64;                     // the instantiations of cclip_similarity_topk
-  int st;
-  if (a.D <= 128) st = wide ? range_launch<4, 2, 64, EMIT>(a, stream) : range_launch<4, 1, 64, EMIT>(a, stream);
-  else if (a.D <= 512) st = wide ? range_launch<16, 2, 64, EMIT>(a, stream) : range_launch<16, 1, 64, EMIT>(a, stream);
-  else st = range_launch<32, 1, 32, EMIT>(a, stream);
+  const int st = score_dispatch<false>(a.D, a.Q > 64, [&](auto s) {             // the instantiations of cclip_similarity_topk
+    using S = decltype(s);
+    return sweep_launch(range_kernel<S::KSMAX, S::MT, S::GT, EMIT>, a, a.Q, S::MT, S::GT, a.D, a.splits, 1, 0, stream);
+  });
   return st != CCLIP_OK ? st : cclip_launch_status();
 }
 
@@ -171,14 +156,13 @@ static int range_dispatch(const RangeArgs& a, hipStream_t stream) {
 static bool range_args(RangeArgs& a, const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
                        float threshold, int32_t self_join) {
   if (!q || !g) return false;
-  if (Q <= 0 || N <= 0 || N > 0x7fffffffLL) return false;
-  if (D <= 0 || !score_operands_ok(q, ldq, g, ldg, D)) return false;
+  if (Q <= 0 || !score_rows_ok(N)) return false;
+  if (!score_operands_ok(q, ldq, g, ldg, D)) return false;
   if (self_join != 0 && self_join != 1) return false;
   if (self_join && (q != g || ldq != ldg || (int64_t)Q != N)) return false;
   a.q = (const bf16*)q; a.g = (const bf16*)g; a.ldq = ldq; a.ldg = ldg;
   a.Q = Q; a.N = (int)N; a.D = D; a.self_join = self_join; a.thr = threshold;
   range_splits(Q, N, &a.splits, &a.rows_per_split);
-  if (((int64_t)(Q + 63) / 64) * a.splits > 0x7fffffffLL) return false;
   a.counts = nullptr; a.start = nullptr; a.cap = 0; a.index = nullptr; a.scores = nullptr;
   return true;
 }
@@ -188,7 +172,7 @@ using namespace CCLIP_NS;
 
 #ifndef CCLIP_F16
 extern "C" int64_t cclip_similarity_range_workspace(int32_t Q, int64_t N) {
-  if (Q <= 0 || N <= 0 || N > 0x7fffffffLL) return 0;
+  if (Q <= 0 || !score_rows_ok(N)) return 0;
   int splits, rows;
   range_splits(Q, N, &splits, &rows);
   return (int64_t)Q * splits * 4;

@@ -10,16 +10,14 @@
 // Score independent of position.  Every score is ONE accumulator chain over d = 0, 32, 64 .. in that order, whichever tile,
 // split or lane the gallery row lands on, and whichever kernel variant runs; identical gallery rows give identical bits.
 //
-// Phase 1 (topk_partial_kernel): grid = query blocks x gallery splits.  A work-group (4 waves) owns 64 * MT query rows, wave w
-// the rows 16 MT w ..; their A fragments stay in registers.  The split's gallery rows stream through LDS in tiles of GT rows
-// (the swizzled [row][D] image, the tile mover and the multiply of score_tiles.h: one tile buffer, two barriers per tile); the
-// next tile's 16-byte global loads are in flight while the current one is multiplied.
+// Phase 1 (topk_partial_kernel): grid = query blocks x gallery splits; the parts of score_tiles.h in the kernel's own loop
+// with one tile buffer and two barriers per tile (see score_sweep.h for why not its loop).
 // The query is on the accumulator rows: lane (li, g) holds query rows 4g .. 4g+3 against gallery row 16 st + li of sub-tile st.
 // Each lane keeps its rows' running k-th-best score; a sub-tile none of whose scores beats it costs four compares and one
 // wave-uniform branch.  A score that does goes, one at a time, into the row's sorted list in LDS (all 64 lanes shift the list
 // in one step); about k ln(N / k) such inserts per row.  The lists go to the workspace: [Q][splits][k] keys.
 // Phase 2 (topk_merge_kernel): one work-group per query runs the same insert over its splits * k keys and decodes them.
-#include "score_tiles.h"
+#include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
 namespace CCLIP_NS {
@@ -169,20 +167,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const u64* __restrict__
 
 // gallery splits from (Q, N) alone: enough work-groups for two per CU while a split keeps at least 256 rows
 static inline void topk_splits(int64_t Q, int64_t N, int* splits, int* rows_per_split) {
-  const int64_t nqb = (Q + 63) / 64;
-  int64_t want = (512 + nqb - 1) / nqb, most = (N + 255) / 256;
-  int64_t s = want < most ? want : most;
-  if (s < 1) s = 1;
-  int64_t rows = ((N + s - 1) / s + 63) / 64 * 64;
-  s = (N + rows - 1) / rows;                      // no empty split
-  *splits = (int)s; *rows_per_split = (int)rows;
-}
-
-template <int KSMAX, int MT, int GT>
-static int topk_launch(const TopkArgs& a, hipStream_t stream) {
-  const int nqb = (a.Q + 64 * MT - 1) / (64 * MT);
-  const size_t lds = (size_t)GT * a.D * 2 + (size_t)4 * 16 * MT * a.k * 8;   // one tile, the four waves' lists
-  return score_launch(topk_partial_kernel<KSMAX, MT, GT>, (unsigned)(nqb * a.splits), lds, a, stream);
+  gallery_splits(N, (Q + 63) / 64, 512, 256, splits, rows_per_split);
 }
 
 }  // namespace CCLIP_NS
@@ -190,7 +175,7 @@ using namespace CCLIP_NS;
 
 #ifndef CCLIP_F16
 extern "C" int64_t cclip_similarity_topk_workspace(int32_t Q, int64_t N, int32_t k) {
-  if (Q <= 0 || N <= 0 || N > 0x7fffffffLL || k <= 0) return 0;
+  if (Q <= 0 || !score_rows_ok(N) || k <= 0) return 0;
   int splits, rows;
   topk_splits(Q, N, &splits, &rows);
   return (int64_t)Q * splits * k * 8;
@@ -201,8 +186,8 @@ extern "C" int CCLIP_FN(cclip_similarity_topk)(const void* q, int64_t ldq, int32
                                                 int32_t D, int32_t k, float* scores, int32_t* index, void* workspace,
                                                 int64_t workspace_bytes, hipStream_t stream) {
   if (!q || !g || !scores || !index || !workspace) return CCLIP_ERR_ARG;
-  if (Q <= 0 || N <= 0 || N > 0x7fffffffLL || k < 1 || k > 64 || k > N) return CCLIP_ERR_ARG;
-  if (D <= 0 || !score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
+  if (Q <= 0 || !score_rows_ok(N) || k < 1 || k > 64 || k > N) return CCLIP_ERR_ARG;
+  if (!score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
   if (((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3) || ((uintptr_t)index & 3)) return CCLIP_ERR_ARG;
   TopkArgs a;
   a.q = (const bf16*)q; a.g = (const bf16*)g; a.ldq = ldq; a.ldg = ldg;
@@ -210,12 +195,10 @@ extern "C" int CCLIP_FN(cclip_similarity_topk)(const void* q, int64_t ldq, int32
   topk_splits(Q, N, &a.splits, &a.rows_per_split);
   a.ws = (u64*)workspace;
   if (workspace_bytes < (int64_t)Q * a.splits * k * 8) return CCLIP_ERR_ARG;
-  if (((int64_t)(Q + 63) / 64) * a.splits > 0x7fffffffLL) return CCLIP_ERR_ARG;
-  const bool wide = Q > 64;                       // two query tiles per wave halve the LDS reads per MFMA
-  int st;
-  if (D <= 128) st = wide ? topk_launch<4, 2, 64>(a, stream) : topk_launch<4, 1, 64>(a, stream);
-  else if (D <= 512) st = wide ? topk_launch<16, 2, 64>(a, stream) : topk_launch<16, 1, 64>(a, stream);
-  else st = topk_launch<32, 1, 32>(a, stream);
+  const int st = score_dispatch<false>(D, Q > 64, [&](auto s) {
+    using S = decltype(s);                        // one tile, then the four waves' lists
+    return sweep_launch(topk_partial_kernel<S::KSMAX, S::MT, S::GT>, a, Q, S::MT, S::GT, D, a.splits, 1, (size_t)4 * 16 * S::MT * k * 8, stream);
+  });
   if (st != CCLIP_OK) return st;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), 0, stream, (const u64*)a.ws, a.splits, k, scores, index);
   return cclip_launch_status();

@@ -21,7 +21,7 @@
 // registers while tile t is multiplied and lands in the other buffer, so a tile costs one barrier.  Rows beyond R and
 // columns beyond V are loaded clamped (never out of bounds) and masked: they contribute nothing.
 // Phase 2 (lm_merge_kernel): one thread per row folds its partials in split order.
-#include "score_tiles.h"
+#include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
 // the reductions below are written out operation by operation: no fused multiply-add may be formed from them, so that every
@@ -177,15 +177,6 @@ __global__ __launch_bounds__(256) void lm_merge_kernel(const LmPartial* __restri
   if (pred_logit) pred_logit[row] = key_score((unsigned)(key >> 32));
 }
 
-template <int KSMAX, int MT, int GT>
-static int lm_launch(const LmArgs& a, hipStream_t stream) {
-  static_assert(LM_SPLIT_COLS % GT == 0, "a split is a whole number of tiles");
-  const long nrb = ((long)a.R + 64 * MT - 1) / (64 * MT);
-  if (nrb * a.splits > 0x7fffffffL) return CCLIP_ERR_ARG;
-  const size_t lds = (size_t)2 * GT * a.D * 2;    // two tiles
-  return score_launch(lm_partial_kernel<KSMAX, MT, GT>, (unsigned)(nrb * a.splits), lds, a, stream);
-}
-
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
 
@@ -201,7 +192,7 @@ extern "C" int CCLIP_FN(cclip_lm_head_score)(const void* x, int64_t ldx, int32_t
                                               float* pred_logit, void* workspace, hipStream_t stream) {
   if (!x || !w || !labels || !logp || !workspace) return CCLIP_ERR_ARG;
   if (R <= 0 || V <= 0) return CCLIP_ERR_ARG;
-  if (D < 32 || !score_operands_ok(x, ldx, w, ldw, D)) return CCLIP_ERR_ARG;
+  if (!score_operands_ok(x, ldx, w, ldw, D)) return CCLIP_ERR_ARG;
   if (((uintptr_t)workspace & 7) || ((uintptr_t)logp & 3) || ((uintptr_t)lse & 3) || ((uintptr_t)pred & 3) ||
       ((uintptr_t)pred_logit & 3) || ((uintptr_t)labels & 3))
     return CCLIP_ERR_ARG;
@@ -211,12 +202,11 @@ extern "C" int CCLIP_FN(cclip_lm_head_score)(const void* x, int64_t ldx, int32_t
   a.splits = (V + LM_SPLIT_COLS - 1) / LM_SPLIT_COLS;
   a.labels = labels;
   a.ws = (LmPartial*)workspace;
-  const bool wide = R > 64;                       // two row tiles per wave halve the LDS reads per MFMA (same bits either way)
-  int st;
-  if (D <= 128) st = wide ? lm_launch<4, 2, 64>(a, stream) : lm_launch<4, 1, 64>(a, stream);
-  else if (D <= 512) st = wide ? lm_launch<16, 2, 64>(a, stream) : lm_launch<16, 1, 64>(a, stream);
-  else if (D <= 768) st = wide ? lm_launch<24, 2, 32>(a, stream) : lm_launch<24, 1, 32>(a, stream);
-  else st = lm_launch<32, 1, 32>(a, stream);
+  const int st = score_dispatch<true>(D, R > 64, [&](auto s) {
+    using S = decltype(s);
+    static_assert(LM_SPLIT_COLS % S::GT == 0, "a split is a whole number of tiles");
+    return sweep_launch(lm_partial_kernel<S::KSMAX, S::MT, S::GT>, a, R, S::MT, S::GT, D, a.splits, 2, 0, stream);
+  });
   if (st != CCLIP_OK) return st;
   hipLaunchKernelGGL(lm_merge_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, (const LmPartial*)a.ws, R, V, a.splits,
                      labels, ignore_index, logp, lse, pred, pred_logit);

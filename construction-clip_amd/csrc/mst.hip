@@ -12,10 +12,9 @@
 // For a fixed row i the order reads "larger m, equal m to the lower j", which is the usual key score_key(m) << 32 | ~j.
 //
 // mreach_nearest_kernel (the N^2 kernel), grid = blocks of 64 * MT rows x gallery splits: per row i the best key over the rows
-// j with comp[j] != comp[i] (so j != i), 0 = no such row.  The core of embed_kmeans.hip's assign kernel on score_tiles.h: the
-// block's rows stay in registers as A fragments, the split's rows of the SAME matrix stream through two LDS tiles (one
-// barrier per tile) with comp / core of the next tile's rows in flight beside them.  A lane keeps a running maximum per row
-// it owns; the 16 lanes of a group combine by an xor butterfly.  One split: lane 0 stores.  Several: the output is zeroed
+// j with comp[j] != comp[i] (so j != i), 0 = no such row.  The sweep of score_sweep.h with two tile buffers: the split's rows
+// of the SAME matrix are the streamed ones, with comp / core of the next tile's rows in flight beside them (the fetch hook).
+// A lane keeps a running maximum per row it owns; the 16 lanes of a group combine by group_max_key.  One split: lane 0 stores.  Several: the output is zeroed
 // first and lane 0 takes atomicMax on the 64-bit key - an integer maximum of distinct keys has no order, so the output is the
 // same bits for any split and any launch order.  comp is only compared, never used as an index.
 //
@@ -36,7 +35,7 @@
 // comp_in != comp_out: a late work-group of relabel still reads the labels an early one would otherwise have rewritten (the
 // partial_in != partial_out rule of coreset.hip).  Every index taken from memory is clamped into [0, N - 1] before use.
 // Integer atomics only, no float atomics: two calls are bitwise equal.
-#include "score_tiles.h"
+#include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
 #define MST_FLAGS 64                              // int32 flags in the workspace: rounds + 1 <= 32 used
@@ -52,38 +51,19 @@ struct NearestArgs {
   int splits, rows_per_split;                     // rows_per_split is a multiple of 64
 };
 
-__device__ __forceinline__ u64 mst_shfl_xor64(u64 v, int o) {
-  const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
-  return ((u64)hi << 32) | lo;
-}
-
 // <KSMAX, MT, GT> as in score_tiles.h: MT tiles of 16 operand rows per wave, GT streamed rows per tile
 template <int KSMAX, int MT, int GT>
 __global__ __launch_bounds__(256) void mreach_nearest_kernel(const NearestArgs a) {
   constexpr int NST = GT / 16;                    // sub-tiles of 16 streamed rows
   extern __shared__ __attribute__((aligned(16))) char lds[];
   if (a.live && *a.live == 0) return;             // (grid-uniform, before any barrier)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 15, g = lane >> 4;
+  const SweepCtx<MT> ctx(a.D, a.N, a.N, a.splits, a.rows_per_split);
+  const int li = ctx.li;
   const long N = a.N;
-  const TileGeom geo(a.D);
-  const int tilebytes = GT * geo.rowbytes;
-
-  const int split = blockIdx.x % a.splits;
-  const long n0 = (long)split * a.rows_per_split;                 // (n0 < N: the launcher leaves no split empty)
-  const long n1 = min(N, n0 + a.rows_per_split);
-  const long ntiles = (n1 - n0 + GT - 1) / GT;
-
-  // rows are counted from the block's first row, so that no int sum comes near 2^31 whatever N is
-  const long row0 = (long)(blockIdx.x / a.splits) * (64 * MT);    // (row0 < N: the grid has no empty block)
-  const int last = (int)min(N - 1 - row0, (long)(64 * MT - 1));   // the block's last live row, block-relative
-  const bf16* xb = a.x + row0 * a.ldx;
-  const int q0 = wave * (16 * MT);
-  const bool active = q0 <= last;                 // (wave-uniform) a wave without rows only helps to load
 
   bf16x8 af[MT][KSMAX];
-  load_a_frags<KSMAX, MT>(af, xb, a.ldx, q0, last, geo.nks, lane);
-  // per-row state of this lane, rows q0 + 16 mt + 4 g + r: the row's component, its core key, the best key so far
+  ctx.load_a(af, a.x, a.ldx);
+  // per-row state of this lane: the row's component, its core key, the best key so far
   int ci[MT][4];
   unsigned kci[MT][4];
   u64 b1[MT][4];
@@ -91,7 +71,7 @@ __global__ __launch_bounds__(256) void mreach_nearest_kernel(const NearestArgs a
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const long row = row0 + min(q0 + 16 * mt + 4 * g + r, last);  // (a clamped row is loaded, never written)
+      const long row = ctx.row_clamped(mt, r);    // (a clamped row is loaded, never written)
       ci[mt][r] = a.comp[row];
       kci[mt][r] = score_key(a.core[row]);
       b1[mt][r] = 0ull;
@@ -100,7 +80,7 @@ __global__ __launch_bounds__(256) void mreach_nearest_kernel(const NearestArgs a
   // comp and the core key of the streamed rows this lane meets in a tile: rows base + 16 st + li, clamped to N - 1
   int cj[NST], cjn[NST];
   unsigned kcj[NST], kcjn[NST];
-  auto side = [&](long base, int (&c)[NST], unsigned (&k)[NST]) {
+  auto side = [&](long base, int (&c)[NST], unsigned (&k)[NST]) CCLIP_SWEEP_INLINE {
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
       const long j = min(base + 16 * st + li, N - 1);
@@ -108,81 +88,46 @@ __global__ __launch_bounds__(256) void mreach_nearest_kernel(const NearestArgs a
       k[st] = score_key(a.core[j]);
     }
   };
+  side(ctx.n0, cj, kcj);
 
-  TileMover<KSMAX, GT> mover(geo, tid);
-  mover.fetch(a.x + n0 * a.ldx, a.ldx, 0, (int)min(N - 1 - n0, (long)(GT - 1)));      // rows >= N are clamped (never selected below)
-  side(n0, cj, kcj);
-  int buf = 0;
-  for (long t = 0; t < ntiles; ++t, buf ^= 1) {
-    const long base = n0 + t * GT;
-    char* Xs = lds + buf * tilebytes;
-    mover.store(Xs);
-    __syncthreads();                              // tile `base` is whole; every wave has left the tile before last (this buffer's next content)
-    if (t + 1 < ntiles) {
-      mover.fetch(a.x + (base + GT) * a.ldx, a.ldx, 0, (int)min(N - 1 - (base + GT), (long)(GT - 1)));
-      side(base + GT, cjn, kcjn);
-    }
-    if (active) {
-      f32x4 acc[MT][NST];
-      tile_multiply<KSMAX, MT, GT>(acc, af, Xs, geo, lane);
+  // rows >= N are clamped (never selected below)
+  stream_tiles<KSMAX, MT, GT>(
+      ctx, af, a.x, a.ldx, ctx.n0, ctx.n1, N - 1, lds,
+      [&](long base, f32x4 (&acc)[MT][NST]) CCLIP_SWEEP_INLINE {
+        for_subtiles<GT>(ctx, base, ctx.n1, [&](int st, long nb, bool okc) CCLIP_SWEEP_INLINE {
+          const unsigned low = ~(unsigned)(nb + li);
 #pragma unroll
-      for (int st = 0; st < NST; ++st) {
-        const long nb = base + 16 * st;
-        if (nb >= n1) continue;                   // (wave-uniform)
-        const bool okc = nb + li < n1;
-        const unsigned low = ~(unsigned)(nb + li);
+          for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
+            for (int r = 0; r < 4; ++r) {
+              const unsigned k = min(min(score_key(acc[mt][st][r]), kci[mt][r]), kcj[st]);
+              const bool valid = okc && cj[st] != ci[mt][r];
+              const u64 cand = valid ? (((u64)k << 32) | low) : 0ull;                 // selected, not multiplied
+              b1[mt][r] = cand > b1[mt][r] ? cand : b1[mt][r];
+            }
+        });
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const unsigned k = min(min(score_key(acc[mt][st][r]), kci[mt][r]), kcj[st]);
-            const bool valid = okc && cj[st] != ci[mt][r];
-            const u64 cand = valid ? (((u64)k << 32) | low) : 0ull;                   // selected, not multiplied
-            b1[mt][r] = cand > b1[mt][r] ? cand : b1[mt][r];
-          }
-      }
-    }
-#pragma unroll
-    for (int st = 0; st < NST; ++st) { cj[st] = cjn[st]; kcj[st] = kcjn[st]; }
-  }
-  if (!active) return;
+        for (int st = 0; st < NST; ++st) { cj[st] = cjn[st]; kcj[st] = kcjn[st]; }    // the next tile's, fetched beside it
+      },
+      [&](long next) CCLIP_SWEEP_INLINE { side(next, cjn, kcjn); });
+  if (!ctx.active) return;
 
-  // the 16 lanes of a group hold disjoint rows j: a fixed xor butterfly (both partners compute the same bits), lane 0 writes
+  // the 16 lanes of a group hold disjoint rows j; lane 0 writes
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      u64 m1 = b1[mt][r];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        const u64 p1 = mst_shfl_xor64(m1, o);
-        m1 = m1 > p1 ? m1 : p1;
-      }
-      const int rel = q0 + 16 * mt + 4 * g + r;
-      if (li == 0 && rel <= last) {
-        if (a.splits == 1) a.out[row0 + rel] = m1;
-        else if (m1 != 0ull) atomicMax(a.out + row0 + rel, m1);   // (the launcher zeroed out; distinct keys: no order)
+      const u64 m1 = group_max_key(b1[mt][r]);
+      if (li == 0 && ctx.row_live(mt, r)) {
+        if (a.splits == 1) a.out[ctx.row(mt, r)] = m1;
+        else if (m1 != 0ull) atomicMax(a.out + ctx.row(mt, r), m1);   // (the launcher zeroed out; distinct keys: no order)
       }
     }
 }
 
-// gallery splits from N alone: about 1024 work-groups while a split keeps at least 1024 rows
+// gallery splits from N alone: about 1024 work-groups of 128 rows while a split keeps at least 1024 rows
 static inline void nearest_splits(int64_t N, int* splits, int* rows_per_split) {
-  const int64_t nblk = (N + 127) / 128;
-  int64_t want = (1024 + nblk - 1) / nblk, most = (N + 1023) / 1024;
-  int64_t s = want < most ? want : most;
-  if (s < 1) s = 1;
-  const int64_t rows = ((N + s - 1) / s + 63) / 64 * 64;
-  s = (N + rows - 1) / rows;                      // no empty split
-  *splits = (int)s; *rows_per_split = (int)rows;
-}
-
-template <int KSMAX, int MT, int GT>
-static int nearest_launch(const NearestArgs& a, hipStream_t stream) {
-  const long nblk = ((long)a.N + 64 * MT - 1) / (64 * MT);        // < 2^26
-  if (nblk * a.splits > 0x7fffffffL) return CCLIP_ERR_ARG;
-  const size_t lds = (size_t)2 * GT * a.D * 2;                    // two tiles
-  return score_launch(mreach_nearest_kernel<KSMAX, MT, GT>, (unsigned)(nblk * a.splits), lds, a, stream);
+  gallery_splits(N, (N + 127) / 128, 1024, 1024, splits, rows_per_split);
 }
 
 // a.x .. a.live set by the caller, whose arguments have been checked.  zero: a.out is not known to hold zeros (more than one
@@ -190,18 +135,15 @@ static int nearest_launch(const NearestArgs& a, hipStream_t stream) {
 static int nearest_dispatch(NearestArgs& a, bool zero, hipStream_t stream) {
   nearest_splits(a.N, &a.splits, &a.rows_per_split);
   if (zero && a.splits > 1 && hipMemsetAsync(a.out, 0, (size_t)a.N * 8, stream) != hipSuccess) return CCLIP_ERR_LAUNCH;
-  const bool wide = a.N > 64;                     // two row tiles per wave halve the LDS reads per MFMA (same bits either way)
-  const int D = a.D;
-  if (D <= 128) return wide ? nearest_launch<4, 2, 64>(a, stream) : nearest_launch<4, 1, 64>(a, stream);
-  if (D <= 512) return wide ? nearest_launch<16, 2, 64>(a, stream) : nearest_launch<16, 1, 64>(a, stream);
-  if (D <= 768) return wide ? nearest_launch<24, 2, 32>(a, stream) : nearest_launch<24, 1, 32>(a, stream);
-  return nearest_launch<32, 1, 32>(a, stream);
+  return score_dispatch<true>(a.D, a.N > 64, [&](auto s) {
+    using S = decltype(s);
+    return sweep_launch(mreach_nearest_kernel<S::KSMAX, S::MT, S::GT>, a, a.N, S::MT, S::GT, a.D, a.splits, 2, 0, stream);
+  });
 }
 
 static bool nearest_operands_ok(const void* x, int64_t ldx, int64_t N, int32_t D, const float* core) {
   if (!x || !core) return false;
-  if (N <= 0 || N > 0x7fffffffLL) return false;
-  if (D < 32 || !score_operands_ok(x, ldx, x, ldx, D)) return false;
+  if (!score_rows_ok(N) || !score_operands_ok(x, ldx, x, ldx, D)) return false;
   return !((uintptr_t)core & 3);
 }
 
@@ -213,8 +155,6 @@ struct MstArgs {
   int* u; int* v; float* m;
   int* flags; int round;                          // flags[round]: this round is live; flags[round + 1]: the next one is
 };
-
-__device__ __forceinline__ int mst_clamp(int v, int N) { return v < 0 ? 0 : (v > N - 1 ? N - 1 : v); }
 
 __global__ __launch_bounds__(256) void mst_init_kernel(const MstArgs a, int* comp0) {
   const long i = blockIdx.x * 256L + threadIdx.x;
@@ -229,8 +169,8 @@ __global__ __launch_bounds__(256) void mst_init_kernel(const MstArgs a, int* com
 __device__ __forceinline__ bool mst_row_edge(const MstArgs& a, int i, int& c, u64& k1, unsigned& hi) {
   const u64 key = a.rowkey[i];
   if (key == 0ull) return false;
-  const int j = mst_clamp((int)~(unsigned)key, a.N);
-  c = mst_clamp(a.cin[i], a.N);                   // (a name is a row: it indexes ck1 / ck2)
+  const int j = clamp_index((int)~(unsigned)key, 0, a.N - 1);
+  c = clamp_index(a.cin[i], 0, a.N - 1);                   // (a name is a row: it indexes ck1 / ck2)
   k1 = (key & 0xffffffff00000000ull) | (unsigned)~(unsigned)min(i, j);
   hi = (unsigned)max(i, j);
   return true;
@@ -262,10 +202,10 @@ __global__ __launch_bounds__(256) void mst_hook_kernel(const MstArgs a) {
   const unsigned k2 = a.ck2[c];
   int par = c;
   if (k1 != 0ull) {
-    const int lo = mst_clamp((int)~(unsigned)k1, N), hi = mst_clamp((int)k2, N);
-    const bool lo_in = mst_clamp(a.cin[lo], N) == c;              // exactly one endpoint of an outgoing edge lies in c
+    const int lo = clamp_index((int)~(unsigned)k1, 0, N - 1), hi = clamp_index((int)k2, 0, N - 1);
+    const bool lo_in = clamp_index(a.cin[lo], 0, N - 1) == c;              // exactly one endpoint of an outgoing edge lies in c
     const int i = lo_in ? lo : hi, j = lo_in ? hi : lo;
-    const int t = mst_clamp(a.cin[j], N);
+    const int t = clamp_index(a.cin[j], 0, N - 1);
     const bool same = a.ck1[t] == k1 && a.ck2[t] == k2;           // t chose this very edge
     if (t != c && !(same && c < t)) {
       par = t;
@@ -278,7 +218,7 @@ __global__ __launch_bounds__(256) void mst_hook_kernel(const MstArgs a) {
 __device__ __forceinline__ int mst_root(const int* parent, int c, int N) {
   int r = c;
   for (int step = 0; step < N; ++step) {          // (the hooks form a forest; the bound only guards garbage)
-    const int p = mst_clamp(parent[r], N);
+    const int p = clamp_index(parent[r], 0, N - 1);
     if (p == r) break;
     r = p;
   }
@@ -289,8 +229,8 @@ __global__ __launch_bounds__(256) void mst_relabel_kernel(const MstArgs a) {
   if (a.flags[a.round] == 0) return;
   const long i = blockIdx.x * 256L + threadIdx.x;
   if (i >= a.N) return;
-  const int r = mst_root(a.parent, mst_clamp(a.cin[i], a.N), a.N);
-  const int r0 = mst_root(a.parent, mst_clamp(a.cin[0], a.N), a.N);
+  const int r = mst_root(a.parent, clamp_index(a.cin[i], 0, a.N - 1), a.N);
+  const int r0 = mst_root(a.parent, clamp_index(a.cin[0], 0, a.N - 1), a.N);
   a.cout[i] = r;
   if (r != r0) a.flags[a.round + 1] = 1;          // (every writer stores the same value)
   a.ck1[i] = 0ull; a.ck2[i] = 0xffffffffu;        // (not read in this kernel)
@@ -304,12 +244,12 @@ using namespace CCLIP_NS;
 
 #ifndef CCLIP_F16
 extern "C" int64_t cclip_mst_workspace(int64_t N) {
-  if (N <= 0 || N > 0x7fffffffLL) return 0;
+  if (!score_rows_ok(N)) return 0;
   return mst_workspace(N);
 }
 
 extern "C" int32_t cclip_mreach_nearest_splits(int64_t N) {
-  if (N <= 0 || N > 0x7fffffffLL) return 0;
+  if (!score_rows_ok(N)) return 0;
   int splits, rows;
   nearest_splits(N, &splits, &rows);
   return splits;

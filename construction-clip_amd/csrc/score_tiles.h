@@ -1,9 +1,10 @@
-// The streamed-tile core of the scoring kernels (embed_topk.hip, lm_score.hip).  A work-group of four waves keeps 64 * MT
+// The streamed-tile parts of the scoring kernels (every kernel on score_sweep.h, plus the backward kernels of
+// embed_cache_bwd.hip and embed_probe.hip, which run their own tile loops on these parts).  A work-group of four waves keeps 64 * MT
 // operand rows as MFMA A fragments in registers and streams a [rows][D] 16-bit matrix through LDS in tiles of GT rows:
 // row-major, 16-byte chunk c of row r stored at chunk c ^ (r & mask) - the swizzle of attention_tiles.h at row length D,
 // conflict-free for the B-fragment reads.  Lane (li, g) of a wave holds the operand rows 4g .. 4g+3 against tile row
 // 16 st + li of sub-tile st, and every score is ONE accumulator chain over d = 0, 32, 64 .. in that order.
-// What a kernel does with acc[][], how many tile buffers it keeps and where its barriers stand are its own.
+// The tile loop, its buffers and its barriers are score_sweep.h's; what a kernel does with acc[][] is its own.
 //   KSMAX: k-steps of 32 the A fragments are sized for (D <= 32 KSMAX); MT: operand tiles of 16 rows per wave; GT: rows per tile
 #pragma once
 #include "cclip_common.h"
@@ -11,7 +12,6 @@
 
 namespace CCLIP_NS {
 
-typedef unsigned long long u64;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // one 16-byte chunk
 
 struct TileGeom {
@@ -99,9 +99,9 @@ static int score_launch(void (*kernel)(const Args), unsigned grid, size_t lds, c
   return CCLIP_OK;
 }
 
-// The contract of the two 16-bit operands [rows][D] with row strides lda, ldb (elements) that both C entries check
+// The contract of the two 16-bit operands [rows][D] with row strides lda, ldb (elements) that every C entry checks
 static inline bool score_operands_ok(const void* a, int64_t lda, const void* b, int64_t ldb, int32_t D) {
-  return !((D & 31) || D > 1024 || (lda & 7) || (ldb & 7) || lda < D || ldb < D || (((uintptr_t)a | (uintptr_t)b) & 15));
+  return !(D < 32 || (D & 31) || D > 1024 || (lda & 7) || (ldb & 7) || lda < D || ldb < D || (((uintptr_t)a | (uintptr_t)b) & 15));
 }
 
 }  // namespace CCLIP_NS

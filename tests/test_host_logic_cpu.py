@@ -376,3 +376,52 @@ def test_duet_takes_strict_turns_and_propagates_errors():
         duet.run(seq("a", 3), boom)
     with pytest.raises(ValueError):
         duet.run(boom, seq("b", 3))
+
+
+# Split counts of the streamed-score kernels, recorded from the build before their split rules became one function
+# (csrc/score_sweep.h: gallery_splits).  N: (topk splits per Q, range splits per Q, cache splits at Np = 16 ceil(N / 16) per Q,
+# nearest splits), Q = 1, 64, 65, 1024.
+_SPLIT_QS = (1, 64, 65, 1024)
+_SPLIT_TABLE = {
+    1: ((1, 1, 1, 1), (1, 1, 1, 1), (1, 1, 1, 1), 1),
+    63: ((1, 1, 1, 1), (1, 1, 1, 1), (1, 1, 1, 1), 1),
+    64: ((1, 1, 1, 1), (1, 1, 1, 1), (1, 1, 1, 1), 1),
+    65: ((1, 1, 1, 1), (1, 1, 1, 1), (1, 1, 1, 1), 1),
+    255: ((1, 1, 1, 1), (1, 1, 1, 1), (1, 1, 1, 1), 1),
+    256: ((1, 1, 1, 1), (1, 1, 1, 1), (1, 1, 1, 1), 1),
+    257: ((2, 2, 2, 2), (2, 2, 2, 2), (2, 2, 2, 2), 1),
+    1023: ((4, 4, 4, 4), (4, 4, 4, 4), (4, 4, 4, 4), 1),
+    1024: ((4, 4, 4, 4), (4, 4, 4, 4), (4, 4, 4, 4), 1),
+    1025: ((5, 5, 5, 5), (5, 5, 5, 5), (5, 5, 5, 5), 2),
+    4099: ((17, 17, 17, 17), (17, 17, 17, 17), (17, 17, 17, 17), 5),
+    100003: ((391, 391, 224, 32), (391, 391, 224, 32), (391, 391, 391, 391), 2),
+    1048576: ((512, 512, 256, 32), (512, 512, 256, 32), (512, 512, 512, 512), 1),
+    2147483647: ((512, 512, 256, 32), (512, 512, 256, 32), (512, 512, 512, 512), 1),
+}
+
+
+def test_streamed_score_split_counts_are_the_recorded_ones():
+    """The workspace entries (what cclip_hip/ops.py sizes its buffers by) and cclip_mreach_nearest_splits report, for every
+    (Q, N) of the grid, the split count the four separate rules gave."""
+    import ctypes
+    import __graft_entry__ as ge
+    ge.build()
+    from cclip_hip import load_library
+    lib = load_library()
+    L, I = ctypes.c_int64, ctypes.c_int32
+    for name in ("cclip_similarity_topk_workspace", "cclip_similarity_range_workspace", "cclip_cache_affinity_workspace"):
+        getattr(lib, name).restype = ctypes.c_int64
+    lib.cclip_mreach_nearest_splits.restype = ctypes.c_int32
+    for N, (topk, rng, cache, nearest) in _SPLIT_TABLE.items():
+        Np = min((N + 15) // 16 * 16, 2 ** 31 - 16)
+        for Q, t, r, c in zip(_SPLIT_QS, topk, rng, cache):
+            assert lib.cclip_similarity_topk_workspace(I(Q), L(N), I(1)) == Q * t * 8, (Q, N)
+            assert lib.cclip_similarity_topk_workspace(I(Q), L(N), I(7)) == Q * t * 7 * 8, (Q, N)
+            assert lib.cclip_similarity_range_workspace(I(Q), L(N)) == Q * r * 4, (Q, N)
+            assert lib.cclip_cache_affinity_workspace(I(Q), L(Np), I(1)) == Q * c * 4, (Q, Np)
+        assert lib.cclip_mreach_nearest_splits(L(N)) == nearest, N
+    # the shared row-count check
+    assert lib.cclip_similarity_range_workspace(I(1), L(0)) == 0
+    assert lib.cclip_similarity_range_workspace(I(1), L(2 ** 31)) == 0
+    assert lib.cclip_mreach_nearest_splits(L(0)) == 0
+    assert lib.cclip_mreach_nearest_splits(L(2 ** 31)) == 0

@@ -10,7 +10,12 @@ wider buffer, duplicated rows / equal columns, a NaN row, an ignored and an out-
 xent_rows_classes and sigmoid_rows: R = 9 over C = 1, 63, 64, 257, 300 without a gradient, with one, and with the gradient
 written over the logits, every input holding a row of ties and an all-NaN row; xent_rows also with a 16-bit gradient.
 caption_select: N = 3, K = 1, 5, 64, E = 4, 512, 1024 with references, with and without lm_mean, with a NaN score.
-sample_rows: V = 5, 4099, 50257 with top-k, with top-p and with neither, from fixed u.  l2norm_fwd and text_embed: one case."""
+sample_rows: V = 5, 4099, 50257 with top-k, with top-p and with neither, from fixed u.  l2norm_fwd and text_embed: one case.
+The other kernels on csrc/score_sweep.h - similarity_range (self-join on and off), kmeans_assign, cache_affinity forward and
+backward, probe forward and backward, mreach_nearest and mst_boruvka - run over SWEEP_SHAPES in both dtypes: one D per
+dispatch rung and a D that is not a power-of-two number of chunks, 1 / 63 / 65 / 129 operand rows (a partly filled wave, an
+idle wave, both row-tile counts), 1 .. 3000 streamed rows (a partial sub-tile, a partial tile, two tiles, several splits), and
+one case each with padded row strides."""
 import argparse
 import os
 import sys
@@ -26,6 +31,9 @@ TOPK_SHAPES = [(1, 1, 64, 1), (3, 5, 128, 5), (16, 64, 512, 10), (130, 4097, 128
                (3, 1000, 32, 5), (100, 1000, 96, 5), (100, 4097, 160, 10)]
 LM_SHAPES = [(1, 1, 32), (3, 15, 32), (17, 300, 128), (300, 300, 128), (70, 2050, 512), (65, 4099, 768), (33, 1000, 1024)]
 ROW_R, ROW_C = 9, (1, 63, 64, 257, 300)
+# (operand rows, streamed rows, D)
+SWEEP_SHAPES = [(1, 1, 32), (63, 17, 128), (65, 64, 160), (129, 65, 512), (65, 1025, 768), (129, 3000, 1024), (129, 3000, 128),
+                (1, 1025, 512), (63, 3000, 160)]
 
 
 def rnd(seed, *shape, scale=1.0):
@@ -69,6 +77,53 @@ def lm_cases():
         labels = torch.randint(0, V, (R,), generator=torch.Generator().manual_seed(550)).to(torch.int32)
         labels[3], labels[4], labels[5] = -100, V, -1               # ignored; out of range above and below
         yield f"lm/{tag}/slice_labels_equal_columns", dict(zip(names, ops.lm_head_score(wide[:, 32:32 + D], w, labels.cuda())))
+
+
+def unit(seed, n, D, dt):
+    x = rnd(seed, n, D)
+    return (x / x.norm(dim=1, keepdim=True)).to(dt).cuda()
+
+
+def sweep_cases():
+    for dt, tag in DTYPES:
+        for i, (R, S, D) in enumerate(SWEEP_SHAPES + [SWEEP_SHAPES[3]]):
+            pad = i == len(SWEEP_SHAPES)                            # the last case again, with padded row strides
+            name = f"{tag}/{R}x{S}x{D}" + ("/padded" if pad else "")
+            q, g = unit(1000 + i, R, D, dt), unit(1100 + i, S, D, dt)
+            if pad:
+                q, g = padded(q, 8), padded(g, 24)
+            thr = 1.2 / D ** 0.5                                    # a few percent of the pairs
+            yield f"range/{name}", dict(zip(("offsets", "index", "scores"), ops.similarity_range(q, g, thr)))
+            yield f"range_self/{name}", dict(zip(("offsets", "index", "scores"), ops.similarity_range(g, g, thr, self_join=True)))
+            yield f"kmeans_assign/{name}", dict(zip(("assign", "best", "second"), ops.kmeans_assign(q, g, want_second=True)))
+            # few-shot cache over the streamed rows: 5 classes, one of them empty
+            gen = torch.Generator().manual_seed(1200 + i)
+            labels = torch.randint(0, 4, (S,), generator=gen)
+            gather, class_off, class_len = ops.cache_layout(labels, 5)
+            keys = torch.zeros(gather.numel(), D, dtype=dt, device="cuda")
+            src = g.contiguous()
+            keys[(gather >= 0).cuda()] = src[gather[gather >= 0].cuda()]
+            keys[(gather < 0).cuda()] = float("nan")                # padding rows are never used
+            if pad:
+                keys = padded(keys, 16)
+            excl = torch.randint(-1, gather.numel(), (R,), generator=gen).to(torch.int32).cuda()
+            yield f"cache_affinity/{name}", {"A": ops.cache_affinity(q, keys, class_off, class_len, 5.5, exclude=excl)}
+            dA = rnd(1300 + i, R, 5).cuda()
+            yield f"cache_affinity_bwd/{name}", {"dG": ops.cache_affinity_backward(q, keys, class_off, class_len, 5.5, dA, exclude=excl)}
+            # linear probe: the operand rows against C classes
+            C = min(max(2, S // 12), 250)
+            W, bias = rnd(1400 + i, C, D, scale=0.5).cuda(), rnd(1500 + i, C).cuda()
+            y = torch.randint(-1, C, (R,), generator=gen).to(torch.int32).cuda()
+            rw = torch.rand(R, generator=gen).cuda()
+            lse, loss, pred, logits = ops.probe_forward(q, W, bias, y, row_weight=rw, logits=True)
+            yield f"probe_fwd/{name}", {"lse": lse, "loss": loss, "pred": pred, "logits": logits}
+            dW, db, obj = ops.probe_backward(q, W, bias, y, lse, 1.0 / R, 1e-3, row_weight=rw, loss=loss)
+            yield f"probe_bwd/{name}", {"dW": dW, "db": db, "objective": obj}
+            # mutual reachability over the streamed rows
+            core = (torch.rand(S, generator=gen) * 0.5).cuda()
+            comp = torch.randint(0, 3, (S,), generator=gen).to(torch.int32).cuda()
+            yield f"mreach_nearest/{name}", {"keys": ops.mreach_nearest(g, core, comp)}
+            yield f"mst_boruvka/{name}", dict(zip(("u", "v", "m"), ops.mst_boruvka(g, core)))
 
 
 def row_inputs(C, seed):
@@ -159,7 +214,7 @@ def grid_cases():
 
 def cases():
     """(name, {tensor name: tensor}) of every launch, in a fixed order"""
-    for gen in (topk_cases, lm_cases, row_cases, select_cases, sample_cases, grid_cases):
+    for gen in (topk_cases, lm_cases, sweep_cases, row_cases, select_cases, sample_cases, grid_cases):
         yield from gen()
 
 
