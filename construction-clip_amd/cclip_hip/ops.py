@@ -2471,3 +2471,57 @@ def scale_f32(x: torch.Tensor, alpha: float) -> None:
 
 def cast_f32_to_bf16(src, dst) -> None:
     check(_fn("cclip_cast_f32_to_bf16", dst)(_p(src), _p(dst), c_long(src.numel()), _stream()), "cclip_cast_f32_to_bf16")
+
+
+CONCEPT_MAX_V = 1 << 24
+
+
+def concept_codes_workspace(N: int, V: int, D: int) -> int:
+    """bytes of workspace cclip_concept_codes needs (the fp32 w_{k-1} of every row: 4 N * 4 ceil(V / 4); 0 for a problem it
+    would refuse)"""
+    fn = lib.cclip_concept_codes_workspace
+    fn.restype = c_long
+    return int(fn(c_long(N), c_long(V), c_int(D)))
+
+
+def concept_codes(x, c, l1: float, eta: float, iters: int, *, out_w=None, workspace=None):
+    """Sparse non-negative codes of the rows of x [N, D] over the dictionary c [V, D] (both 16-bit unit rows of one dtype under
+    the contract of kmeans_assign): `iters` FISTA iterations of  min_{w >= 0} 1/2 |x - w c|^2 + l1 sum w  with step eta (1 / the
+    largest eigenvalue of c^T c) and beta_k = k / (k + 3), all inside one launch (include/cclip_hip.h, cclip_concept_codes).
+    Returns (w fp32 [N, V], resid2 fp32 [N], l1norm fp32 [N], nnz int32 [N], delta fp32 [N], kkt fp32 [N]): the read-outs are
+    taken at w itself; kkt is the row's distance from optimality.  out_w: an fp32 [N, V] device view with inner stride 1, a row
+    stride that is a multiple of 4 and 16-byte alignment (nothing is written between its rows); workspace: a contiguous fp32
+    device tensor of at least concept_codes_workspace(N, V, D) bytes.  1 <= V <= 2^24, D % 32 == 0, 32 <= D <= 1024, N < 2^31.
+    A row's outputs depend on neither N nor its position; two calls are bitwise equal.  No host read."""
+    N, V, D, ldx, ldc = _kmeans_operands("concept_codes", x, c, "c")
+    if V > CONCEPT_MAX_V:
+        raise NotImplementedError(f"concept_codes: V = {V}; the kernel takes up to {CONCEPT_MAX_V} concepts")
+    l1, eta = float(l1), float(eta)
+    if not (0.0 <= l1 < float("inf")) or not (0.0 <= eta < float("inf")):
+        raise ValueError(f"concept_codes: l1 = {l1} and eta = {eta} must be finite and >= 0")
+    if isinstance(iters, bool) or int(iters) != iters or iters < 0:
+        raise ValueError(f"concept_codes: iters = {iters!r} must be an integer >= 0")
+    dev = x.device
+    if out_w is None:
+        out_w = torch.empty(N, (V + 3) // 4 * 4, device=dev, dtype=torch.float32)[:, :V]
+    elif (not isinstance(out_w, torch.Tensor) or out_w.dtype != torch.float32 or out_w.device != dev
+          or tuple(out_w.shape) != (N, V) or out_w.stride(1) != 1):
+        raise ValueError(f"concept_codes: out_w must be an fp32 [{N}, {V}] view on {dev} with inner stride 1, got "
+                         f"{getattr(out_w, 'dtype', type(out_w))} {tuple(getattr(out_w, 'shape', ()))}")
+    ldw = out_w.stride(0) if N > 1 else max(out_w.stride(0), (V + 3) // 4 * 4)
+    if ldw % 4 or ldw < V or out_w.data_ptr() % 16:
+        raise ValueError(f"concept_codes: out_w must be 16-byte aligned with a row stride >= V that is a multiple of 4 elements "
+                         f"(stride {out_w.stride(0)}, address % 16 = {out_w.data_ptr() % 16})")
+    nbytes = concept_codes_workspace(N, V, D)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or workspace.device != dev
+          or not workspace.is_contiguous() or workspace.numel() * 4 < nbytes or workspace.data_ptr() % 16):
+        raise ValueError(f"concept_codes: workspace must be a contiguous 16-byte aligned fp32 tensor of at least {nbytes} bytes on {dev}")
+    resid2, l1norm, delta, kkt = (torch.empty(N, device=dev, dtype=torch.float32) for _ in range(4))
+    nnz = torch.empty(N, device=dev, dtype=torch.int32)
+    fn = _fn("cclip_concept_codes", x, c)
+    check(fn(_p(x), c_long(ldx), c_long(N), _p(c), c_long(ldc), c_long(V), c_int(D), c_float(l1), c_float(eta), c_int(int(iters)),
+             _p(out_w), c_long(ldw), _p(resid2), _p(l1norm), _p(nnz), _p(delta), _p(kkt), _p(workspace),
+             c_long(workspace.numel() * 4), _stream()), "cclip_concept_codes")
+    return out_w, resid2, l1norm, nnz, delta, kkt

@@ -16,6 +16,7 @@ from .tsne import tsne, TSNEResult  # noqa: F401  (a 2-D map of the stored embed
 from .propagate import spread_labels, LabelSpreadResult, affinity_csr  # noqa: F401  (label spreading: a few labels over the kNN graph)
 from .coreset import select_coreset, CoresetResult  # noqa: F401  (k-centre greedy selection: which photos to label next)
 from .hdbscan import hdbscan, HDBSCANResult, mutual_reachability_mst, MSTResult  # noqa: F401  (density clusters without a k, on an exact spanning tree)
+from .concepts import ConceptDictionary, ConceptDecomposition, ConceptProfile, decompose, concept_profile, distinctive  # noqa: F401  (sparse non-negative concept codes: what is in an embedding, in words)
 from .fewshot import CacheClassifier, confusion_matrix  # noqa: F401  (few-shot classification from the stored, labelled embeddings)
 from .probe import LinearProbe, ProbeLossFunction, ProbeFitResult  # noqa: F401  (linear probe: logistic regression on the stored embeddings)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)

@@ -212,6 +212,12 @@ class EmbeddingIndex:
         from .hdbscan import hdbscan
         return hdbscan(self, **kw)
 
+    def decompose(self, dictionary, **kw):
+        """The stored rows as sparse non-negative combinations of a `ConceptDictionary`'s concepts (clip/concepts.py:
+        csrc/concept_codes.hip): a `ConceptDecomposition`.  The rows are used as stored, not copied, unless centred."""
+        from .concepts import decompose
+        return decompose(self, dictionary, **kw)
+
     @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)

@@ -584,6 +584,37 @@ int cclip_probe_backward(const void* x, int64_t ldx, int64_t N, int32_t D, const
                          float l2, float* dW, float* db, float* objective, void* workspace, int64_t workspace_bytes,
                          hipStream_t stream);
 
+/* ---- Concept decomposition: sparse non-negative codes over a dictionary (csrc/concept_codes.hip) -------------------------
+ * x [N, D] and the dictionary c [V, D]: unit bf16 rows (fp16 in the twin) under the contract of cclip_kmeans_assign (row
+ * strides ldx, ldc in elements, multiples of 8, 16-byte aligned).  Per row of x, independently,
+ *   minimise over w >= 0:  1/2 |x - sum_v w_v c_v|^2 + l1 sum_v w_v
+ * by exactly `iters` FISTA iterations with the non-negative soft threshold, step eta (the caller's 1 / L, L the largest
+ * eigenvalue of c^T c; never computed here) and beta_k = k / (k + 3), w_0 = w_{-1} = 0:
+ *   y_k = w_k + beta_k (w_k - w_{k-1});   g_v = <c_v, x - sum_u y_{k,u} c_u>;   w_{k+1,v} = max(0, y_{k,v} + eta (g_v - l1))
+ * in fp32.  The residual x - sum y c is carried in fp32 at the point the next gradient is taken at (y_{k+1}; w_T in the last
+ * iteration) and enters the MFMA, as the tile of y does, as the 16-bit pair hi = round16(v), lo = round16(v - hi) (what is
+ * dropped: 2^-16 relative in bf16, 2^-22 in fp16).  A padding concept (V up to the tile of 32) counts as a zero row: its weight
+ * is never written and never counted.
+ * Outputs: w fp32 [N, V] (row stride ldw >= V elements, a multiple of 4, 16-byte aligned; nothing is written between the rows)
+ * = w_T, and per row, from a closing sweep at w_T itself (each [N] contiguous):
+ *   resid2 = |x - sum w c|^2   l1norm = sum w   nnz = #{w > 0} int32   delta = max_v |w_T - w_{T-1}|
+ *   kkt    = max_v (w_v > 0 ? |g_v - l1| : max(0, g_v - l1)): the row's distance from optimality
+ * iters == 0 gives w = 0, resid2 = |x|^2, delta = 0.  A row of x that holds a NaN gets NaN weights and NaN float read-outs
+ * (nnz 0) for iters >= 1 and touches no other row.  A row's outputs are a function of (the row, c, l1, eta, iters) alone - not
+ * of N, the row's position or the grid; no atomics, no fused multiply-add, one summation order: two calls are bitwise equal.
+ * ONE launch on `stream` runs every iteration (a work-group owns 32 rows at D <= 512, 16 above, and re-streams c per
+ * iteration); nothing is read on the host.
+ * workspace: at least cclip_concept_codes_workspace(N, V, D) = 4 N * 4 ceil(V / 4) bytes (0 for arguments the call would
+ * refuse), 16-byte aligned: w_{k-1}.  Contents meaningless before and after.
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): a null pointer; N <= 0 or N >= 2^31; V < 1 or V > 2^24; D < 32, D % 32
+ * or D > 1024; ldx or ldc below D or not a multiple of 8, x or c not 16-byte aligned; ldw below V or not a multiple of 4, w or
+ * workspace not 16-byte aligned; a misaligned read-out array; l1 or eta negative or not finite; iters < 0; workspace too
+ * small. */
+int64_t cclip_concept_codes_workspace(int64_t N, int64_t V, int32_t D);
+int cclip_concept_codes(const void* x, int64_t ldx, int64_t N, const void* c, int64_t ldc, int64_t V, int32_t D, float l1,
+                        float eta, int32_t iters, float* w, int64_t ldw, float* resid2, float* l1norm, int32_t* nnz,
+                        float* delta, float* kkt, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- t-SNE of stored embeddings: neighbour probabilities (csrc/tsne.hip, fp32 only) -------------------------------------
  * scores fp32 [N, k] (row stride ld >= k elements): the similarities of every row's k nearest OTHER unit rows, in any order.
  * Per row, with d2_j = 2 - 2 s_j (a negative value taken as 0) and diff_j = d2_j - min_j d2_j, all in fp32:
@@ -1087,6 +1118,9 @@ int cclip_probe_backward_f16(const void* x, int64_t ldx, int64_t N, int32_t D, c
                              const int32_t* labels, const float* row_weight, const float* lse, const float* loss, float scale,
                              float l2, float* dW, float* db, float* objective, void* workspace, int64_t workspace_bytes,
                              hipStream_t stream);
+int cclip_concept_codes_f16(const void* x, int64_t ldx, int64_t N, const void* c, int64_t ldc, int64_t V, int32_t D, float l1,
+                            float eta, int32_t iters, float* w, int64_t ldw, float* resid2, float* l1norm, int32_t* nnz,
+                            float* delta, float* kkt, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
