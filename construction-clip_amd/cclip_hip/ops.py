@@ -685,34 +685,138 @@ def attention_probs(q, k, P, *, B: int, T: int, H: int, causal: bool = False, sc
                                              c_long(P.stride(1)), c_long(P.stride(2)), _stream()), "cclip_attention_probs")
 
 
-def _pair16(fname: str, a, an: str, b, bn: str):
-    """The two 16-bit row-major operands of a score kernel (csrc/score_tiles.h): on the device, 2-D, inner stride 1, equal widths.
-    Returns (rows of a, rows of b, D).  A wrong dtype is lm_head_score's ValueError or similarity_topk's TypeError (_req16, _fn)."""
-    pair = ((a, an), (b, bn))
-    if fname == "lm_head_score":
-        for t, n in pair:
-            if not t.is_cuda:
-                raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {t.device} (no CPU path)")
-        for t, n in pair:
-            if t.dtype not in HALF_TYPES or t.dtype != a.dtype:
-                raise ValueError(f"{fname}: {n} must be bfloat16 or float16, both alike, got {a.dtype} / {t.dtype}")
-    else:
-        for t, n in pair:
-            _req16(t, n)
-    for t, n in pair:
-        if t.dim() != 2 or t.stride(1) != 1:
-            raise ValueError(f"{fname}: {n} must be a 2-D view with inner stride 1, got {tuple(t.shape)} / {t.stride()}")
-    if b.shape[1] != a.shape[1]:
-        raise ValueError(f"{fname}: {an} has {a.shape[1]} columns, {bn} has {b.shape[1]}")
-    return a.shape[0], b.shape[0], a.shape[1]
+# --------------------------------------------------------------------------------------------
+# embedding analysis (retrieval, range search, lm_head scoring, cache classifier, k-means, coreset, spanning tree, linear probe,
+# t-SNE, label spreading, concept codes): one operand contract.  Every wrapper checks in the order cuda, dtype, shape over all
+# its tensors, then the size limits, then alignment, and touches the library only after that.
+# --------------------------------------------------------------------------------------------
+def _fits(shape, got) -> bool:
+    """got against a shape in which None stands for any extent"""
+    if len(got) != len(shape):
+        return False
+    for s, g in zip(shape, got):
+        if s is not None and s != g:
+            return False
+    return True
+
+
+def _dev_tensors(fname: str, dev, specs, *, contiguous: bool = True, host_error=TypeError, dtype_error=TypeError, device_error=ValueError):
+    """The one check of a tensor argument, over specs = (t, name, dtype, shape, optional) in turn: on the device; of `dtype` (one,
+    a tuple to choose from, None: any); on `dev` where one is given; of `shape` (a tuple, None in it: any extent; an int: that
+    many dimensions; None: any) and contiguous unless told otherwise.  A host tensor or a non-tensor is a host_error, a wrong
+    dtype a dtype_error, another device a device_error, everything else a ValueError."""
+    for t, n, dtype, shape, optional in specs:
+        if t is None and optional:
+            continue
+        if isinstance(t, torch.Tensor) and (t.is_cuda if dev is None else t.device == dev) and \
+                (dtype is None or t.dtype == dtype or (dtype.__class__ is tuple and t.dtype in dtype)) and \
+                (shape is None or t.shape == shape or (t.dim() == shape if shape.__class__ is int else _fits(shape, t.shape))) and \
+                (not contiguous or t.is_contiguous()):
+            continue                                         # all is well; below, what is not, in the contract's order
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise host_error(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if dtype is not None and t.dtype != dtype and not (dtype.__class__ is tuple and t.dtype in dtype):
+            names = " or ".join(str(d)[6:] for d in (dtype if isinstance(dtype, tuple) else (dtype,)))
+            raise dtype_error(f"{fname}: {n}: expected {names}, got {t.dtype} on {t.device}")
+        if dev is not None and t.device != dev:
+            raise device_error(f"{fname}: {n} must be on {dev}, got {t.device}")
+        want = ("contiguous " if contiguous else "") + (f"{shape}-D " if shape.__class__ is int else f"{list(shape)} " if shape is not None else "")
+        raise ValueError(f"{fname}: {n} must be a {want}tensor (None: any extent), got {tuple(t.shape)} / {t.stride()}")
+
+
+def _dev_tensor(fname: str, t, n: str, dtype, shape, dev, *, optional: bool = False, **how):
+    """_dev_tensors for one tensor, which it returns"""
+    _dev_tensors(fname, dev, ((t, n, dtype, shape, optional),), **how)
+    return t
+
+
+def _out(fname: str, t, n: str, dtype, shape, dev, *, host_error=ValueError, dtype_error=ValueError):
+    """An output the caller may provide: allocated when t is None, else checked; whatever is wrong with it is a ValueError, unless
+    the wrapper has always answered a host tensor or a dtype otherwise."""
+    if t is None:
+        return torch.empty(*shape, device=dev, dtype=dtype)
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.shape == shape and t.is_contiguous()):
+        _dev_tensors(fname, dev, ((t, n, dtype, shape, False),), host_error=host_error, dtype_error=dtype_error)   # says what is wrong
+    return t
+
+
+def _workspace(fname: str, ws, nbytes: int, dtype, dev, *, align16: bool = False, flat: bool = False, host_error=ValueError):
+    """Scratch of at least nbytes: allocated when ws is None, else the caller's contiguous `dtype` tensor (flat: a vector)."""
+    size = dtype.itemsize
+    if ws is None:
+        return torch.empty((nbytes + size - 1) // size, device=dev, dtype=dtype)
+    _dev_tensor(fname, ws, "workspace", dtype, 1 if flat else None, dev, host_error=host_error, dtype_error=host_error)
+    if ws.numel() * size < nbytes or (align16 and ws.data_ptr() % 16):
+        raise ValueError(f"{fname}: workspace must hold at least {nbytes} bytes{', 16-byte aligned' if align16 else ''}, got "
+                         f"{ws.numel() * size} (address % 16 = {ws.data_ptr() % 16})")
+    return ws
+
+
+def _finite(fname: str, n: str, v, *, nonneg: bool = False) -> float:
+    v = float(v)
+    if v != v or v in (float("inf"), float("-inf")) or (nonneg and v < 0):
+        raise ValueError(f"{fname}: {n} must be finite{' and >= 0' if nonneg else ''}, got {v}")
+    return v
+
+
+_QUERIES = {}
+
+
+def _query(name: str, restype, *cargs) -> int:
+    """A size query of the library (the *_workspace, *_splits, *_blocks, *_parts and *_groups entries): pure functions of the sizes."""
+    fn = _QUERIES.get(name)
+    if fn is None:
+        fn = _QUERIES[name] = getattr(lib, name)
+        fn.restype = restype
+    return int(fn(*cargs))
+
+
+def _ld(t, *, multiple: int, at_least: int) -> int:
+    """Row stride (elements) of a 2-D view.  A one-row view's is free: it is rounded down to a multiple of `multiple` and up to
+    at_least, so that it fits whatever the kernel asks of a stride."""
+    return t.stride(0) if t.shape[0] > 1 else max(at_least, t.stride(0) // multiple * multiple)
+
+
+def _view16(fname: str, specs, dtype_error=TypeError):
+    """The 16-bit row-major operands of a score kernel (csrc/score_tiles.h), first part; specs = (t, name, HALF_TYPES, None,
+    False) each: all on the device, then all bfloat16 or float16, then all 2-D with inner stride 1."""
+    if dtype_error is not TypeError:                         # a host tensor is a TypeError: it comes before any operand's dtype
+        _dev_tensors(fname, None, [(s[0], s[1], None, None, False) for s in specs], contiguous=False)
+    _dev_tensors(fname, None, specs, contiguous=False, dtype_error=dtype_error)
+    for s in specs:
+        if s[0].dim() != 2 or s[0].stride(1) != 1:
+            raise ValueError(f"{fname}: {s[1]} must be a 2-D view with inner stride 1, got {tuple(s[0].shape)} / {s[0].stride()}")
+
+
+def _limits16(fname: str, D: int, names: str, rows, *, min_d: int = 32, max_d: int = 1024):
+    """Second part, once every tensor of the call has passed the first: no empty operand, D % 32 == 0 inside min_d .. max_d, row
+    counts (`names`: what the messages call them) that fit the kernels' int32 indices."""
+    if min(rows) >= 1 and not D % 32 and min_d <= D <= max_d and max(rows) < 2 ** 31:
+        return
+    shown = ", ".join(f"{k} = {v}" for k, v in zip(names.split(), rows))
+    if min(rows) < 1:
+        raise ValueError(f"{fname}: empty operand ({shown})")
+    if D % 32 or not min_d <= D <= max_d:
+        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and {f'{min_d} <= ' if min_d else ''}D <= {max_d}")
+    raise NotImplementedError(f"{fname}: {shown}; the kernel's row indices are int32 (< 2^31)")
 
 
 def _ld16(fname: str, t, n: str) -> int:
-    """Row stride (elements) of such an operand, checked for the kernel's 16-byte loads; a one-row view's is rounded to fit."""
-    if (t.shape[0] > 1 and t.stride(0) % 8) or t.data_ptr() % 16:
+    """Last part: the row stride (elements) for the kernel's 16-byte loads, a multiple of 8 from a 16-byte aligned base."""
+    ld = t.stride(0) if t.shape[0] > 1 else _ld(t, multiple=8, at_least=t.shape[1])
+    if ld % 8 or t.data_ptr() % 16:
         raise ValueError(f"{fname}: {n} must be 16-byte aligned with a row stride that is a multiple of 8 elements "
                          f"(stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16})")
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0) // 8 * 8)
+    return ld
+
+
+def _pair16(fname: str, a, an: str, b, bn: str, *, dtype_error=TypeError):
+    """The first part for the two operands of a score kernel, and their equal widths.  Returns (rows of a, rows of b, D).
+    bfloat16 against float16 is answered where each wrapper has always answered it: by _fn, or right after this."""
+    _view16(fname, ((a, an, HALF_TYPES, None, False), (b, bn, HALF_TYPES, None, False)), dtype_error)
+    if b.shape[1] != a.shape[1]:
+        raise ValueError(f"{fname}: {an} has {a.shape[1]} columns, {bn} has {b.shape[1]}")
+    return a.shape[0], b.shape[0], a.shape[1]
 
 
 SIMILARITY_TOPK_MAX_K = 64
@@ -721,9 +825,7 @@ SIMILARITY_TOPK_MAX_D = 1024
 
 def similarity_topk_workspace(Q: int, N: int, k: int) -> int:
     """bytes of candidate workspace cclip_similarity_topk needs for this problem (Q * splits * k * 8)"""
-    fn = lib.cclip_similarity_topk_workspace
-    fn.restype = c_long
-    return int(fn(c_int(Q), c_long(N), c_int(k)))
+    return _query("cclip_similarity_topk_workspace", c_long, c_int(Q), c_long(N), c_int(k))
 
 
 def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
@@ -731,27 +833,19 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
     row strides multiples of 8 elements, 16-byte aligned.  Returns (scores fp32 [Q, k] descending, index int32 [Q, k]); equal
     scores by the lower gallery index, NaN last.  The Q x N matrix is never formed: the only scratch is the per-split
     candidate workspace.  1 <= k <= 64, k <= N, D % 32 == 0, D <= 1024, N < 2^31.  Enqueues two launches; no host read."""
-    Q, N, D = _pair16("similarity_topk", q, "q", g, "g")
-    if Q < 1 or N < 1:
-        raise ValueError(f"similarity_topk: empty operand (Q = {Q}, N = {N})")
+    fname = "similarity_topk"
+    Q, N, D = _pair16(fname, q, "q", g, "g")
     if not 1 <= k <= SIMILARITY_TOPK_MAX_K:
-        raise ValueError(f"similarity_topk: k = {k} outside the kernel's range 1 .. {SIMILARITY_TOPK_MAX_K}")
+        raise ValueError(f"{fname}: k = {k} outside the kernel's range 1 .. {SIMILARITY_TOPK_MAX_K}")
     if k > N:
-        raise ValueError(f"similarity_topk: k = {k} above the gallery's {N} rows")
-    if D % 32 or D > SIMILARITY_TOPK_MAX_D:
-        raise NotImplementedError(f"similarity_topk: D = {D}; the kernel needs D % 32 == 0 and D <= {SIMILARITY_TOPK_MAX_D}")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"similarity_topk: N = {N}; the kernel's gallery index is int32 (N < 2^31)")
-    ldq, ldg = _ld16("similarity_topk", q, "q"), _ld16("similarity_topk", g, "g")
+        raise ValueError(f"{fname}: k = {k} above the gallery's {N} rows")
+    _limits16(fname, D, "Q N", (Q, N), min_d=0, max_d=SIMILARITY_TOPK_MAX_D)        # D = 0: left to the C entry, as ever
+    ldq, ldg = _ld16(fname, q, "q"), _ld16(fname, g, "g")
     fn = _fn("cclip_similarity_topk", q, g)
-    if out_scores is None:
-        out_scores = torch.empty(Q, k, device=q.device, dtype=torch.float32)
-    if out_index is None:
-        out_index = torch.empty(Q, k, device=q.device, dtype=torch.int32)
-    _req(out_scores, torch.float32, "out_scores"); _req(out_index, torch.int32, "out_index")
-    assert out_scores.is_contiguous() and out_index.is_contiguous() and tuple(out_scores.shape) == (Q, k) == tuple(out_index.shape)
+    out_scores = _out(fname, out_scores, "out_scores", torch.float32, (Q, k), q.device, host_error=TypeError, dtype_error=TypeError)
+    out_index = _out(fname, out_index, "out_index", torch.int32, (Q, k), q.device, host_error=TypeError, dtype_error=TypeError)
     nbytes = similarity_topk_workspace(Q, N, k)
-    ws = torch.empty(nbytes // 8, device=q.device, dtype=torch.int64)
+    ws = _workspace(fname, None, nbytes, torch.int64, q.device)
     check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(N), c_int(D), c_int(k), _p(out_scores), _p(out_index),
              _p(ws), c_long(nbytes), _stream()), "cclip_similarity_topk")
     return out_scores, out_index
@@ -759,9 +853,7 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
 
 def similarity_range_workspace(Q: int, N: int) -> int:
     """bytes of per-(query row, gallery split) hit counts cclip_similarity_range_count fills (Q * splits * 4)"""
-    fn = lib.cclip_similarity_range_workspace
-    fn.restype = c_long
-    return int(fn(c_int(Q), c_long(N)))
+    return _query("cclip_similarity_range_workspace", c_long, c_int(Q), c_long(N))
 
 
 def similarity_range(q, g, threshold: float, self_join: bool = False):
@@ -772,19 +864,15 @@ def similarity_range(q, g, threshold: float, self_join: bool = False):
     returns every other pair.  self_join (g must be q itself) keeps only the pairs n > i at about half the work.  The Q x N
     matrix is never formed.  Count launch, a cumsum over the Q * splits counts on the device, ONE host read of the total H to
     size the outputs (the only synchronisation), emit launch; H == 0 returns empty tensors and launches no emit."""
-    Q, N, D = _pair16("similarity_range", q, "q", g, "g")
-    if Q < 1 or N < 1:
-        raise ValueError(f"similarity_range: empty operand (Q = {Q}, N = {N})")
-    if D % 32 or D > SIMILARITY_TOPK_MAX_D:
-        raise NotImplementedError(f"similarity_range: D = {D}; the kernel needs D % 32 == 0 and D <= {SIMILARITY_TOPK_MAX_D}")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"similarity_range: N = {N}; the kernel's gallery index is int32 (N < 2^31)")
+    fname = "similarity_range"
+    Q, N, D = _pair16(fname, q, "q", g, "g")
+    _limits16(fname, D, "Q N", (Q, N), min_d=0, max_d=SIMILARITY_TOPK_MAX_D)
     threshold = float(threshold)
     if threshold != threshold:
-        raise ValueError("similarity_range: threshold is NaN")
-    ldq, ldg = _ld16("similarity_range", q, "q"), _ld16("similarity_range", g, "g")
+        raise ValueError(f"{fname}: threshold is NaN")
+    ldq, ldg = _ld16(fname, q, "q"), _ld16(fname, g, "g")
     if self_join and (q.data_ptr() != g.data_ptr() or Q != N or ldq != ldg):
-        raise ValueError(f"similarity_range: self_join needs g to be q itself (same memory, same rows), got Q = {Q}, N = {N}")
+        raise ValueError(f"{fname}: self_join needs g to be q itself (same memory, same rows), got Q = {Q}, N = {N}")
     count = _fn("cclip_similarity_range_count", q, g)
     emit = _fn("cclip_similarity_range_emit", q, g)
     nbytes = similarity_range_workspace(Q, N)
@@ -808,9 +896,7 @@ LM_HEAD_SCORE_MAX_D = 1024
 
 def lm_head_score_workspace(R: int, V: int) -> int:
     """bytes of per-split partials cclip_lm_head_score needs (R * ceil(V / 1024) * 24)"""
-    fn = lib.cclip_lm_head_score_workspace
-    fn.restype = c_long
-    return int(fn(c_int(R), c_int(V)))
+    return _query("cclip_lm_head_score_workspace", c_long, c_int(R), c_int(V))
 
 
 def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, lse=None, pred=None, pred_logit=None):
@@ -819,34 +905,24 @@ def lm_head_score(x16, w16, labels_i32, *, ignore_index: int = -100, logp=None, 
     pred_logit), each [R]: logp = z[label] - lse (exactly 0 where label == ignore_index, NaN for any other label outside
     [0, V)), lse = logsumexp(z), pred = argmax (equal logits: the lower column; NaN below every number) and its logit.
     D % 32 == 0, 32 <= D <= 1024.  A row's outputs do not depend on R.  Enqueues two launches; no host read."""
-    R, V, D = _pair16("lm_head_score", x16, "x16", w16, "w16")
-    if not labels_i32.is_cuda:
-        raise TypeError(f"lm_head_score: labels_i32: expected a cuda tensor, got {labels_i32.device} (no CPU path)")
-    if labels_i32.dtype != torch.int32:
-        raise ValueError(f"lm_head_score: labels must be int32, got {labels_i32.dtype}")
-    if R < 1 or V < 1:
-        raise ValueError(f"lm_head_score: empty operand (R = {R}, V = {V})")
-    if V >= 2 ** 31:
-        raise ValueError(f"lm_head_score: V = {V}; column indices are int32")
-    if labels_i32.dim() != 1 or labels_i32.numel() != R or not labels_i32.is_contiguous():
-        raise ValueError(f"lm_head_score: labels must be a contiguous [{R}] vector, got {tuple(labels_i32.shape)}")
-    if D % 32 or not 32 <= D <= LM_HEAD_SCORE_MAX_D:
-        raise NotImplementedError(f"lm_head_score: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {LM_HEAD_SCORE_MAX_D}")
-    ldx, ldw = _ld16("lm_head_score", x16, "x16"), _ld16("lm_head_score", w16, "w16")
-    fn = _fn("cclip_lm_head_score", x16, w16)
+    fname = "lm_head_score"
+    # this wrapper answers a wrong dtype, mixed dtypes and V >= 2^31 with a ValueError (the others: TypeError, NotImplementedError)
+    R, V, D = _pair16(fname, x16, "x16", w16, "w16", dtype_error=ValueError)
+    if w16.dtype != x16.dtype:
+        raise ValueError(f"{fname}: x16 and w16 must be bfloat16 or float16, both alike, got {x16.dtype} / {w16.dtype}")
     dev = x16.device
-    outs = []
-    for t, n, dt in ((logp, "logp", torch.float32), (lse, "lse", torch.float32), (pred, "pred", torch.int32),
-                     (pred_logit, "pred_logit", torch.float32)):
-        if t is None:
-            t = torch.empty(R, device=dev, dtype=dt)
-        if t.dtype != dt or t.device != dev or tuple(t.shape) != (R,) or not t.is_contiguous():
-            raise ValueError(f"lm_head_score: {n} must be a contiguous {dt} [{R}] vector on {dev}, got {t.dtype} {tuple(t.shape)}")
-        outs.append(t)
-    ws = torch.empty(lm_head_score_workspace(R, V) // 8, device=dev, dtype=torch.int64)
+    _dev_tensor(fname, labels_i32, "labels_i32", torch.int32, (R,), None, dtype_error=ValueError)
+    if V >= 2 ** 31:
+        raise ValueError(f"{fname}: V = {V}; column indices are int32")
+    _limits16(fname, D, "R V", (R, V), max_d=LM_HEAD_SCORE_MAX_D)
+    ldx, ldw = _ld16(fname, x16, "x16"), _ld16(fname, w16, "w16")
+    fn = _fn("cclip_lm_head_score", x16, w16)
+    outs = tuple(_out(fname, t, n, dt, (R,), dev) for t, n, dt in ((logp, "logp", torch.float32), (lse, "lse", torch.float32),
+                                                                   (pred, "pred", torch.int32), (pred_logit, "pred_logit", torch.float32)))
+    ws = _workspace(fname, None, lm_head_score_workspace(R, V), torch.int64, dev)
     check(fn(_p(x16), c_long(ldx), c_int(R), c_int(D), _p(w16), c_long(ldw), c_int(V), _p(labels_i32), c_int(ignore_index),
              _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _p(ws), _stream()), "cclip_lm_head_score")
-    return tuple(outs)
+    return outs
 
 
 CACHE_AFFINITY_MAX_C = 256
@@ -920,9 +996,22 @@ def _cache_segments_on(dev, class_off, class_len):
 
 def cache_affinity_workspace(Q: int, Np: int, C: int) -> int:
     """bytes of per-split class sums cclip_cache_affinity needs (Q * splits(Np) * C * 4; 0 for a problem it would refuse)"""
-    fn = lib.cclip_cache_affinity_workspace
-    fn.restype = c_long
-    return int(fn(c_int(Q), c_long(Np), c_int(C)))
+    return _query("cclip_cache_affinity_workspace", c_long, c_int(Q), c_long(Np), c_int(C))
+
+
+def _cache_operands(fname: str, q, g, class_off, class_len, beta, exclude):
+    """The argument checks cache_affinity and cache_affinity_backward share.  Returns (Q, Np, D, C, ldq, ldg, beta)."""
+    Q, Np, D = _pair16(fname, q, "q", g, "g")
+    C = _check_cache_segments(class_off, class_len, Np)
+    beta = _finite(fname, "beta", beta)
+    _limits16(fname, D, "Q Np", (Q, Np), max_d=CACHE_AFFINITY_MAX_D)
+    ldq, ldg = _ld16(fname, q, "q"), _ld16(fname, g, "g")
+    if g.dtype != q.dtype:
+        raise TypeError(f"{fname}: mixed bfloat16 / float16 operands")
+    if g.device != q.device:
+        raise TypeError(f"{fname}: q on {q.device}, g on {g.device}")
+    _dev_tensor(fname, exclude, "exclude", torch.int32, (Q,), q.device, optional=True)
+    return Q, Np, D, C, ldq, ldg, beta
 
 
 def cache_affinity(q, g, class_off, class_len, beta: float, *, exclude=None, out=None):
@@ -934,34 +1023,16 @@ def cache_affinity(q, g, class_off, class_len, beta: float, *, exclude=None, out
     Returns fp32 [Q, C]; an empty class is exactly 0.  The Q x Np matrix is never formed: the only scratch is the per-split
     workspace.  1 <= C <= 256, D % 32 == 0, 32 <= D <= 1024, Np < 2^31.  A query's row does not depend on Q.  Enqueues two
     launches; no host read."""
-    Q, Np, D = _pair16("cache_affinity", q, "q", g, "g")
-    C = _check_cache_segments(class_off, class_len, Np)
-    if Q < 1 or Np < 1:
-        raise ValueError(f"cache_affinity: empty operand (Q = {Q}, Np = {Np})")
-    beta = float(beta)
-    if beta != beta or beta in (float("inf"), float("-inf")):
-        raise ValueError(f"cache_affinity: beta must be finite, got {beta}")
-    if D % 32 or not 32 <= D <= CACHE_AFFINITY_MAX_D:
-        raise NotImplementedError(f"cache_affinity: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {CACHE_AFFINITY_MAX_D}")
-    ldq, ldg = _ld16("cache_affinity", q, "q"), _ld16("cache_affinity", g, "g")
-    fn = _fn("cclip_cache_affinity", q, g)
+    fname = "cache_affinity"
+    Q, Np, D, C, ldq, ldg, beta = _cache_operands(fname, q, g, class_off, class_len, beta, exclude)
     dev = q.device
-    if g.device != dev:
-        raise TypeError(f"cache_affinity: q on {dev}, g on {g.device}")
-    if exclude is not None:
-        _req(exclude, torch.int32, "exclude")
-        if tuple(exclude.shape) != (Q,) or not exclude.is_contiguous() or exclude.device != dev:
-            raise ValueError(f"cache_affinity: exclude must be a contiguous int32 [{Q}] vector on {dev}, got {tuple(exclude.shape)}")
-    if out is None:
-        out = torch.empty(Q, C, device=dev, dtype=torch.float32)
-    _req(out, torch.float32, "out")
-    if tuple(out.shape) != (Q, C) or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"cache_affinity: out must be a contiguous fp32 [{Q}, {C}] tensor on {dev}, got {tuple(out.shape)}")
+    out = _out(fname, out, "out", torch.float32, (Q, C), dev, host_error=TypeError, dtype_error=TypeError)
     off_d, len_d = _cache_segments_on(dev, class_off, class_len)
     nbytes = cache_affinity_workspace(Q, Np, C)
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
-    check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(Np), c_int(D), _p(off_d), _p(len_d), c_int(C),
-             c_float(beta), _p(exclude), _p(out), _p(ws), c_long(nbytes), _stream()), "cclip_cache_affinity")
+    ws = _workspace(fname, None, nbytes, torch.float32, dev)
+    check(_fn("cclip_cache_affinity", q, g)(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(Np), c_int(D), _p(off_d), _p(len_d),
+                                            c_int(C), c_float(beta), _p(exclude), _p(out), _p(ws), c_long(nbytes), _stream()),
+          "cclip_cache_affinity")
     return out
 
 
@@ -972,39 +1043,17 @@ def cache_affinity_backward(q, g, class_off, class_len, beta: float, dA, *, excl
     for the live rows and exactly +0.0 for the padding rows; every row is written (`out` needs no zero fill), a padding row's
     content (NaN) never reaches it, and the Q x Np matrix is never formed.  No atomics: two launches are bitwise equal.
     Enqueues two launches; no host read."""
-    Q, Np, D = _pair16("cache_affinity_backward", q, "q", g, "g")
-    C = _check_cache_segments(class_off, class_len, Np)
-    if Q < 1 or Np < 1:
-        raise ValueError(f"cache_affinity_backward: empty operand (Q = {Q}, Np = {Np})")
-    beta = float(beta)
-    if beta != beta or beta in (float("inf"), float("-inf")):
-        raise ValueError(f"cache_affinity_backward: beta must be finite, got {beta}")
-    if D % 32 or not 32 <= D <= CACHE_AFFINITY_MAX_D:
-        raise NotImplementedError(f"cache_affinity_backward: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {CACHE_AFFINITY_MAX_D}")
-    ldq, ldg = _ld16("cache_affinity_backward", q, "q"), _ld16("cache_affinity_backward", g, "g")
-    fn = _fn("cclip_cache_affinity_bwd", q, g)
+    fname = "cache_affinity_backward"
+    Q, Np, D, C, ldq, ldg, beta = _cache_operands(fname, q, g, class_off, class_len, beta, exclude)
     dev = q.device
-    if g.device != dev:
-        raise TypeError(f"cache_affinity_backward: q on {dev}, g on {g.device}")
-    if exclude is not None:
-        _req(exclude, torch.int32, "exclude")
-        if tuple(exclude.shape) != (Q,) or not exclude.is_contiguous() or exclude.device != dev:
-            raise ValueError(f"cache_affinity_backward: exclude must be a contiguous int32 [{Q}] vector on {dev}, got {tuple(exclude.shape)}")
-    _req(dA, torch.float32, "dA")
-    if tuple(dA.shape) != (Q, C) or not dA.is_contiguous() or dA.device != dev:
-        raise ValueError(f"cache_affinity_backward: dA must be a contiguous fp32 [{Q}, {C}] tensor on {dev}, got {tuple(dA.shape)}")
-    if out is None:
-        out = torch.empty(Np, D, device=dev, dtype=torch.float32)
-    _req(out, torch.float32, "out")
-    if tuple(out.shape) != (Np, D) or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"cache_affinity_backward: out must be a contiguous fp32 [{Np}, {D}] tensor on {dev}, got {tuple(out.shape)}")
+    _dev_tensor(fname, dA, "dA", torch.float32, (Q, C), dev)
+    out = _out(fname, out, "out", torch.float32, (Np, D), dev, host_error=TypeError, dtype_error=TypeError)
     off_d, len_d = _cache_segments_on(dev, class_off, class_len)
-    wfn = lib.cclip_cache_affinity_bwd_workspace
-    wfn.restype = c_long
-    nbytes = int(wfn(c_int(Q), c_int(C)))
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
-    check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(Np), c_int(D), _p(off_d), _p(len_d), c_int(C),
-             c_float(beta), _p(exclude), _p(dA), _p(out), _p(ws), c_long(nbytes), _stream()), "cclip_cache_affinity_bwd")
+    nbytes = _query("cclip_cache_affinity_bwd_workspace", c_long, c_int(Q), c_int(C))
+    ws = _workspace(fname, None, nbytes, torch.float32, dev)
+    check(_fn("cclip_cache_affinity_bwd", q, g)(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(Np), c_int(D), _p(off_d),
+                                                _p(len_d), c_int(C), c_float(beta), _p(exclude), _p(dA), _p(out), _p(ws), c_long(nbytes),
+                                                _stream()), "cclip_cache_affinity_bwd")
     return out
 
 
@@ -1012,28 +1061,14 @@ KMEANS_MAX_D = 1024
 
 
 def _kmeans_operands(fname: str, x, c, cn: str):
-    """The argument checks kmeans_assign and kmeans_update share (those of similarity_topk).  Returns (N, K, D, ldx, ldc)."""
+    """The argument checks of the wrappers that take rows x and centroids (or concepts) c.  Returns (N, K, D, ldx, ldc)."""
     N, K, D = _pair16(fname, x, "x", c, cn)
-    if N < 1 or K < 1:
-        raise ValueError(f"{fname}: empty operand (N = {N}, K = {K})")
-    if D % 32 or not 32 <= D <= KMEANS_MAX_D:
-        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {KMEANS_MAX_D}")
-    if N >= 2 ** 31 or K >= 2 ** 31:
-        raise NotImplementedError(f"{fname}: N = {N}, K = {K}; the kernel's row and centroid indices are int32 (< 2^31)")
+    _limits16(fname, D, "N K", (N, K), max_d=KMEANS_MAX_D)
     if c.device != x.device:
         raise TypeError(f"{fname}: x on {x.device}, {cn} on {c.device}")
     if c.dtype != x.dtype:
         raise TypeError(f"{fname}: mixed bfloat16 / float16 operands")
     return N, K, D, _ld16(fname, x, "x"), _ld16(fname, c, cn)
-
-
-def _kmeans_out(fname: str, t, n: str, shape, dtype, dev):
-    if t is None:
-        return torch.empty(*shape, device=dev, dtype=dtype)
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f"{fname}: {n} must be a contiguous {dtype} {list(shape)} tensor on {dev}, got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    return t
 
 
 def kmeans_assign(x, c, *, want_second: bool = False, out_assign=None, out_best=None, out_second=None):
@@ -1043,12 +1078,13 @@ def kmeans_assign(x, c, *, want_second: bool = False, out_assign=None, out_best=
     score (NaN if K == 1).  Equal scores go to the lower centroid, NaN ranks below every number; the three are bit for bit what
     similarity_topk(x, c, min(2, K)) returns.  The N x K matrix is never formed and there is no workspace.  D % 32 == 0,
     32 <= D <= 1024, N and K < 2^31.  A row's outputs do not depend on N.  Enqueues one launch; no host read."""
-    N, K, D, ldx, ldc = _kmeans_operands("kmeans_assign", x, c, "c")
+    fname = "kmeans_assign"
+    N, K, D, ldx, ldc = _kmeans_operands(fname, x, c, "c")
     dev = x.device
-    out_assign = _kmeans_out("kmeans_assign", out_assign, "out_assign", (N,), torch.int32, dev)
-    out_best = _kmeans_out("kmeans_assign", out_best, "out_best", (N,), torch.float32, dev)
+    out_assign = _out(fname, out_assign, "out_assign", torch.int32, (N,), dev)
+    out_best = _out(fname, out_best, "out_best", torch.float32, (N,), dev)
     if want_second or out_second is not None:
-        out_second = _kmeans_out("kmeans_assign", out_second, "out_second", (N,), torch.float32, dev)
+        out_second = _out(fname, out_second, "out_second", torch.float32, (N,), dev)
     fn = _fn("cclip_kmeans_assign", x, c)
     check(fn(_p(x), c_long(ldx), c_long(N), _p(c), c_long(ldc), c_long(K), c_int(D), _p(out_assign), _p(out_best), _p(out_second),
              _stream()), "cclip_kmeans_assign")
@@ -1057,9 +1093,7 @@ def kmeans_assign(x, c, *, want_second: bool = False, out_assign=None, out_best=
 
 def kmeans_update_workspace(N: int, K: int, D: int) -> int:
     """bytes of per-slab partial sums cclip_kmeans_update needs ((ceil(N / 256) + K) * D * 4; 0 for a problem it would refuse)"""
-    fn = lib.cclip_kmeans_update_workspace
-    fn.restype = c_long
-    return int(fn(c_long(N), c_long(K), c_int(D)))
+    return _query("cclip_kmeans_update_workspace", c_long, c_long(N), c_long(K), c_int(D))
 
 
 def kmeans_update(x, assign, K: int, prev_c, *, out_c=None, out_norm=None, check_range: bool = True):
@@ -1074,26 +1108,22 @@ def kmeans_update(x, assign, K: int, prev_c, *, out_c=None, out_norm=None, check
     ValueError, caught by ONE device-side min / max read back together and nothing else; check_range=False skips that read for
     an assign that comes straight from kmeans_assign against K centroids.  No float atomics: two calls are bitwise equal.
     Enqueues two launches."""
-    N, Kp, D, ldx, ldp = _kmeans_operands("kmeans_update", x, prev_c, "prev_c")
+    fname = "kmeans_update"
+    N, Kp, D, ldx, ldp = _kmeans_operands(fname, x, prev_c, "prev_c")
     K = int(K)
     if Kp != K:
-        raise ValueError(f"kmeans_update: prev_c has {Kp} rows for K = {K}")
+        raise ValueError(f"{fname}: prev_c has {Kp} rows for K = {K}")
     dev = x.device
-    if not isinstance(assign, torch.Tensor) or not assign.is_cuda:
-        raise TypeError(f"kmeans_update: assign: expected a cuda tensor, got {getattr(assign, 'device', type(assign))} (no CPU path)")
-    if assign.dtype not in (torch.int32, torch.int64):
-        raise TypeError(f"kmeans_update: assign must be int32 or int64, got {assign.dtype}")
-    if assign.dim() != 1 or assign.numel() != N or assign.device != dev:
-        raise ValueError(f"kmeans_update: assign must be a [{N}] vector on {dev}, got {tuple(assign.shape)} on {assign.device}")
-    if out_c is not None and (not isinstance(out_c, torch.Tensor) or out_c.dtype != x.dtype or out_c.device != dev or
-                              tuple(out_c.shape) != (K, D) or out_c.stride(1) != 1 or (K > 1 and out_c.stride(0) < D)):
-        raise ValueError(f"kmeans_update: out_c must be a {x.dtype} [{K}, {D}] tensor on {dev} with inner stride 1, got "
-                         f"{getattr(out_c, 'dtype', type(out_c))} {tuple(getattr(out_c, 'shape', ()))}")
-    out_norm = _kmeans_out("kmeans_update", out_norm, "out_norm", (K,), torch.float32, dev)
+    _dev_tensor(fname, assign, "assign", (torch.int32, torch.int64), (N,), dev, contiguous=False)
+    if out_c is not None:
+        _dev_tensor(fname, out_c, "out_c", x.dtype, (K, D), dev, contiguous=False, host_error=ValueError, dtype_error=ValueError)
+        if out_c.stride(1) != 1 or (K > 1 and out_c.stride(0) < D):
+            raise ValueError(f"{fname}: out_c must have inner stride 1 and rows that do not overlap, got strides {out_c.stride()}")
+    out_norm = _out(fname, out_norm, "out_norm", torch.float32, (K,), dev)
     if check_range:
         lo, hi = torch.stack([assign.min(), assign.max()]).tolist()             # the one host read
         if lo < 0 or hi >= K:
-            raise ValueError(f"kmeans_update: assign outside [0, {K}): min {lo}, max {hi}")
+            raise ValueError(f"{fname}: assign outside [0, {K}): min {lo}, max {hi}")
     if out_c is None:
         out_c = torch.empty(K, D, device=dev, dtype=x.dtype)
     ids, order = torch.sort(assign, stable=True)
@@ -1101,9 +1131,9 @@ def kmeans_update(x, assign, K: int, prev_c, *, out_c=None, out_norm=None, check
     counts = seg_off.diff().long()
     order = order.to(torch.int32)
     nbytes = kmeans_update_workspace(N, K, D)
-    ws = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
+    ws = _workspace(fname, None, nbytes, torch.float32, dev)
     fn = _fn("cclip_kmeans_update", x, prev_c)
-    ldo = out_c.stride(0) if K > 1 else max(D, out_c.stride(0))
+    ldo = _ld(out_c, multiple=1, at_least=D)
     check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(order), _p(seg_off), c_long(K), _p(prev_c), c_long(ldp), _p(out_c),
              c_long(ldo), _p(out_norm), _p(ws), c_long(nbytes), _stream()), "cclip_kmeans_update")
     return out_c, out_norm, counts
@@ -1114,46 +1144,22 @@ CORESET_FROM_PARTIALS, CORESET_SCAN_ONLY = -1, -2        # the `centre` modes of
 
 def coreset_blocks(N: int) -> int:
     """work-groups of one cclip_coreset_step launch = keys per partial buffer: min(1024, ceil(N / 64)); 0 for an N it would refuse"""
-    fn = lib.cclip_coreset_blocks
-    fn.restype = c_int
-    return int(fn(c_long(N)))
+    return _query("cclip_coreset_blocks", c_int, c_long(N))
 
 
 def coreset_workspace(N: int) -> int:
     """bytes of the two partial-key buffers cclip_coreset_greedy alternates between (2 * coreset_blocks(N) * 8)"""
-    fn = lib.cclip_coreset_workspace
-    fn.restype = c_long
-    return int(fn(c_long(N)))
+    return _query("cclip_coreset_workspace", c_long, c_long(N))
 
 
-def _coreset_state(fname: str, x, mind, owner, weight):
-    """The argument checks coreset_step and coreset_greedy share: x as for kmeans_assign, mind fp32 [N], owner int32 [N] and
-    weight fp32 [N] or None, contiguous on x's device.  Returns (N, D, ldx)."""
-    _req16(x, "x")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError(f"{fname}: x must be a 2-D view with inner stride 1, got {tuple(x.shape)} / {x.stride()}")
+def _rows16_state(fname: str, x, *vectors):
+    """The argument checks of the wrappers over one 16-bit operand x (as for kmeans_assign) and its per-row state `vectors`,
+    (t, name, dtype, optional) each: [N], contiguous on x's device.  Returns (N, D, ldx)."""
+    _view16(fname, ((x, "x", HALF_TYPES, None, False),))
     N, D = x.shape
-    if N < 1:
-        raise ValueError(f"{fname}: empty operand (N = {N})")
-    if D % 32 or not 32 <= D <= KMEANS_MAX_D:
-        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {KMEANS_MAX_D}")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
-    for t, n, dt in ((mind, "mind", torch.float32), (owner, "owner", torch.int32), (weight, "weight", torch.float32)):
-        if t is None and n == "weight":
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
-        if t.dtype != dt or t.device != x.device or tuple(t.shape) != (N,) or not t.is_contiguous():
-            raise ValueError(f"{fname}: {n} must be a contiguous {dt} [{N}] tensor on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    _limits16(fname, D, "N", (N,), max_d=KMEANS_MAX_D)
+    _dev_tensors(fname, x.device, [(t, n, dt, (N,), optional) for t, n, dt, optional in vectors], dtype_error=ValueError)
     return N, D, _ld16(fname, x, "x")
-
-
-def _coreset_keys(fname: str, t, n: str, shape, dev):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.device != dev or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError(f"{fname}: {n} must be a contiguous torch.int64 {list(shape)} tensor on {dev}, got "
-                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    return t
 
 
 def coreset_step(x, mind, owner, partial_out, *, centre: Optional[int] = None, partial_in=None, scan_only: bool = False, weight=None,
@@ -1169,28 +1175,29 @@ def coreset_step(x, mind, owner, partial_out, *, centre: Optional[int] = None, p
     eligible), larger weight * mind first, equal values to the lower row.  Returns (pick int32 [1], radius fp32 [1]) - pick -1
     and radius NaN when partial_in holds no eligible row - or (None, None) for scan_only.  D % 32 == 0, 32 <= D <= 1024,
     N < 2^31.  No atomics: two calls from equal states are bitwise equal.  Enqueues one launch; no host read."""
-    N, D, ldx = _coreset_state("coreset_step", x, mind, owner, weight)
+    fname = "coreset_step"
+    N, D, ldx = _rows16_state(fname, x, (mind, "mind", torch.float32, False), (owner, "owner", torch.int32, False),
+                              (weight, "weight", torch.float32, True))
     dev, P = x.device, coreset_blocks(N)
-    _coreset_keys("coreset_step", partial_out, "partial_out", (P,), dev)
+    _dev_tensors(fname, dev, ((partial_out, "partial_out", torch.int64, (P,), False), (partial_in, "partial_in", torch.int64, (P,), True)),
+                 host_error=ValueError, dtype_error=ValueError)
     if scan_only:
         if centre is not None:
-            raise ValueError("coreset_step: scan_only takes no centre")
+            raise ValueError(f"{fname}: scan_only takes no centre")
         mode = CORESET_SCAN_ONLY
     elif centre is None:
         if partial_in is None:
-            raise ValueError("coreset_step: without a centre the pick comes from partial_in")
+            raise ValueError(f"{fname}: without a centre the pick comes from partial_in")
         mode = CORESET_FROM_PARTIALS
     else:
         mode = int(centre)
         if not 0 <= mode < N:
-            raise ValueError(f"coreset_step: centre = {centre} outside [0, {N})")
-    if partial_in is not None:
-        _coreset_keys("coreset_step", partial_in, "partial_in", (P,), dev)
-        if partial_in.data_ptr() == partial_out.data_ptr():
-            raise ValueError("coreset_step: partial_in and partial_out must be different buffers (other work-groups still read the old keys)")
+            raise ValueError(f"{fname}: centre = {centre} outside [0, {N})")
+    if partial_in is not None and partial_in.data_ptr() == partial_out.data_ptr():
+        raise ValueError(f"{fname}: partial_in and partial_out must be different buffers (other work-groups still read the old keys)")
     if not scan_only:
-        out_pick = _kmeans_out("coreset_step", out_pick, "out_pick", (1,), torch.int32, dev)
-        out_radius = _kmeans_out("coreset_step", out_radius, "out_radius", (1,), torch.float32, dev)
+        out_pick = _out(fname, out_pick, "out_pick", torch.int32, (1,), dev)
+        out_radius = _out(fname, out_radius, "out_radius", torch.float32, (1,), dev)
     else:
         out_pick = out_radius = None
     fn = _fn("cclip_coreset_step", x)
@@ -1206,24 +1213,26 @@ def coreset_greedy(x, mind, owner, m: int, *, first: Optional[int] = None, works
     int in [0, N): pick 0 takes that row; first None: workspace[0] already holds the keys of the state (a scan_only step into
     it).  Returns (picks int32 [m], radius fp32 [m], workspace): bit for bit what m single steps give; the state's keys end in
     workspace[m % 2].  Once no eligible row is left the picks are -1 with radius NaN.  m == 0 launches nothing.  No host read."""
-    N, D, ldx = _coreset_state("coreset_greedy", x, mind, owner, weight)
+    fname = "coreset_greedy"
+    N, D, ldx = _rows16_state(fname, x, (mind, "mind", torch.float32, False), (owner, "owner", torch.int32, False),
+                              (weight, "weight", torch.float32, True))
     dev, P = x.device, coreset_blocks(N)
     m = int(m)
     if not 0 <= m <= N:
-        raise ValueError(f"coreset_greedy: m = {m} outside [0, {N}]")
+        raise ValueError(f"{fname}: m = {m} outside [0, {N}]")
     if first is None:
         if workspace is None:
-            raise ValueError("coreset_greedy: without a first row workspace[0] must hold the keys of the state")
+            raise ValueError(f"{fname}: without a first row workspace[0] must hold the keys of the state")
         mode = CORESET_FROM_PARTIALS
     else:
         mode = int(first)
         if not 0 <= mode < N:
-            raise ValueError(f"coreset_greedy: first = {first} outside [0, {N})")
-    if workspace is None:
+            raise ValueError(f"{fname}: first = {first} outside [0, {N})")
+    if workspace is None:                                    # the two key buffers by shape, zeroed: not scratch sized in bytes
         workspace = torch.zeros(2, P, device=dev, dtype=torch.int64)
-    _coreset_keys("coreset_greedy", workspace, "workspace", (2, P), dev)
-    out_picks = _kmeans_out("coreset_greedy", out_picks, "out_picks", (m,), torch.int32, dev)
-    out_radius = _kmeans_out("coreset_greedy", out_radius, "out_radius", (m,), torch.float32, dev)
+    _dev_tensor(fname, workspace, "workspace", torch.int64, (2, P), dev, host_error=ValueError, dtype_error=ValueError)
+    out_picks = _out(fname, out_picks, "out_picks", torch.int32, (m,), dev)
+    out_radius = _out(fname, out_radius, "out_radius", torch.float32, (m,), dev)
     fn = _fn("cclip_coreset_greedy", x)
     check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(weight), _p(mind), _p(owner), c_int(mode), c_long(m), _p(out_picks),
              _p(out_radius), _p(workspace), c_long(workspace.numel() * 8), _stream()), "cclip_coreset_greedy")
@@ -1233,39 +1242,12 @@ def coreset_greedy(x, mind, owner, m: int, *, first: Optional[int] = None, works
 def mst_workspace(N: int) -> int:
     """bytes of scratch cclip_mst_boruvka needs (32 N + 256: the row keys, the component keys, the parents, two label buffers,
     the round flags); 0 for an N it would refuse"""
-    fn = lib.cclip_mst_workspace
-    fn.restype = c_long
-    return int(fn(c_long(N)))
+    return _query("cclip_mst_workspace", c_long, c_long(N))
 
 
 def mreach_nearest_splits(N: int) -> int:
     """gallery splits of one cclip_mreach_nearest launch (a function of N alone); 0 for an N it would refuse"""
-    fn = lib.cclip_mreach_nearest_splits
-    fn.restype = c_int
-    return int(fn(c_long(N)))
-
-
-def _mreach_operands(fname: str, x, core):
-    """The argument checks mreach_nearest and mst_boruvka share: x as for kmeans_assign, core fp32 [N] contiguous on x's device.
-    Returns (N, D, ldx)."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise TypeError(f"{fname}: x: expected a cuda tensor, got {getattr(x, 'device', type(x))} (no CPU path)")
-    _req16(x, "x")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError(f"{fname}: x must be a 2-D view with inner stride 1, got {tuple(x.shape)} / {x.stride()}")
-    N, D = x.shape
-    if N < 1:
-        raise ValueError(f"{fname}: empty operand (N = {N})")
-    if D % 32 or not 32 <= D <= KMEANS_MAX_D:
-        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {KMEANS_MAX_D}")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
-    if not isinstance(core, torch.Tensor) or not core.is_cuda:
-        raise TypeError(f"{fname}: core: expected a cuda tensor, got {getattr(core, 'device', type(core))} (no CPU path)")
-    if core.dtype != torch.float32 or core.device != x.device or tuple(core.shape) != (N,) or not core.is_contiguous():
-        raise ValueError(f"{fname}: core must be a contiguous torch.float32 [{N}] tensor on {x.device}, got {core.dtype} "
-                         f"{tuple(core.shape)} on {core.device}")
-    return N, D, _ld16(fname, x, "x")
+    return _query("cclip_mreach_nearest_splits", c_int, c_long(N))
 
 
 def mreach_nearest(x, core, comp, *, out=None):
@@ -1276,13 +1258,10 @@ def mreach_nearest(x, core, comp, *, out=None):
     number - or 0 where no such row exists.  The score carries the bits similarity_topk returns for the pair; the N x N matrix
     is never formed.  Integer atomics only where the gallery is split: two calls are bitwise equal.  D % 32 == 0,
     32 <= D <= 1024, N < 2^31.  No host read."""
-    N, D, ldx = _mreach_operands("mreach_nearest", x, core)
-    if not isinstance(comp, torch.Tensor) or not comp.is_cuda:
-        raise TypeError(f"mreach_nearest: comp: expected a cuda tensor, got {getattr(comp, 'device', type(comp))} (no CPU path)")
-    if comp.dtype != torch.int32 or comp.device != x.device or tuple(comp.shape) != (N,) or not comp.is_contiguous():
-        raise ValueError(f"mreach_nearest: comp must be a contiguous torch.int32 [{N}] tensor on {x.device}, got {comp.dtype} "
-                         f"{tuple(comp.shape)} on {comp.device}")
-    out = _kmeans_out("mreach_nearest", out, "out", (N,), torch.int64, x.device)
+    fname = "mreach_nearest"
+    N, D, ldx = _rows16_state(fname, x, (core, "core", torch.float32, False))
+    _dev_tensor(fname, comp, "comp", torch.int32, (N,), x.device, dtype_error=ValueError)
+    out = _out(fname, out, "out", torch.int64, (N,), x.device)
     fn = _fn("cclip_mreach_nearest", x)
     check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(core), _p(comp), _p(out), _stream()), "cclip_mreach_nearest")
     return out
@@ -1295,14 +1274,10 @@ def mst_boruvka(x, core, *, workspace=None):
     m = NaN (N == 1: that slot alone).  ceil(log2 N) Boruvka rounds are enqueued by one native call; a device flag ends the
     work once one component is left.  workspace: an int64 tensor of at least mst_workspace(N) bytes.  Two calls are bitwise
     equal.  No host read."""
-    N, D, ldx = _mreach_operands("mst_boruvka", x, core)
+    fname = "mst_boruvka"
+    N, D, ldx = _rows16_state(fname, x, (core, "core", torch.float32, False))
     dev = x.device
-    nbytes = mst_workspace(N)
-    if workspace is None:
-        workspace = torch.empty((nbytes + 7) // 8, device=dev, dtype=torch.int64)
-    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.int64 or workspace.device != dev or
-            not workspace.is_contiguous() or workspace.numel() * 8 < nbytes):
-        raise ValueError(f"mst_boruvka: workspace must be a contiguous torch.int64 tensor of at least {nbytes} bytes on {dev}")
+    workspace = _workspace(fname, workspace, mst_workspace(N), torch.int64, dev)
     u = torch.empty(N, device=dev, dtype=torch.int32)
     v = torch.empty(N, device=dev, dtype=torch.int32)
     m = torch.empty(N, device=dev, dtype=torch.float32)
@@ -1319,51 +1294,25 @@ PROBE_MAX_D = 1024
 def probe_workspace(N: int, C: int, D: int) -> int:
     """bytes of workspace cclip_probe_forward / cclip_probe_backward need (the hi + lo image of W, the per-slot partials of dW
     and db, the reduction tree: include/cclip_hip.h states the closed form; 0 for a problem they would refuse)"""
-    fn = lib.cclip_probe_workspace
-    fn.restype = c_long
-    return int(fn(c_long(N), c_int(C), c_int(D)))
+    return _query("cclip_probe_workspace", c_long, c_long(N), c_int(C), c_int(D))
 
 
 def probe_parts(N: int, C: int, D: int) -> int:
     """the number of partial slots the backward's rows are split into: a function of (N, C, D) alone"""
-    return int(lib.cclip_probe_parts(c_long(N), c_int(C), c_int(D)))
+    return _query("cclip_probe_parts", c_int, c_long(N), c_int(C), c_int(D))
 
 
 def _probe_operands(fname: str, x, W, bias, labels, row_weight):
     """The argument checks probe_forward and probe_backward share.  Returns (N, C, D, ldx)."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise TypeError(f"{fname}: x: expected a cuda tensor, got {getattr(x, 'device', type(x))} (no CPU path)")
-    _req16(x, "x")
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError(f"{fname}: x must be a 2-D view with inner stride 1, got {tuple(x.shape)} / {x.stride()}")
-    N, D = x.shape
-    dev = x.device
-    if not isinstance(W, torch.Tensor) or W.dtype != torch.float32 or W.device != dev:
-        raise TypeError(f"{fname}: W: expected fp32 on {dev}, got {getattr(W, 'device', type(W))} {getattr(W, 'dtype', '')}")
-    if W.dim() != 2 or W.shape[1] != D or not W.is_contiguous():
-        raise ValueError(f"{fname}: W must be a contiguous [C, {D}] matrix, got {tuple(W.shape)}")
-    C = W.shape[0]
-    if N < 1:
-        raise ValueError(f"{fname}: empty operand (N = {N})")
+    _view16(fname, ((x, "x", HALF_TYPES, None, False),))
+    (N, D), dev = x.shape, x.device
+    C = _dev_tensor(fname, W, "W", torch.float32, (None, D), dev, device_error=TypeError).shape[0]   # an operand, like c and g
+    _limits16(fname, D, "N", (N,), max_d=PROBE_MAX_D)
     if not 2 <= C <= PROBE_MAX_C:
         raise NotImplementedError(f"{fname}: C = {C}; the kernel takes 2 .. {PROBE_MAX_C} classes")
-    if D % 32 or not 32 <= D <= PROBE_MAX_D:
-        raise NotImplementedError(f"{fname}: D = {D}; the kernel needs D % 32 == 0 and 32 <= D <= {PROBE_MAX_D}")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
-    for t, n, shape, dtype in ((bias, "bias", (C,), torch.float32), (labels, "labels", (N,), torch.int32),
-                               (row_weight, "row_weight", (N,), torch.float32)):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"{fname}: {n} must be a contiguous {dtype} {list(shape)} vector on {dev}, got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+    _dev_tensors(fname, dev, ((bias, "bias", torch.float32, (C,), True), (labels, "labels", torch.int32, (N,), True),
+                              (row_weight, "row_weight", torch.float32, (N,), True)), host_error=ValueError, dtype_error=ValueError)
     return N, C, D, _ld16(fname, x, "x")
-
-
-def _probe_ws(N: int, C: int, D: int, dev):
-    nbytes = probe_workspace(N, C, D)
-    return torch.empty(nbytes // 4, device=dev, dtype=torch.float32), nbytes
 
 
 def probe_forward(x, W, bias, labels, row_weight=None, logits: bool = False, out=None):
@@ -1374,18 +1323,20 @@ def probe_forward(x, W, bias, labels, row_weight=None, logits: bool = False, out
     row_weight[n] * (lse[n] - z[n, labels[n]]) and exactly +0.0 for an ignored or zero-weight row, pred the argmax (ties to the
     lower class, NaN lowest).  `out`: a tuple of tensors to write those into.  The N x C matrix is written only with logits=True.
     A row's outputs do not depend on N.  2 <= C <= 256, D % 32 == 0, 32 <= D <= 1024.  Enqueues two launches; no host read."""
-    N, C, D, ldx = _probe_operands("probe_forward", x, W, bias, labels, row_weight)
+    fname = "probe_forward"
+    N, C, D, ldx = _probe_operands(fname, x, W, bias, labels, row_weight)
     dev = x.device
     o = tuple(out) if out is not None else (None, None, None, None)
     if len(o) not in (3, 4):
-        raise ValueError("probe_forward: out must be (lse, loss, pred) or (lse, loss, pred, logits)")
-    lse = _kmeans_out("probe_forward", o[0], "lse", (N,), torch.float32, dev)
-    loss = _kmeans_out("probe_forward", o[1], "loss", (N,), torch.float32, dev)
-    pred = _kmeans_out("probe_forward", o[2], "pred", (N,), torch.int32, dev)
+        raise ValueError(f"{fname}: out must be (lse, loss, pred) or (lse, loss, pred, logits)")
+    lse = _out(fname, o[0], "lse", torch.float32, (N,), dev)
+    loss = _out(fname, o[1], "loss", torch.float32, (N,), dev)
+    pred = _out(fname, o[2], "pred", torch.int32, (N,), dev)
     z = None
     if logits or (len(o) == 4 and o[3] is not None):
-        z = _kmeans_out("probe_forward", o[3] if len(o) == 4 else None, "logits", (N, C), torch.float32, dev)
-    ws, nbytes = _probe_ws(N, C, D, dev)
+        z = _out(fname, o[3] if len(o) == 4 else None, "logits", torch.float32, (N, C), dev)
+    nbytes = probe_workspace(N, C, D)
+    ws = _workspace(fname, None, nbytes, torch.float32, dev)
     fn = _fn("cclip_probe_forward", x)
     check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(W), _p(bias), c_int(C), _p(labels), _p(row_weight), _p(lse), _p(loss),
              _p(pred), _p(z), _p(ws), c_long(nbytes), _stream()), "cclip_probe_forward")
@@ -1401,29 +1352,24 @@ def probe_backward(x, W, bias, labels, lse, scale: float, l2: float, row_weight=
     rows' weights), the caller's.  `out`: (dW, db) or (dW, db, objective) to write into.  The rows are split over the grid and
     the partial sums merged in a fixed order: no atomics, two calls are bitwise equal.  Enqueues three launches, four with the
     objective; no host read."""
-    N, C, D, ldx = _probe_operands("probe_backward", x, W, bias, labels, row_weight)
+    fname = "probe_backward"
+    N, C, D, ldx = _probe_operands(fname, x, W, bias, labels, row_weight)
     dev = x.device
-    scale, l2 = float(scale), float(l2)
-    for v, n in ((scale, "scale"), (l2, "l2")):
-        if v != v or v in (float("inf"), float("-inf")) or v < 0:
-            raise ValueError(f"probe_backward: {n} must be finite and >= 0, got {v}")
-    for t, n in ((lse, "lse"), (loss, "loss")):
-        if t is None and n == "loss":
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (N,) or not t.is_contiguous():
-            raise ValueError(f"probe_backward: {n} must be probe_forward's contiguous fp32 [{N}] vector on {dev}, got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    scale, l2 = _finite(fname, "scale", scale, nonneg=True), _finite(fname, "l2", l2, nonneg=True)
+    _dev_tensors(fname, dev, ((lse, "lse", torch.float32, (N,), False), (loss, "loss", torch.float32, (N,), True)),
+                 host_error=ValueError, dtype_error=ValueError)
     o = tuple(out) if out is not None else (None, None, None)
     if len(o) not in (2, 3):
-        raise ValueError("probe_backward: out must be (dW, db) or (dW, db, objective)")
-    dW = _kmeans_out("probe_backward", o[0], "dW", (C, D), torch.float32, dev)
-    db = _kmeans_out("probe_backward", o[1], "db", (C,), torch.float32, dev)
+        raise ValueError(f"{fname}: out must be (dW, db) or (dW, db, objective)")
+    dW = _out(fname, o[0], "dW", torch.float32, (C, D), dev)
+    db = _out(fname, o[1], "db", torch.float32, (C,), dev)
     obj = None
     if loss is not None:
-        obj = _kmeans_out("probe_backward", o[2] if len(o) == 3 else None, "objective", (1,), torch.float32, dev)
+        obj = _out(fname, o[2] if len(o) == 3 else None, "objective", torch.float32, (1,), dev)
     elif len(o) == 3 and o[2] is not None:
-        raise ValueError("probe_backward: an objective output needs `loss`")
-    ws, nbytes = _probe_ws(N, C, D, dev)
+        raise ValueError(f"{fname}: an objective output needs `loss`")
+    nbytes = probe_workspace(N, C, D)
+    ws = _workspace(fname, None, nbytes, torch.float32, dev)
     fn = _fn("cclip_probe_backward", x)
     check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(W), _p(bias), c_int(C), _p(labels), _p(row_weight), _p(lse), _p(loss),
              c_float(scale), c_float(l2), _p(dW), _p(db), _p(obj), _p(ws), c_long(nbytes), _stream()), "cclip_probe_backward")
@@ -1436,17 +1382,12 @@ TSNE_SPLIT_MAX = 16        # the most splits of its j range
 TSNE_BISECT_STEPS = 100
 
 
-def _tsne_f32(fname: str, t, n: str, shape, dev=None):
-    """A contiguous fp32 device tensor of the given shape (None in shape = any size)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{fname}: {n} must be float32, got {t.dtype}")
-    if t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)) or not t.is_contiguous() or \
-            (dev is not None and t.device != dev):
-        raise ValueError(f"{fname}: {n} must be a contiguous float32 {list(shape)} tensor on {dev or 'the device'}, got "
-                         f"{tuple(t.shape)} / {t.stride()} on {t.device}")
-    return t
+def _rows_int32(fname: str, N: int) -> int:
+    if N < 1:
+        raise ValueError(f"{fname}: empty operand (N = {N})")
+    if N >= 2 ** 31:
+        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    return N
 
 
 def tsne_affinities(scores, perplexity: float, *, out_P=None, out_beta=None):
@@ -1454,28 +1395,23 @@ def tsne_affinities(scores, perplexity: float, *, out_P=None, out_beta=None):
     similarities of every row's k nearest other unit rows (inner stride 1; a row-strided view is fine), 1 <= k <= 63,
     1 < perplexity < k.  Returns (P fp32 [N, k] with rows summing to 1, beta fp32 [N]): beta by 100 fixed bisection steps so
     that the row's entropy is log(perplexity).  One launch; no host read."""
-    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
-        raise TypeError(f"tsne_affinities: scores: expected a cuda tensor, got {getattr(scores, 'device', type(scores))} (no CPU path)")
-    if scores.dtype != torch.float32:
-        raise TypeError(f"tsne_affinities: scores must be float32, got {scores.dtype}")
+    fname = "tsne_affinities"
+    _dev_tensor(fname, scores, "scores", torch.float32, None, None, contiguous=False)
     if scores.dim() != 2 or scores.stride(1) != 1:
-        raise ValueError(f"tsne_affinities: scores must be a 2-D view with inner stride 1, got {tuple(scores.shape)} / {scores.stride()}")
+        raise ValueError(f"{fname}: scores must be a 2-D view with inner stride 1, got {tuple(scores.shape)} / {scores.stride()}")
     N, k = scores.shape
-    if N < 1:
-        raise ValueError("tsne_affinities: empty operand (N = 0)")
     if not 1 <= k <= TSNE_MAX_K:
-        raise ValueError(f"tsne_affinities: k = {k} outside the kernel's range 1 .. {TSNE_MAX_K}")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"tsne_affinities: N = {N}; the kernel's row index is int32 (N < 2^31)")
+        raise ValueError(f"{fname}: k = {k} outside the kernel's range 1 .. {TSNE_MAX_K}")
+    _rows_int32(fname, N)
     perplexity = float(perplexity)
     if not 1.0 < perplexity < k:
-        raise ValueError(f"tsne_affinities: perplexity = {perplexity} must lie inside (1, k = {k})")
-    ld = scores.stride(0) if N > 1 else max(k, scores.stride(0))
+        raise ValueError(f"{fname}: perplexity = {perplexity} must lie inside (1, k = {k})")
+    ld = _ld(scores, multiple=1, at_least=k)
     if ld < k:
-        raise ValueError(f"tsne_affinities: row stride {ld} below k = {k}")
+        raise ValueError(f"{fname}: row stride {ld} below k = {k}")
     dev = scores.device
-    out_P = _kmeans_out("tsne_affinities", out_P, "out_P", (N, k), torch.float32, dev)
-    out_beta = _kmeans_out("tsne_affinities", out_beta, "out_beta", (N,), torch.float32, dev)
+    out_P = _out(fname, out_P, "out_P", torch.float32, (N, k), dev)
+    out_beta = _out(fname, out_beta, "out_beta", torch.float32, (N,), dev)
     check(lib.cclip_tsne_affinities(_p(scores), c_long(ld), c_long(N), c_int(k), c_float(perplexity), _p(out_P), _p(out_beta),
                                     _stream()), "cclip_tsne_affinities")
     return out_P, out_beta
@@ -1483,14 +1419,12 @@ def tsne_affinities(scores, perplexity: float, *, out_P=None, out_beta=None):
 
 def tsne_repulsion_splits(N: int) -> int:
     """the number of runs the repulsion kernel cuts its j range into: a function of N alone (0 for an N it would refuse)"""
-    return int(lib.cclip_tsne_repulsion_splits(c_long(N)))
+    return _query("cclip_tsne_repulsion_splits", c_int, c_long(N))
 
 
 def tsne_repulsion_workspace(N: int) -> int:
     """bytes of per-(split, row) partials cclip_tsne_repulsion needs ((3 N splits + ceil(N / 256)) * 4; 0 for an N it would refuse)"""
-    fn = lib.cclip_tsne_repulsion_workspace
-    fn.restype = c_long
-    return int(fn(c_long(N)))
+    return _query("cclip_tsne_repulsion_workspace", c_long, c_long(N))
 
 
 def tsne_repulsion(y, *, out_zrow=None, out_rep=None, out_z=None, workspace=None):
@@ -1498,26 +1432,29 @@ def tsne_repulsion(y, *, out_zrow=None, out_rep=None, out_z=None, workspace=None
     w_ij = 1 / (1 + |y_i - y_j|^2) over all j != i, returns (zrow fp32 [N] = sum_j w_ij, rep fp32 [N, 2] = sum_j w_ij^2
     (y_i - y_j), z fp32 [1] = sum_i zrow[i]).  No N x N matrix, no float atomics: two calls are bitwise equal.  `workspace`: a
     float32 device vector of at least tsne_repulsion_workspace(N) bytes to reuse.  Three launches; no host read."""
-    _tsne_f32("tsne_repulsion", y, "y", (None, 2))
-    N = y.shape[0]
-    if N < 1:
-        raise ValueError("tsne_repulsion: empty operand (N = 0)")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"tsne_repulsion: N = {N}; the kernel's row index is int32 (N < 2^31)")
+    fname = "tsne_repulsion"
+    N = _rows_int32(fname, _dev_tensor(fname, y, "y", torch.float32, (None, 2), None).shape[0])
     dev = y.device
-    out_zrow = _kmeans_out("tsne_repulsion", out_zrow, "out_zrow", (N,), torch.float32, dev)
-    out_rep = _kmeans_out("tsne_repulsion", out_rep, "out_rep", (N, 2), torch.float32, dev)
-    out_z = _kmeans_out("tsne_repulsion", out_z, "out_z", (1,), torch.float32, dev)
-    nbytes = tsne_repulsion_workspace(N)
-    if workspace is None:
-        workspace = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
-    else:
-        _tsne_f32("tsne_repulsion", workspace, "workspace", (None,), dev)
-        if workspace.numel() * 4 < nbytes:
-            raise ValueError(f"tsne_repulsion: workspace has {workspace.numel() * 4} bytes, {nbytes} needed")
+    out_zrow = _out(fname, out_zrow, "out_zrow", torch.float32, (N,), dev)
+    out_rep = _out(fname, out_rep, "out_rep", torch.float32, (N, 2), dev)
+    out_z = _out(fname, out_z, "out_z", torch.float32, (1,), dev)
+    workspace = _workspace(fname, workspace, tsne_repulsion_workspace(N), torch.float32, dev, flat=True, host_error=TypeError)
     check(lib.cclip_tsne_repulsion(_p(y), c_long(N), _p(out_zrow), _p(out_rep), _p(out_z), _p(workspace),
                                    c_long(workspace.numel() * 4), _stream()), "cclip_tsne_repulsion")
     return out_zrow, out_rep, out_z
+
+
+def _csr(fname: str, N: int, dev, offsets, cols, vals, *, int32_nnz: bool) -> int:
+    """A graph over N rows as CSR: offsets int64 [N + 1], cols int32 [nnz], vals fp32 [nnz], contiguous on dev.  Returns nnz;
+    int32_nnz: for a kernel whose entry index is int32."""
+    _dev_tensors(fname, dev, ((offsets, "offsets", torch.int64, (N + 1,), False), (cols, "cols", torch.int32, 1, False),
+                              (vals, "vals", torch.float32, 1, False)))
+    nnz = cols.numel()
+    if vals.numel() != nnz:
+        raise ValueError(f"{fname}: cols has {nnz} entries, vals {vals.numel()}")
+    if int32_nnz and (N >= 2 ** 31 or nnz >= 2 ** 31):
+        raise NotImplementedError(f"{fname}: N = {N}, nnz = {nnz}; the kernel's indices are int32 (both < 2^31)")
+    return nnz
 
 
 def tsne_step(y, vel, gains, offsets, cols, vals, rep, z, *, exaggeration: float = 1.0, momentum: float = 0.8,
@@ -1528,39 +1465,22 @@ def tsne_step(y, vel, gains, offsets, cols, vals, rep, z, *, exaggeration: float
     than y, kl_row fp32 [N] the rows' KL terms with the un-exaggerated P.  update=False only evaluates kl_row (vel, gains and
     rep may be None; y_out is None).  One launch; no host read."""
     fname = "tsne_step"
-    _tsne_f32(fname, y, "y", (None, 2))
-    N, dev = y.shape[0], y.device
-    if N < 1:
-        raise ValueError("tsne_step: empty operand (N = 0)")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"tsne_step: N = {N}; the kernel's row index is int32 (N < 2^31)")
-    for t, n, dt, shape in ((offsets, "offsets", torch.int64, (N + 1,)), (cols, "cols", torch.int32, (None,)),
-                            (vals, "vals", torch.float32, (None,))):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
-        if t.dtype != dt:
-            raise TypeError(f"{fname}: {n} must be {dt}, got {t.dtype}")
-        if t.dim() != 1 or (shape[0] is not None and t.numel() != shape[0]) or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"{fname}: {n} must be a contiguous {dt} {list(shape)} vector on {dev}, got {tuple(t.shape)} on {t.device}")
-    nnz = cols.numel()
-    if vals.numel() != nnz:
-        raise ValueError(f"{fname}: cols has {nnz} entries, vals {vals.numel()}")
-    _tsne_f32(fname, z, "z", (1,), dev)
-    for v, n in ((exaggeration, "exaggeration"), (momentum, "momentum"), (learning_rate, "learning_rate"), (min_gain, "min_gain")):
-        v = float(v)
-        if v != v or v in (float("inf"), float("-inf")) or v < 0:
-            raise ValueError(f"{fname}: {n} must be finite and >= 0, got {v}")
+    N = _rows_int32(fname, _dev_tensor(fname, y, "y", torch.float32, (None, 2), None).shape[0])
+    dev = y.device
+    nnz = _csr(fname, N, dev, offsets, cols, vals, int32_nnz=False)
+    _dev_tensor(fname, z, "z", torch.float32, (1,), dev)
+    exaggeration, momentum, learning_rate, min_gain = (_finite(fname, n, v, nonneg=True) for n, v in (
+        ("exaggeration", exaggeration), ("momentum", momentum), ("learning_rate", learning_rate), ("min_gain", min_gain)))
     if update:
-        for t, n in ((vel, "vel"), (gains, "gains"), (rep, "rep")):
-            _tsne_f32(fname, t, n, (N, 2), dev)
-        out_y = _kmeans_out(fname, out_y, "out_y", (N, 2), torch.float32, dev)
+        _dev_tensors(fname, dev, [(t, n, torch.float32, (N, 2), False) for t, n in ((vel, "vel"), (gains, "gains"), (rep, "rep"))])
+        out_y = _out(fname, out_y, "out_y", torch.float32, (N, 2), dev)
         if out_y.data_ptr() == y.data_ptr():
             raise ValueError(f"{fname}: out_y must not be y: other rows still read y")
     else:
         if out_y is not None:
             raise ValueError(f"{fname}: update=False writes no out_y")
         vel = gains = rep = None
-    out_kl = _kmeans_out(fname, out_kl, "out_kl", (N,), torch.float32, dev)
+    out_kl = _out(fname, out_kl, "out_kl", torch.float32, (N,), dev)
     check(lib.cclip_tsne_step(_p(y), _p(vel), _p(gains), c_long(N), _p(offsets), _p(cols), _p(vals), c_long(nnz), _p(rep), _p(z),
                               c_float(exaggeration), c_float(momentum), c_float(learning_rate), c_float(min_gain), _p(out_y),
                               _p(out_kl), _stream()), "cclip_tsne_step")
@@ -1572,25 +1492,7 @@ LABEL_SPREAD_MAX_C = 1024
 
 def label_spread_groups(C: int) -> int:
     """the number of edge groups a row's entries are dealt over in label_spread_step: a function of C alone (0 for a C it would refuse)"""
-    return int(lib.cclip_label_spread_groups(c_int(C)))
-
-
-def _label_csr(fname: str, N: int, dev, offsets, cols, vals) -> int:
-    """offsets int64 [N + 1], cols int32 [nnz], vals fp32 [nnz], contiguous on dev; returns nnz"""
-    for t, n, dt, shape in ((offsets, "offsets", torch.int64, (N + 1,)), (cols, "cols", torch.int32, (None,)),
-                            (vals, "vals", torch.float32, (None,))):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
-        if t.dtype != dt:
-            raise TypeError(f"{fname}: {n} must be {dt}, got {t.dtype}")
-        if t.dim() != 1 or (shape[0] is not None and t.numel() != shape[0]) or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"{fname}: {n} must be a contiguous {dt} {list(shape)} vector on {dev}, got {tuple(t.shape)} on {t.device}")
-    nnz = cols.numel()
-    if vals.numel() != nnz:
-        raise ValueError(f"{fname}: cols has {nnz} entries, vals {vals.numel()}")
-    if N >= 2 ** 31 or nnz >= 2 ** 31:
-        raise NotImplementedError(f"{fname}: N = {N}, nnz = {nnz}; the kernel's indices are int32 (both < 2^31)")
-    return nnz
+    return _query("cclip_label_spread_groups", c_int, c_int(C))
 
 
 def label_graph_normalize(offsets, cols, vals, *, out_deg=None, out_vals=None):
@@ -1599,29 +1501,24 @@ def label_graph_normalize(offsets, cols, vals, *, out_deg=None, out_vals=None):
     sums; vals_out fp32 [nnz] = (vals r_i) r_j with r = 1 / sqrt(deg), 0 where deg is not > 0).  out_vals may be `vals`.
     Two launches; no host read."""
     fname = "label_graph_normalize"
-    if not isinstance(offsets, torch.Tensor) or not offsets.is_cuda:
-        raise TypeError(f"{fname}: offsets: expected a cuda tensor, got {getattr(offsets, 'device', type(offsets))} (no CPU path)")
+    _dev_tensor(fname, offsets, "offsets", None, None, None, contiguous=False)
     N, dev = offsets.numel() - 1, offsets.device
     if N < 1:
         raise ValueError(f"{fname}: empty operand (N = {N})")
-    nnz = _label_csr(fname, N, dev, offsets, cols, vals)
-    out_deg = _kmeans_out(fname, out_deg, "out_deg", (N,), torch.float32, dev)
-    out_vals = _kmeans_out(fname, out_vals, "out_vals", (nnz,), torch.float32, dev)
+    nnz = _csr(fname, N, dev, offsets, cols, vals, int32_nnz=True)
+    out_deg = _out(fname, out_deg, "out_deg", torch.float32, (N,), dev)
+    out_vals = _out(fname, out_vals, "out_vals", torch.float32, (nnz,), dev)
     check(lib.cclip_label_graph_normalize(_p(offsets), _p(cols), _p(vals), c_long(N), c_long(nnz), _p(out_deg), _p(out_vals),
                                           _stream()), "cclip_label_graph_normalize")
     return out_deg, out_vals
 
 
-def _label_F(fname: str, F, n: str = "F"):
-    _tsne_f32(fname, F, n, (None, None))
+def _label_F(fname: str, F):
+    _dev_tensors(fname, None, ((F, "F", torch.float32, 2, False),))
     N, C = F.shape
-    if N < 1:
-        raise ValueError(f"{fname}: empty operand (N = 0)")
     if not 2 <= C <= LABEL_SPREAD_MAX_C:
         raise ValueError(f"{fname}: C = {C} outside the kernel's range 2 .. {LABEL_SPREAD_MAX_C}")
-    if N >= 2 ** 31:
-        raise NotImplementedError(f"{fname}: N = {N}; the kernel's row index is int32 (N < 2^31)")
-    return N, C
+    return _rows_int32(fname, N), C
 
 
 def label_spread_step(F, labels, offsets, cols, vals, alpha: float, class_weight=None, *, out_F=None, out_delta=None,
@@ -1633,24 +1530,16 @@ def label_spread_step(F, labels, offsets, cols, vals, alpha: float, class_weight
     fname = "label_spread_step"
     N, C = _label_F(fname, F)
     dev = F.device
-    nnz = _label_csr(fname, N, dev, offsets, cols, vals)
-    for t, n, dt, shape in ((labels, "labels", torch.int32, (N,)), (class_weight, "class_weight", torch.float32, (C,))):
-        if t is None and n == "class_weight":
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError(f"{fname}: {n}: expected a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
-        if t.dtype != dt:
-            raise TypeError(f"{fname}: {n} must be {dt}, got {t.dtype}")
-        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"{fname}: {n} must be a contiguous {dt} {list(shape)} vector on {dev}, got {tuple(t.shape)} on {t.device}")
+    nnz = _csr(fname, N, dev, offsets, cols, vals, int32_nnz=True)
+    _dev_tensors(fname, dev, ((labels, "labels", torch.int32, (N,), False), (class_weight, "class_weight", torch.float32, (C,), True)))
     alpha = float(alpha)
     if not 0.0 <= alpha <= 1.0:
         raise ValueError(f"{fname}: alpha = {alpha} outside [0, 1]")
-    out_F = _kmeans_out(fname, out_F, "out_F", (N, C), torch.float32, dev)
+    out_F = _out(fname, out_F, "out_F", torch.float32, (N, C), dev)
     if out_F.data_ptr() == F.data_ptr():
         raise ValueError(f"{fname}: out_F must not be F: other rows still read F")
     if delta:
-        out_delta = _kmeans_out(fname, out_delta, "out_delta", (N,), torch.float32, dev)
+        out_delta = _out(fname, out_delta, "out_delta", torch.float32, (N,), dev)
     elif out_delta is not None:
         raise ValueError(f"{fname}: delta=False writes no out_delta")
     check(lib.cclip_label_spread_step(_p(F), _p(out_F), c_long(N), c_int(C), _p(labels), _p(class_weight), _p(offsets), _p(cols),
@@ -1667,12 +1556,12 @@ def label_spread_finish(F, *, out_dist=None, out_pred=None, out_conf=None, out_c
     N, C = _label_F(fname, F)
     dev = F.device
     if dist:
-        out_dist = _kmeans_out(fname, out_dist, "out_dist", (N, C), torch.float32, dev)
+        out_dist = _out(fname, out_dist, "out_dist", torch.float32, (N, C), dev)
     elif out_dist is not None:
         raise ValueError(f"{fname}: dist=False writes no out_dist")
-    out_pred = _kmeans_out(fname, out_pred, "out_pred", (N,), torch.int32, dev)
-    out_conf = _kmeans_out(fname, out_conf, "out_conf", (N,), torch.float32, dev)
-    out_cert = _kmeans_out(fname, out_cert, "out_cert", (N,), torch.float32, dev)
+    out_pred = _out(fname, out_pred, "out_pred", torch.int32, (N,), dev)
+    out_conf = _out(fname, out_conf, "out_conf", torch.float32, (N,), dev)
+    out_cert = _out(fname, out_cert, "out_cert", torch.float32, (N,), dev)
     check(lib.cclip_label_spread_finish(_p(F), c_long(N), c_int(C), _p(out_dist), _p(out_pred), _p(out_conf), _p(out_cert),
                                         _stream()), "cclip_label_spread_finish")
     return out_dist, out_pred, out_conf, out_cert
@@ -2479,9 +2368,7 @@ CONCEPT_MAX_V = 1 << 24
 def concept_codes_workspace(N: int, V: int, D: int) -> int:
     """bytes of workspace cclip_concept_codes needs (the fp32 w_{k-1} of every row: 4 N * 4 ceil(V / 4); 0 for a problem it
     would refuse)"""
-    fn = lib.cclip_concept_codes_workspace
-    fn.restype = c_long
-    return int(fn(c_long(N), c_long(V), c_int(D)))
+    return _query("cclip_concept_codes_workspace", c_long, c_long(N), c_long(V), c_int(D))
 
 
 def concept_codes(x, c, l1: float, eta: float, iters: int, *, out_w=None, workspace=None):
@@ -2493,31 +2380,26 @@ def concept_codes(x, c, l1: float, eta: float, iters: int, *, out_w=None, worksp
     stride that is a multiple of 4 and 16-byte alignment (nothing is written between its rows); workspace: a contiguous fp32
     device tensor of at least concept_codes_workspace(N, V, D) bytes.  1 <= V <= 2^24, D % 32 == 0, 32 <= D <= 1024, N < 2^31.
     A row's outputs depend on neither N nor its position; two calls are bitwise equal.  No host read."""
-    N, V, D, ldx, ldc = _kmeans_operands("concept_codes", x, c, "c")
+    fname = "concept_codes"
+    N, V, D, ldx, ldc = _kmeans_operands(fname, x, c, "c")
     if V > CONCEPT_MAX_V:
-        raise NotImplementedError(f"concept_codes: V = {V}; the kernel takes up to {CONCEPT_MAX_V} concepts")
-    l1, eta = float(l1), float(eta)
-    if not (0.0 <= l1 < float("inf")) or not (0.0 <= eta < float("inf")):
-        raise ValueError(f"concept_codes: l1 = {l1} and eta = {eta} must be finite and >= 0")
+        raise NotImplementedError(f"{fname}: V = {V}; the kernel takes up to {CONCEPT_MAX_V} concepts")
+    l1, eta = _finite(fname, "l1", l1, nonneg=True), _finite(fname, "eta", eta, nonneg=True)
     if isinstance(iters, bool) or int(iters) != iters or iters < 0:
-        raise ValueError(f"concept_codes: iters = {iters!r} must be an integer >= 0")
+        raise ValueError(f"{fname}: iters = {iters!r} must be an integer >= 0")
     dev = x.device
     if out_w is None:
         out_w = torch.empty(N, (V + 3) // 4 * 4, device=dev, dtype=torch.float32)[:, :V]
-    elif (not isinstance(out_w, torch.Tensor) or out_w.dtype != torch.float32 or out_w.device != dev
-          or tuple(out_w.shape) != (N, V) or out_w.stride(1) != 1):
-        raise ValueError(f"concept_codes: out_w must be an fp32 [{N}, {V}] view on {dev} with inner stride 1, got "
-                         f"{getattr(out_w, 'dtype', type(out_w))} {tuple(getattr(out_w, 'shape', ()))}")
-    ldw = out_w.stride(0) if N > 1 else max(out_w.stride(0), (V + 3) // 4 * 4)
+    else:
+        _dev_tensor(fname, out_w, "out_w", torch.float32, (N, V), dev, contiguous=False, host_error=ValueError, dtype_error=ValueError)
+        if out_w.stride(1) != 1:
+            raise ValueError(f"{fname}: out_w must have inner stride 1, got strides {out_w.stride()}")
+    # a one-row out_w: its stride is raised to the 4 ceil(V / 4) the kernel needs but, unlike _ld16's, not rounded down to a multiple
+    ldw = _ld(out_w, multiple=1, at_least=(V + 3) // 4 * 4)
     if ldw % 4 or ldw < V or out_w.data_ptr() % 16:
-        raise ValueError(f"concept_codes: out_w must be 16-byte aligned with a row stride >= V that is a multiple of 4 elements "
+        raise ValueError(f"{fname}: out_w must be 16-byte aligned with a row stride >= V that is a multiple of 4 elements "
                          f"(stride {out_w.stride(0)}, address % 16 = {out_w.data_ptr() % 16})")
-    nbytes = concept_codes_workspace(N, V, D)
-    if workspace is None:
-        workspace = torch.empty(nbytes // 4, device=dev, dtype=torch.float32)
-    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or workspace.device != dev
-          or not workspace.is_contiguous() or workspace.numel() * 4 < nbytes or workspace.data_ptr() % 16):
-        raise ValueError(f"concept_codes: workspace must be a contiguous 16-byte aligned fp32 tensor of at least {nbytes} bytes on {dev}")
+    workspace = _workspace(fname, workspace, concept_codes_workspace(N, V, D), torch.float32, dev, align16=True)
     resid2, l1norm, delta, kkt = (torch.empty(N, device=dev, dtype=torch.float32) for _ in range(4))
     nnz = torch.empty(N, device=dev, dtype=torch.int32)
     fn = _fn("cclip_concept_codes", x, c)

@@ -185,3 +185,44 @@ def test_script_argument_parsing_and_majority_labels(capsys):
     capsys.readouterr()
     got = cluster_images.majority_labels([0, 0, 0, 0, 1, 1, 2, 2, 2], ["a", "b", "b", "", "", None, "z", "y", ""], 4)
     assert got == [("b", 2 / 3, 1), (None, 0.0, 2), ("y", 0.5, 1), (None, 0.0, 0)]
+
+
+def test_analysis_wrappers_refuse_host_tensors_before_the_library(monkeypatch):
+    """every wrapper of the embedding-analysis family (k-means and what was built beside it): well-formed host tensors are a
+    TypeError raised by the argument checks, before the library is loaded - there is no host path"""
+    import cclip_hip._lib as L
+    from cclip_hip import ops
+
+    def boom():
+        raise AssertionError("the library must not be touched")
+    monkeypatch.setattr(L, "load_library", boom)
+    x, c = torch.zeros(3, 32).bfloat16(), torch.zeros(2, 32).bfloat16()
+    f, i = (lambda *s: torch.zeros(*s)), (lambda *s: torch.zeros(*s, dtype=torch.int32))
+    _, class_off, class_len = ops.cache_layout([0, 1, 0], 2)
+    off, cols, vals = torch.tensor([0, 2, 3, 4]), i(4), f(4)
+    calls = {
+        "similarity_topk": lambda: ops.similarity_topk(x, c, 2),
+        "similarity_range": lambda: ops.similarity_range(x, c, 0.5),
+        "lm_head_score": lambda: ops.lm_head_score(x, c, i(3)),
+        "cache_affinity": lambda: ops.cache_affinity(x, torch.zeros(32, 32).bfloat16(), class_off, class_len, 5.5),
+        "cache_affinity_backward": lambda: ops.cache_affinity_backward(x, torch.zeros(32, 32).bfloat16(), class_off, class_len, 5.5, f(3, 2)),
+        "kmeans_assign": lambda: ops.kmeans_assign(x, c),
+        "kmeans_update": lambda: ops.kmeans_update(x, i(3), 2, c),
+        "coreset_step": lambda: ops.coreset_step(x, f(3), i(3), torch.zeros(1, dtype=torch.int64), centre=0),
+        "coreset_greedy": lambda: ops.coreset_greedy(x, f(3), i(3), 2, first=0),
+        "mreach_nearest": lambda: ops.mreach_nearest(x, f(3), i(3)),
+        "mst_boruvka": lambda: ops.mst_boruvka(x, f(3)),
+        "probe_forward": lambda: ops.probe_forward(x, f(2, 32), f(2), i(3)),
+        "probe_backward": lambda: ops.probe_backward(x, f(2, 32), f(2), i(3), f(3), 0.5, 0.0),
+        "tsne_affinities": lambda: ops.tsne_affinities(f(3, 3), 2.0),
+        "tsne_repulsion": lambda: ops.tsne_repulsion(f(3, 2)),
+        "tsne_step": lambda: ops.tsne_step(f(3, 2), f(3, 2), f(3, 2), off, cols, vals, f(3, 2), f(1)),
+        "label_graph_normalize": lambda: ops.label_graph_normalize(off, cols, vals),
+        "label_spread_step": lambda: ops.label_spread_step(f(3, 2), i(3), off, cols, vals, 0.9),
+        "label_spread_finish": lambda: ops.label_spread_finish(f(3, 2)),
+        "concept_codes": lambda: ops.concept_codes(x, c, 0.1, 0.5, 2),
+    }
+    for name, call in calls.items():
+        with pytest.raises(TypeError, match="cuda") as info:
+            call()
+        assert name in str(info.value), f"{name}: {info.value}"
