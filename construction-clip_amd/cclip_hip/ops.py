@@ -2273,24 +2273,32 @@ def xent_rows(logits, labels_i32, *, loss_row=None, pred=None, dlogits=None, gra
                               c_long(0 if dlogits is None else dlogits.stride(0)), _p(rowdot), _stream()), "cclip_xent_rows")
 
 
-_PER_ROW = (("loss_row", torch.float32), ("pred", torch.int32), ("hit", torch.float32), ("rowdot", torch.float32),
-            ("rowsum", torch.float32))
+_PER_ROW = dict(loss_row=torch.float32, pred=torch.int32, hit=torch.float32, agree=torch.float32, rowdot=torch.float32,
+                rowsum=torch.float32)
 
 
-def _class_rows(logits, row_class_i32, col_class_i32, dlogits, *per_row):
-    """The arguments the class-vector row losses share (xent_rows_classes, sigmoid_rows): fp32 logits [R, C] with unit column
-    stride, the int32 class vectors [R] and [C], the optional fp32 gradient, which may be `logits` itself, and the optional
-    per-row outputs [R] in the order of _PER_ROW.  Returns (R, C)."""
-    _req(logits, torch.float32, "logits"); _req(row_class_i32, torch.int32, "row_class"); _req(col_class_i32, torch.int32, "col_class")
+def _loss_rows(logits, dlogits, *, classes=None, teacher=None, **per_row):
+    """The arguments the fp32 row losses share (xent_rows_classes, sigmoid_rows, kl_rows): fp32 logits [R, C] with unit column
+    stride; `classes`, the int32 class vectors ([R], [C]) of the class-vector losses; `teacher`, the second fp32 [R, C]
+    operand of kl_rows on the same device (unit column stride, a row stride of its own); the optional per-row outputs [R] by
+    their names in _PER_ROW; and the optional fp32 gradient, which may be `logits` itself.  Returns (R, C)."""
+    _req(logits, torch.float32, "logits")
+    for t, name in zip(classes or (), ("row_class", "col_class")):
+        _req(t, torch.int32, name)
+    if teacher is not None:
+        _req(teacher, torch.float32, "teacher")
     if logits.dim() != 2 or logits.stride(1) != 1:
         raise ValueError(f"logits: expected [R, C] with unit column stride, got {tuple(logits.shape)} strides {logits.stride()}")
     R, C = logits.shape
-    for t, n, name in ((row_class_i32, R, "row_class"), (col_class_i32, C, "col_class")):
+    for t, n, name in zip(classes or (), (R, C), ("row_class", "col_class")):
         if t.shape != (n,) or not t.is_contiguous():
             raise ValueError(f"{name}: expected contiguous [{n}], got {tuple(t.shape)}")
-    for t, (name, dt) in zip(per_row, _PER_ROW):
+    if teacher is not None and (teacher.shape != (R, C) or teacher.stride(1) != 1 or teacher.device != logits.device):
+        raise ValueError(f"teacher: expected [{R}, {C}] with unit column stride on {logits.device}, got {tuple(teacher.shape)} "
+                         f"strides {teacher.stride()} on {teacher.device}")
+    for name, t in per_row.items():
         if t is not None:
-            _req(t, dt, name)
+            _req(t, _PER_ROW[name], name)
             if t.shape != (R,) or not t.is_contiguous():
                 raise ValueError(f"{name}: expected contiguous [{R}], got {tuple(t.shape)}")
     if dlogits is not None:
@@ -2304,7 +2312,7 @@ def xent_rows_classes(logits, row_class_i32, col_class_i32, *, loss_row=None, pr
                       grad_scale: float = 1.0, rowdot=None) -> None:
     """Class-aware row cross-entropy (include/cclip_hip.h, cclip_xent_rows_classes): the positives of row r are the columns
     whose class equals row_class[r]; a negative class id is 'unlabelled'.  fp32 only; dlogits may be `logits` itself."""
-    R, C = _class_rows(logits, row_class_i32, col_class_i32, dlogits, loss_row, pred, hit, rowdot)
+    R, C = _loss_rows(logits, dlogits, classes=(row_class_i32, col_class_i32), loss_row=loss_row, pred=pred, hit=hit, rowdot=rowdot)
     check(lib.cclip_xent_rows_classes(_p(logits), c_long(logits.stride(0)), c_int(R), c_int(C), _p(row_class_i32),
                                       _p(col_class_i32), c_float(grad_scale), _p(loss_row), _p(pred), _p(hit), _p(dlogits),
                                       c_long(0 if dlogits is None else dlogits.stride(0)), _p(rowdot), _stream()),
@@ -2319,13 +2327,28 @@ def sigmoid_rows(logits, row_class_i32, col_class_i32, bias, *, loss_row=None, p
     _req(bias, torch.float32, "bias")
     if bias.numel() != 1:
         raise ValueError(f"bias: expected one element, got {tuple(bias.shape)}")
-    R, C = _class_rows(logits, row_class_i32, col_class_i32, dlogits, loss_row, pred, hit, rowdot, rowsum)
+    R, C = _loss_rows(logits, dlogits, classes=(row_class_i32, col_class_i32), loss_row=loss_row, pred=pred, hit=hit, rowdot=rowdot,
+                      rowsum=rowsum)
     if dlogits is None and (rowdot is not None or rowsum is not None):
         raise ValueError("rowdot / rowsum are written only together with dlogits")
     check(lib.cclip_sigmoid_rows(_p(logits), c_long(logits.stride(0)), c_int(R), c_int(C), _p(row_class_i32), _p(col_class_i32),
                                  _p(bias), c_float(grad_scale), _p(loss_row), _p(pred), _p(hit), _p(dlogits),
                                  c_long(0 if dlogits is None else dlogits.stride(0)), _p(rowdot), _p(rowsum), _stream()),
           "cclip_sigmoid_rows")
+
+
+def kl_rows(logits, teacher, *, loss_row=None, pred=None, agree=None, dlogits=None, grad_scale: float = 1.0,
+            rowdot=None) -> None:
+    """Distillation row loss (include/cclip_hip.h, cclip_kl_rows): KL(softmax(teacher row) || softmax(logits row)) per row, its
+    gradient w.r.t. `logits`, and whether the two rows' arg-maxes agree.  `teacher` is fp32 [R, C] on the device of `logits`
+    with a row stride of its own, and is only read.  fp32 only; dlogits may be `logits` itself; rowdot comes only with
+    dlogits."""
+    R, C = _loss_rows(logits, dlogits, teacher=teacher, loss_row=loss_row, pred=pred, agree=agree, rowdot=rowdot)
+    if dlogits is None and rowdot is not None:
+        raise ValueError("rowdot is written only together with dlogits")
+    check(lib.cclip_kl_rows(_p(logits), c_long(logits.stride(0)), _p(teacher), c_long(teacher.stride(0)), c_int(R), c_int(C),
+                            c_float(grad_scale), _p(loss_row), _p(pred), _p(agree), _p(dlogits),
+                            c_long(0 if dlogits is None else dlogits.stride(0)), _p(rowdot), _stream()), "cclip_kl_rows")
 
 
 def reduce_dot(a, b, out, *, alpha: float = 1.0, mul_dev=None, accumulate: bool = False) -> None:

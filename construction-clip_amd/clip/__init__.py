@@ -5,6 +5,7 @@ from . import simple_tokenizer  # noqa: F401  (attention.py:114 uses clip.simple
 from .model import CLIP, build_model  # noqa: F401
 from .loss import contrastive_loss, ContrastiveLoss, class_ids, unique_texts  # noqa: F401
 from .loss import sigmoid_loss, SigmoidLoss  # noqa: F401  (SigLIP's pairwise sigmoid objective on the same head)
+from .loss import distill_loss, DistillLoss  # noqa: F401  (KL to a frozen teacher's similarity rows, same head)
 from .preprocess_device import DevicePreprocess  # noqa: F401
 from .explain import interpret, image_relevance_map, text_token_scores  # noqa: F401  (attention.py:14, 88-92, 115-117)
 from .explain import interpret_rows, text_row_scores  # noqa: F401  (the same rows for towers of more than 128 tokens)

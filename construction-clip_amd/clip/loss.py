@@ -19,7 +19,10 @@ token rows equally across ranks for the data-parallel (square) form.
 `sigmoid_loss` / `SigmoidLoss` is the second objective: SigLIP's pairwise sigmoid loss over the same logits plus a learnable
 bias, pairwise or class-aware by the same `labels=` conventions, on ops.sigmoid_rows (one logits GEMM, one row-kernel launch).
 
-Two autograd Functions, `_Contrastive` (both softmax forms) and `_Sigmoid`, differ in their row kernels and statistics.  The
+`distill_loss` / `DistillLoss` is the third: the KL divergence from a frozen teacher's similarity rows to the student's, both
+directions, on ops.kl_rows - the soft counterpart that keeps a fine-tune on few pairs near what the pretrained model knew.
+
+Three autograd Functions, `_Contrastive` (both softmax forms), `_Sigmoid` and `_Distill`, differ in their row kernels and statistics.  The
 steps around those are written once: `_normalise_gather` (two l2norm_fwd, the all-gather), `_feature_grads` (cross GEMMs,
 reduce-scatter, local GEMMs), `_backward_tail` (two l2norm_bwd, the logit_scale gradient) and `_classes` (what `labels` and
 `text_labels` mean, with the refusals).  tools/loss_dump.py records the launch sequence and the results of every form.
@@ -379,6 +382,112 @@ class SigmoidLoss(torch.nn.Module):
     def forward(self, image_features, text_features, logit_scale, labels=None, text_labels=None):
         return sigmoid_loss(image_features, text_features, logit_scale, self.logit_bias, self.group, labels=labels,
                             text_labels=text_labels)
+
+
+class _Distill(torch.autograd.Function):
+    """The distillation loss: each row of the student's L = s I T^T and of its transpose is pulled towards the same row of a
+    frozen teacher's G = s_t I_t T_t^T by KL(softmax G_row || softmax L_row) (DESIGN.md 'Distillation loss').  Both directions
+    normalise over their own rows, so this is _Contrastive's two-sided scheme with ops.kl_rows as the row kernel and the
+    teacher's two row blocks, formed by the same launches, in place of the class vectors.  Single process, M free, never
+    packed.  The teacher tensors arrive detached and get no gradient."""
+
+    @staticmethod
+    def forward(ctx, fi, ft, logit_scale, ti, tt, teacher_scale):
+        r = _Ranks(None, False, 0, 1)
+        dev = fi.device
+        fi, ft, ti, tt = (x.contiguous().float() for x in (fi, ft, ti, tt))
+        ls = _scalar(logit_scale)
+        N, M = fi.shape[0], ft.shape[0]
+        need_grad = any(ctx.needs_input_grad[:3])
+        # the teacher's scale arrives as exp(logit_scale): a float is a host constant of its GEMMs, a tensor goes back to the
+        # log form their device-scalar argument takes (one element, on the device; nothing is read on the host)
+        if isinstance(teacher_scale, torch.Tensor):
+            t_scale = dict(alpha_log_dev=_scalar(teacher_scale).to(dev).log())
+        else:
+            t_scale = dict(alpha=float(teacher_scale))
+
+        f = _normalise_gather(fi, ft, M, r, packed=False, one_sided=False)
+        g = _normalise_gather(ti, tt, M, r, packed=False, one_sided=False)
+        L_i = torch.empty(N, M, device=dev, dtype=torch.float32)
+        L_t = torch.empty(M, N, device=dev, dtype=torch.float32)
+        G_i, G_t = torch.empty_like(L_i), torch.empty_like(L_t)
+        ops.gemm_f32(f.i_n, f.t_all, L_i, alpha_log_dev=ls)
+        ops.gemm_f32(f.t_n, f.i_all, L_t, alpha_log_dev=ls)
+        ops.gemm_f32(g.i_n, g.t_all, G_i, **t_scale)
+        ops.gemm_f32(g.t_n, g.i_all, G_t, **t_scale)
+        loss_rows = torch.empty(N + M, device=dev, dtype=torch.float32)
+        rowdot = torch.empty(N + M, device=dev, dtype=torch.float32) if need_grad else None
+        agree = torch.empty(N, device=dev, dtype=torch.float32)
+        gs_i, gs_t = 1.0 / (2.0 * N), 1.0 / (2.0 * M)                            # fixed denominators: host constants
+        out = torch.empty(2, device=dev, dtype=torch.float32)                    # [loss, #image rows agreeing with the teacher]
+
+        def side(L, rows, gs):
+            # the gradient of the mean loss overwrites the student's logits in place (nothing else needs them)
+            return dict(loss_row=loss_rows[rows], dlogits=L if need_grad else None, grad_scale=gs,
+                        rowdot=rowdot[rows] if need_grad else None)
+
+        image_rows, text_rows = slice(0, N), slice(N, None)
+        ops.kl_rows(L_i, G_i, agree=agree, **side(L_i, image_rows, gs_i))
+        ops.kl_rows(L_t, G_t, **side(L_t, text_rows, gs_t))
+        ops.reduce_dot(loss_rows[image_rows], None, out[0:1], alpha=gs_i)
+        ops.reduce_dot(loss_rows[text_rows], None, out[0:1], alpha=gs_t, accumulate=True)
+        ops.reduce_dot(agree, None, out[1:2])
+        if need_grad:
+            ctx.saved = (*_feature_grads(L_i, L_t, f, ls, r), f.i_n, f.t_n, f.inv_i, f.inv_t, rowdot)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, dloss, _dout):
+        _, grads = _backward_tail(ctx.saved, dloss)
+        ctx.saved = None
+        return (*grads, None, None, None)
+
+
+def distill_loss(image_features: torch.Tensor, text_features: torch.Tensor, logit_scale: torch.Tensor,
+                 teacher_image_features: torch.Tensor, teacher_text_features: torch.Tensor, teacher_scale,
+                 group: Optional["dist.ProcessGroup"] = None):
+    """Contrastive relational distillation (CLIP-KD, Yang et al. 2024; the LwF regulariser when the teacher is the checkpoint
+    the run started from): with the student's L = exp(logit_scale) cos(image i, text j) [N, M] and a frozen teacher's
+    G = teacher_scale cos(teacher image i, teacher text j) over the same N images and M texts,
+
+        loss = (1/2N) sum_i KL(softmax G_i || softmax L_i) + (1/2M) sum_j KL(softmax G^T_j || softmax L^T_j)
+
+    Returns (loss, stats), stats = tensor([loss, number of image rows whose arg-max text is the teacher's]), non-differentiable.
+
+    Only logits are compared, so the teacher's embedding width is its own.  M is free: the U distinct texts of a batch
+    (unique_texts), encoded once by both models, are as good as N.  `teacher_scale` is the teacher's own exp(logit_scale), a
+    float or a one-element tensor (used on the device, never read on the host; it passes through a log and an exp, one fp32
+    rounding of log(teacher_scale)).  Gradients flow to the student's features and to logit_scale; the teacher's tensors are
+    detached on entry.  Add it to a hard loss as `hard + weight * distill`.  Single process only."""
+    if _collectives(group):
+        raise NotImplementedError("distillation loss is single-process only; under data parallelism train with the hard loss "
+                                  "alone (contrastive_loss or sigmoid_loss take the group)")
+    for name, s, t in (("image", image_features, teacher_image_features), ("text", text_features, teacher_text_features)):
+        if s.dim() != 2 or t.dim() != 2 or s.shape[0] != t.shape[0]:
+            raise ValueError(f"teacher_{name}_features: expected [{s.shape[0]}, E_teacher] (one row per student {name} row), "
+                             f"got {tuple(t.shape)}")
+    if teacher_image_features.shape[1] != teacher_text_features.shape[1] or image_features.shape[1] != text_features.shape[1]:
+        raise ValueError("image and text features of one model need equal embedding widths")
+    if isinstance(teacher_scale, torch.Tensor):
+        if teacher_scale.numel() != 1:
+            raise ValueError(f"teacher_scale: expected a float or one element, got {tuple(teacher_scale.shape)}")
+        teacher_scale = teacher_scale.detach()
+    return _Distill.apply(image_features, text_features, logit_scale, teacher_image_features.detach(),
+                          teacher_text_features.detach(), teacher_scale)
+
+
+class DistillLoss(torch.nn.Module):
+    """distill_loss with the teacher's scale (its exp(logit_scale)) held as a buffer: nothing here is learnable."""
+
+    def __init__(self, teacher_scale, group=None):
+        super().__init__()
+        self.group = group
+        self.register_buffer("teacher_scale", torch.as_tensor(teacher_scale, dtype=torch.float32).detach().reshape(()).clone())
+
+    def forward(self, image_features, text_features, logit_scale, teacher_image_features, teacher_text_features):
+        return distill_loss(image_features, text_features, logit_scale, teacher_image_features, teacher_text_features,
+                            self.teacher_scale, self.group)
 
 
 class ContrastiveLoss(torch.nn.Module):

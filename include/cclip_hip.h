@@ -791,6 +791,20 @@ int cclip_xent_rows_classes(const float* logits, int64_t ld, int32_t R, int32_t 
 int cclip_sigmoid_rows(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* row_class,
                        const int32_t* col_class, const float* bias_dev, float grad_scale, float* loss_row, int32_t* pred,
                        float* hit, float* dlogits, int64_t ldd, float* rowdot, float* rowsum, hipStream_t stream);
+/* cclip_kl_rows: the distillation row loss (fp32 only).  l = row r of logits [R, C] (leading dimension ld), g = row r of
+ *   teacher [R, C] (leading dimension ldt, independent of ld; never written), lse = logsumexp:
+ *   p_t[c] = exp(g[c] - lse(g)), p_s[c] = exp(l[c] - lse(l)),
+ *   loss_row = sum_c p_t[c] * ((g[c] - lse(g)) - (l[c] - lse(l)))   (KL(teacher || student); a cell with p_t == 0 adds 0, so
+ *   a teacher cell of -inf contributes exactly nothing), dlogits = (p_s - p_t) * grad_scale (fp32, may alias logits),
+ *   rowdot = sum_c dlogits[c] * l[c] (written only together with dlogits), pred = argmax(l) (first max), agree = 1.0f when
+ *   argmax(l) == argmax(g), else 0.0f (a row without a maximum agrees with nothing).  Every output pointer is optional.  A
+ *   teacher row equal to the logits row gives loss_row and dlogits exactly 0.  A NaN in either row makes that row's loss_row
+ *   NaN and touches no other row.  One wave per row, two sweeps (row statistics, then loss and gradient), no atomics: two
+ *   launches are bitwise equal.
+ *   CCLIP_ERR_ARG (nothing launched): null logits or teacher; R <= 0 or C <= 0; ld < C; ldt < C; dlogits with ldd < C. */
+int cclip_kl_rows(const float* logits, int64_t ld, const float* teacher, int64_t ldt, int32_t R, int32_t C, float grad_scale,
+                  float* loss_row, int32_t* pred, float* agree, float* dlogits, int64_t ldd, float* rowdot,
+                  hipStream_t stream);
 /* out (+)= alpha * (mul_dev ? *mul_dev : 1) * sum_i a[i] * (b ? b[i] : 1)   (single block, deterministic) */
 int cclip_reduce_dot(const float* a, const float* b, int64_t n, float alpha, const float* mul_dev, float* out,
                      int32_t accumulate, hipStream_t stream);

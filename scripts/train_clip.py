@@ -18,7 +18,16 @@ labels= / text_labels=), and the logged accuracy counts an arg-max on the image'
 (image, text) cell is scored on its own against a learnable `logit_bias` (`--logit-bias-init`, SigLIP's -10), which suits the
 small batches of this loop.  It composes with `--class-aware` (distinct texts once, every text of the class a positive).  The
 bias is not a CLIP weight: it has an AdamW of its own at `--lr` under the same warm-up, it is logged with the loss, and it is
-saved next to each checkpoint as `<checkpoint>_logit_bias.pt` - the checkpoint itself stays a pure OpenAI-layout state_dict."""
+saved next to each checkpoint as `<checkpoint>_logit_bias.pt` - the checkpoint itself stays a pure OpenAI-layout state_dict.
+
+`--distill-from {pretrained|PATH}` (implies the fused path) adds `--distill-weight` times clip.distill_loss to whichever hard
+loss the run chose: a second, frozen model from clip.load - `pretrained`: the named model (`--distill-arch`, default `--model`)
+as clip.load gives it, i.e. what the run started from; PATH: a state_dict checkpoint - encodes exactly the image and text
+tensors the student encodes (under `--class-aware` the distinct texts, once), in eval mode under no_grad, and the student's
+similarity rows are pulled towards the teacher's (KL, both directions).  A few thousand pairs otherwise make the towers forget
+what zero-shot heads and free-text search rely on.  The teacher is never handed to the optimiser; its input resolution and
+token layout must be the student's.  The step log gains `distill` (the KL term) and `agree` (the share of images whose
+arg-max text is the teacher's)."""
 from __future__ import annotations
 
 import argparse
@@ -54,9 +63,44 @@ def build_args():
     ap.add_argument("--loss", choices=("softmax", "sigmoid"), default="softmax",
                     help="sigmoid: SigLIP's pairwise sigmoid loss with a learnable logit bias (implies the fused path)")
     ap.add_argument("--logit-bias-init", type=float, default=-10.0, help="initial logit bias of --loss sigmoid")
+    ap.add_argument("--distill-from", default=None, metavar="{pretrained|PATH}",
+                    help="distil from a frozen teacher: 'pretrained' (clip.load of --distill-arch) or a state_dict checkpoint "
+                         "(implies the fused path)")
+    ap.add_argument("--distill-arch", default=None, metavar="NAME", help="model name of '--distill-from pretrained' (default: --model)")
+    ap.add_argument("--distill-weight", type=float, default=1.0, help="total = hard + this * distill")
     ap.add_argument("--synthetic", action="store_true", help="generated images + labels, seeded weights, byte tokenizer")
     ap.add_argument("--seed", type=int, default=567)
     return ap
+
+
+def check_teacher(model, teacher) -> None:
+    """The teacher encodes the very tensors the student encodes: refuse one that wants other pixels or other tokens."""
+    a, b = model.visual.input_resolution, teacher.visual.input_resolution
+    if a != b:
+        raise ValueError(f"--distill-from: the teacher's input resolution is {b}, the student's {a}; both encode the same "
+                         "preprocessed images")
+    for what in ("context_length", "vocab_size"):
+        a, b = getattr(model, what), getattr(teacher, what)
+        if a != b:
+            raise ValueError(f"--distill-from: the teacher's {what} is {b}, the student's {a}; both encode the same token rows")
+
+
+def load_teacher(args, model, device):
+    """(frozen teacher in eval mode, clip.DistillLoss holding its scale) of --distill-from, or (None, None)"""
+    if args.distill_from is None:
+        return None, None
+    import clip
+    if args.distill_from == "pretrained":
+        name = args.distill_arch or args.model
+    elif os.path.isfile(args.distill_from):
+        name = args.distill_from
+    else:
+        raise ValueError(f"--distill-from: {args.distill_from!r} is neither 'pretrained' nor a checkpoint file")
+    teacher, _ = clip.load(name, device=device, jit=False)
+    check_teacher(model, teacher)
+    teacher.eval()
+    teacher.requires_grad_(False)
+    return teacher, clip.DistillLoss(teacher.logit_scale.detach().exp()).to(device)
 
 
 def evaluate(model, loader, device):
@@ -88,6 +132,7 @@ def main(argv=None):
     model, preprocess = clip.load(args.model, device=device, jit=False)
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location="cpu", weights_only=True))
+    teacher, distill = load_teacher(args, model, device)
     tokenize = C.get_tokenize(model)
     mk = lambda split: ClipPairDataset(preprocess, args.json, args.image_path, args.train_ratio, args.key, split,   # noqa: E731
                                        args.combination_num, tokenize=tokenize)
@@ -112,9 +157,11 @@ def main(argv=None):
             if bias_opt is not None:
                 bias_opt.zero_grad()
             label = torch.arange(image.shape[0], device=device)
+            encoded = text                                                                  # the token rows the text tower sees
             if args.class_aware:
                 text_u, inverse = clip.unique_texts(text)                                   # [U, 77], text == text_u[inverse]
                 fi, ft = model.encode_image_text(image, text_u)                             # the text tower sees U rows, not G*K
+                encoded = text_u
                 text_ids = torch.arange(text_u.shape[0], device=device)
                 if sig is not None:
                     loss, stats = sig(fi, ft, model.logit_scale, labels=inverse, text_labels=text_ids)
@@ -125,7 +172,7 @@ def main(argv=None):
                 fi, ft = model.encode_image_text(image, text)
                 loss, stats = sig(fi, ft, model.logit_scale)
                 acc = float(stats[1]) / image.shape[0]
-            elif args.fused_loss:
+            elif args.fused_loss or teacher is not None:
                 fi, ft = model.encode_image_text(image, text)
                 loss, stats = clip.contrastive_loss(fi, ft, model.logit_scale, None)
                 acc = float(stats[1]) / image.shape[0] if len(stats) > 1 else float("nan")
@@ -133,14 +180,22 @@ def main(argv=None):
                 logits_i, logits_t = model(image, text)                                     # train.py:161
                 loss = (ce(logits_i, label) + ce(logits_t, label)) / 2                      # train.py:164-166
                 acc = float((logits_i.argmax(1) == label).float().mean())                   # train.py:173
+            extra = {}
+            if teacher is not None:
+                with torch.no_grad():
+                    tfi, tft = teacher.encode_image_text(image, encoded)                    # the tensors the student encoded
+                hard = loss
+                soft, dstats = distill(fi, ft, model.logit_scale, tfi, tft)
+                loss = hard + args.distill_weight * soft
+                extra = dict(hard=round(float(hard.detach()), 6), distill=round(float(dstats[0]), 6),
+                             agree=round(float(dstats[1]) / image.shape[0], 4))
             loss.backward()
             opt.step()
             sched.step()
-            extra = {}
             if sig is not None:
                 bias_opt.step()
                 bias_sched.step()
-                extra = dict(logit_bias=round(float(sig.logit_bias.detach()), 6))
+                extra.update(logit_bias=round(float(sig.logit_bias.detach()), 6))
             step += 1
             C.log_line(epoch=epoch, step=step, loss=round(float(loss.detach()), 6), accuracy=round(acc, 4), lr=sched.get_last_lr()[0],
                        **extra)
