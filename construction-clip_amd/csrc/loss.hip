@@ -41,9 +41,9 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
   }
 }
 
+// `dlogits` may alias `logits` when DT is float (the contract: row_kernels.h, sweep_row4_store; here with one column per trip):
+// the label's logit is taken before any store.
 template <typename DT>
-// `dlogits` may alias `logits` (clip/loss.py overwrites the logits with their gradient in place), so neither carries
-// __restrict__: every element is read by the lane that later writes it, and the label's logit is taken before any store.
 __global__ __launch_bounds__(256) void xent_rows_kernel(const float* logits, long ld, int R, int C,
                                                         const int* __restrict__ labels, int ignore_index,
                                                         float grad_scale, float* __restrict__ loss_row,
@@ -55,18 +55,14 @@ __global__ __launch_bounds__(256) void xent_rows_kernel(const float* logits, lon
     const int label = labels[r];
     float m = -__builtin_inff(), s = 0.f;
     int arg = 0x7fffffff;
-    for (int c = lane; c < C; c += 64) {
-      const float v = row[c];
-      if (v > m) { s = s * __expf(m - v) + 1.f; m = v; arg = c; }
-      else s += __expf(v - m);
-    }
+    for (int c = lane; c < C; c += 64) online_softmax_step<false>(row[c], c, m, s, arg);
     wave_softmax_argmax(m, s, arg);
     const float lse = m + __logf(s);
     const bool ignored = label == ignore_index || label < 0 || label >= C;
     const float at_label = ignored ? 0.f : row[label];
     if (lane == 0) {
       if (loss_row) loss_row[r] = ignored ? 0.f : lse - at_label;
-      if (pred) pred[r] = arg;
+      store_pred_hit(r, arg, C, pred, nullptr, [] { return false; });       // this kernel has no hit output
     }
     if (dlogits) {
       DT* drow = dlogits + (long)r * ldd;
@@ -108,8 +104,7 @@ using namespace CCLIP_NS;
 extern "C" int cclip_l2norm_fwd(const float* x, int64_t ldx, int32_t rows, int32_t D, float* y, int64_t ldy,
                                 float* inv_norm, hipStream_t stream) {
   if (!x || !y || rows <= 0 || D <= 0) return CCLIP_ERR_ARG;
-  hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(grid_rows4(rows)), dim3(256), 0, stream, x, (long)ldx, rows, D, y, (long)ldy, inv_norm);
-  return cclip_launch_status();
+  return launch_rows4(l2norm_fwd_kernel, rows, stream, x, ldx, rows, D, y, ldy, inv_norm);
 }
 #endif
 #ifndef CCLIP_F16
@@ -117,8 +112,7 @@ extern "C" int cclip_l2norm_bwd(const float* dy, int64_t lddy, const float* y, i
                                 int32_t rows, int32_t D, float* dx, int64_t lddx, const float* mul_dev,
                                 hipStream_t stream) {
   if (!dy || !y || !inv_norm || !dx || rows <= 0 || D <= 0) return CCLIP_ERR_ARG;
-  hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(grid_rows4(rows)), dim3(256), 0, stream, dy, (long)lddy, y, (long)ldy, inv_norm, rows, D, dx, (long)lddx, mul_dev);
-  return cclip_launch_status();
+  return launch_rows4(l2norm_bwd_kernel, rows, stream, dy, lddy, y, ldy, inv_norm, rows, D, dx, lddx, mul_dev);
 }
 #endif
 extern "C" int CCLIP_FN(cclip_xent_rows)(const float* logits, int64_t ld, int32_t R, int32_t C, const int32_t* labels,
@@ -127,12 +121,11 @@ extern "C" int CCLIP_FN(cclip_xent_rows)(const float* logits, int64_t ld, int32_
                                hipStream_t stream) {
   if (!logits || !labels || R <= 0 || C <= 0) return CCLIP_ERR_ARG;
   if (dlogits_is_bf16 && (const void*)dlogits == (const void*)logits) return CCLIP_ERR_ARG;
-  dim3 grid(grid_rows4(R)), block(256);
   if (dlogits_is_bf16)
-    hipLaunchKernelGGL((xent_rows_kernel<bf16>), grid, block, 0, stream, logits, (long)ld, R, C, labels, ignore_index, grad_scale, loss_row, pred, (bf16*)dlogits, (long)ldd, rowdot);
-  else
-    hipLaunchKernelGGL((xent_rows_kernel<float>), grid, block, 0, stream, logits, (long)ld, R, C, labels, ignore_index, grad_scale, loss_row, pred, (float*)dlogits, (long)ldd, rowdot);
-  return cclip_launch_status();
+    return launch_rows4(xent_rows_kernel<bf16>, R, stream, logits, ld, R, C, labels, ignore_index, grad_scale, loss_row, pred,
+                        (bf16*)dlogits, ldd, rowdot);
+  return launch_rows4(xent_rows_kernel<float>, R, stream, logits, ld, R, C, labels, ignore_index, grad_scale, loss_row, pred,
+                      (float*)dlogits, ldd, rowdot);
 }
 
 #ifndef CCLIP_F16

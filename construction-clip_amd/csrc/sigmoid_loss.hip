@@ -13,7 +13,8 @@
 //                  The pairwise form is the same kernel with row ids rank * N_loc + r and column ids 0 .. C-1.
 //
 // Unlike the softmax kernels there is no row statistic to wait for: loss, gradient and the row sums come out of ONE sweep, each
-// element read once and written once.  Shape, grid cap and the direct (through-L2) read of col_class are class_loss.hip's.
+// element read once and written once.  Shape, grid cap and the sweep are row_kernels.h's; why col_class is read directly
+// (through L2) is in class_loss.hip.
 //
 // Numerics.  With x = -y u, e = exp(-|x|) in (0, 1] and w = 1 + e:
 //   softplus(x) = max(x, 0) + log1p(e),    sigmoid(x) = x >= 0 ? 1 / w : e / w
@@ -25,8 +26,7 @@
 
 namespace CCLIP_NS {
 
-// `dlogits` may alias `logits` (clip/loss.py overwrites the logits with their gradient in place), so neither carries
-// __restrict__: every element is read by the lane that later writes it, and nothing of a row is read twice.
+// `dlogits` may alias `logits` (row_kernels.h, sweep_row4_store): nothing of a row is read twice.
 template <bool GRAD>
 __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* logits, long ld, int R, int C,
                                                            const int* __restrict__ row_class,
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* logits, 
     float m = -__builtin_inff(), loss = 0.f, dot = 0.f, sum = 0.f;
     int arg = 0x7fffffff;
     // one cell: the running (max, argmax) of the row, its loss term, and its gradient (returned; summed into dot and sum)
-    auto step = [&](float v, int k, int c) {
+    sweep_row4_store<GRAD>(row, col_class, drow, lane, C, [&](float v, int k, int c) {
       if (v > m) { m = v; arg = c; }
       const bool pos = labelled && k == cls;
       const float u = v + bias, ax = fabsf(u);
@@ -58,26 +58,10 @@ __global__ __launch_bounds__(256) void sigmoid_rows_kernel(const float* logits, 
       dot += d * v;
       sum += d;
       return d;
-    };
-    int c = lane;
-    // four columns per trip, all eight loads issued before the first use (class_loss.hip: at one wave per SIMD nothing else
-    // hides a load's latency); every element is read before the (possibly aliasing) write of the same element
-    for (; c + 192 < C; c += 256) {
-      const float v0 = row[c], v1 = row[c + 64], v2 = row[c + 128], v3 = row[c + 192];
-      const int k0 = col_class[c], k1 = col_class[c + 64], k2 = col_class[c + 128], k3 = col_class[c + 192];
-      const float d0 = step(v0, k0, c), d1 = step(v1, k1, c + 64), d2 = step(v2, k2, c + 128), d3 = step(v3, k3, c + 192);
-      if (GRAD) { drow[c] = d0; drow[c + 64] = d1; drow[c + 128] = d2; drow[c + 192] = d3; }
-    }
-    for (; c < C; c += 64) {
-      const float d = step(row[c], col_class[c], c);
-      if (GRAD) drow[c] = d;
-    }
+    });
     wave_argmax(m, arg);
     if (loss_row) { loss = wave_sum(loss); if (lane == 0) loss_row[r] = labelled ? loss : 0.f; }
-    if (lane == 0) {
-      if (pred) pred[r] = arg;
-      if (hit) hit[r] = (labelled && arg < C && col_class[arg] == cls) ? 1.f : 0.f;   // arg >= C: a row without a maximum (all NaN)
-    }
+    if (lane == 0) store_pred_hit(r, arg, C, pred, hit, [=] { return labelled && col_class[arg] == cls; });
     if (GRAD) {
       if (rowdot) { dot = wave_sum(dot); if (lane == 0) rowdot[r] = dot; }
       if (rowsum) { sum = wave_sum(sum); if (lane == 0) rowsum[r] = sum; }
@@ -92,14 +76,8 @@ extern "C" int cclip_sigmoid_rows(const float* logits, int64_t ld, int32_t R, in
                                   const int32_t* col_class, const float* bias_dev, float grad_scale, float* loss_row,
                                   int32_t* pred, float* hit, float* dlogits, int64_t ldd, float* rowdot, float* rowsum,
                                   hipStream_t stream) {
-  if (!logits || !row_class || !col_class || !bias_dev || R <= 0 || C <= 0) return CCLIP_ERR_ARG;
-  if (ld < C || (dlogits && ldd < C)) return CCLIP_ERR_ARG;
-  if (dlogits)
-    hipLaunchKernelGGL(sigmoid_rows_kernel<true>, dim3(grid_rows4(R)), dim3(256), 0, stream, logits, (long)ld, R, C, row_class,
-                       col_class, bias_dev, grad_scale, loss_row, pred, hit, dlogits, (long)ldd, rowdot, rowsum);
-  else
-    hipLaunchKernelGGL(sigmoid_rows_kernel<false>, dim3(grid_rows4(R)), dim3(256), 0, stream, logits, (long)ld, R, C, row_class,
-                       col_class, bias_dev, grad_scale, loss_row, pred, hit, (float*)nullptr, 0L, (float*)nullptr,
-                       (float*)nullptr);
-  return cclip_launch_status();
+  if (!row_loss_shape_ok(logits, R, C, ld, dlogits, ldd) || !row_class || !col_class || !bias_dev) return CCLIP_ERR_ARG;
+  // without a gradient the kernel reads none of dlogits, ldd, rowdot, rowsum
+  return launch_rows4(dlogits ? sigmoid_rows_kernel<true> : sigmoid_rows_kernel<false>, R, stream, logits, ld, R, C, row_class,
+                      col_class, bias_dev, grad_scale, loss_row, pred, hit, dlogits, ldd, rowdot, rowsum);
 }

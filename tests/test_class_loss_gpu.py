@@ -61,7 +61,9 @@ def _compare(got, ref, tag):
     assert torch.all((rowdot.double() - rdot).abs() < H.GRAD_TOL * rabs + 1e-7)
 
 
-@pytest.mark.parametrize("R,C", [(7, 9), (5, 70), (4, 64), (130, 257), (16385, 8)])
+# (3, 255), (5, 256): both sides of the four-column trip of row_kernels.h (at C = 255 lane 63 falls to the tail while the others
+# take a trip); (9, 1000): several trips and a tail
+@pytest.mark.parametrize("R,C", [(7, 9), (5, 70), (4, 64), (130, 257), (16385, 8), (3, 255), (5, 256), (9, 1000)])
 def test_kernel_against_float64(R, C):
     gen = torch.Generator(device="cuda").manual_seed(R * 1000 + C)
     lg = torch.randn(R, C, device="cuda", generator=gen)

@@ -72,8 +72,9 @@ def _case(R, C, seed, lo=-1):
 
 
 # lane tail; one cell; one past a wave; an exact wave; one past it; the four-column trip plus the remainder loop and more than one
-# block; more rows than one trip of the capped grid (4096 blocks of four rows)
-@pytest.mark.parametrize("R,C", [(7, 9), (1, 1), (5, 70), (4, 64), (3, 65), (130, 257), (16385, 8)])
+# block; more rows than one trip of the capped grid (4096 blocks of four rows); both sides of the four-column trip of
+# row_kernels.h (at C = 255 lane 63 falls to the tail while the others take a trip); several trips and a tail
+@pytest.mark.parametrize("R,C", [(7, 9), (1, 1), (5, 70), (4, 64), (3, 65), (130, 257), (16385, 8), (3, 255), (5, 256), (9, 1000)])
 def test_kernel_against_float64(R, C):
     lg, a, b, bias = _case(R, C, R * 1000 + C)
     gs = 1.0 / R

@@ -7,8 +7,10 @@ csrc/score_tiles.h, score_key.h or row_kernels.h, a compiler update): seeded inp
 similarity_topk and lm_head_score run in bf16 and fp16 over shapes that reach every kernel variant, both row-tile counts, a
 partly empty work-group, row widths that are not a power-of-two number of chunks, padded row strides, a column slice of a
 wider buffer, duplicated rows / equal columns, a NaN row, an ignored and an out-of-range label.  xent_rows,
-xent_rows_classes and sigmoid_rows: R = 9 over C = 1, 63, 64, 257, 300 without a gradient, with one, and with the gradient
-written over the logits, every input holding a row of ties and an all-NaN row; xent_rows also with a 16-bit gradient.
+xent_rows_classes, sigmoid_rows and kl_rows: R = 9 over C = 1, 63, 64, 255, 256, 257, 300 (255 .. 257 straddle the four-column
+trip of row_kernels.h) without a gradient, with one, and with the gradient written over the logits, every input holding a row of
+ties and an all-NaN row; xent_rows also with a 16-bit gradient; kl_rows with a teacher of a row stride of its own that holds
+cells at -inf (one of them a lane's first column) and one row equal to the student's.
 caption_select: N = 3, K = 1, 5, 64, E = 4, 512, 1024 with references, with and without lm_mean, with a NaN score.
 sample_rows: V = 5, 4099, 50257 with top-k, with top-p and with neither, from fixed u.  l2norm_fwd and text_embed: one case.
 The other kernels on csrc/score_sweep.h - similarity_range (self-join on and off), kmeans_assign, cache_affinity forward and
@@ -30,7 +32,7 @@ DTYPES = ((torch.bfloat16, "bf16"), (torch.float16, "f16"))
 TOPK_SHAPES = [(1, 1, 64, 1), (3, 5, 128, 5), (16, 64, 512, 10), (130, 4097, 128, 10), (100, 1000, 768, 64), (16, 1000, 1024, 10),
                (3, 1000, 32, 5), (100, 1000, 96, 5), (100, 4097, 160, 10)]
 LM_SHAPES = [(1, 1, 32), (3, 15, 32), (17, 300, 128), (300, 300, 128), (70, 2050, 512), (65, 4099, 768), (33, 1000, 1024)]
-ROW_R, ROW_C = 9, (1, 63, 64, 257, 300)
+ROW_R, ROW_C = 9, (1, 63, 64, 255, 256, 257, 300)
 # (operand rows, streamed rows, D)
 SWEEP_SHAPES = [(1, 1, 32), (63, 17, 128), (65, 64, 160), (129, 65, 512), (65, 1025, 768), (129, 3000, 1024), (129, 3000, 128),
                 (1, 1025, 512), (63, 3000, 160)]
@@ -169,6 +171,17 @@ def row_cases():
             ops.sigmoid_rows(logits, row_class, col_class, bias, loss_row=out["loss_row"], pred=out["pred"], hit=out["hit"], dlogits=dl,
                              grad_scale=0.37, rowdot=out.get("rowdot"), rowsum=out.get("rowsum"))
             yield f"sigmoid_rows/C{C}/{grad}", out
+            logits, labels, row_class, col_class = row_inputs(C, 600 + C)
+            teacher = rnd(602 + C, ROW_R, C, scale=3.0).cuda()
+            teacher[4] = logits[4]                                  # a teacher row equal to the student's: loss and gradient 0
+            teacher[0, C // 2] = teacher[1, 0] = float("-inf")      # masked cells; [1, 0] is the first column lane 0 sees
+            dl = {"none": None, "f32": torch.zeros_like(logits), "alias": logits}[grad]
+            out = {"loss_row": f(), "pred": f(torch.int32), "agree": f()}
+            if dl is not None:
+                out.update(dlogits=dl, rowdot=f())
+            ops.kl_rows(logits, padded(teacher, 8), loss_row=out["loss_row"], pred=out["pred"], agree=out["agree"], dlogits=dl,
+                        grad_scale=0.37, rowdot=out.get("rowdot"))
+            yield f"kl_rows/C{C}/{grad}", out
 
 
 def select_cases():
