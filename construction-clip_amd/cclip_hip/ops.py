@@ -687,7 +687,7 @@ def attention_probs(q, k, P, *, B: int, T: int, H: int, causal: bool = False, sc
 
 # --------------------------------------------------------------------------------------------
 # embedding analysis (retrieval, range search, lm_head scoring, cache classifier, k-means, coreset, spanning tree, linear probe,
-# t-SNE, label spreading, concept codes): one operand contract.  Every wrapper checks in the order cuda, dtype, shape over all
+# t-SNE, label spreading, concept codes, class moments, Gaussian scores): one operand contract.  Every wrapper checks in the order cuda, dtype, shape over all
 # its tensors, then the size limits, then alignment, and touches the library only after that.
 # --------------------------------------------------------------------------------------------
 def _fits(shape, got) -> bool:
@@ -2430,3 +2430,107 @@ def concept_codes(x, c, l1: float, eta: float, iters: int, *, out_w=None, worksp
              _p(out_w), c_long(ldw), _p(resid2), _p(l1norm), _p(nnz), _p(delta), _p(kkt), _p(workspace),
              c_long(workspace.numel() * 4), _stream()), "cclip_concept_codes")
     return out_w, resid2, l1norm, nnz, delta, kkt
+
+
+MOMENTS_MAX_C = 256
+GAUSS_MAX_R = 1024
+GAUSS_MAX_C = 256
+
+
+def moments_parts(N: int, C: int, D: int) -> int:
+    """the number of parts cclip_class_moments splits the rows into: a function of (N, C, D) alone (0 for a refused problem)"""
+    return _query("cclip_moments_parts", c_int, c_long(N), c_int(C), c_int(D))
+
+
+def moments_workspace(N: int, C: int, D: int) -> int:
+    """bytes of workspace cclip_class_moments needs (the partial 128 x 128 blocks of every part and the non-finite flags:
+    include/cclip_hip.h states the closed form; 0 for a problem it would refuse)"""
+    return _query("cclip_moments_workspace", c_long, c_long(N), c_int(C), c_int(D))
+
+
+def class_moments(x, labels, C: int, *, out=None, workspace=None):
+    """Second moments of the rows of x [N, D] (16-bit, under the contract of kmeans_assign) by class: labels int32 [N] or None
+    (every row is class 0; C must be 1).  Returns (count int32 [C], sum fp32 [C, D], gram fp32 [D, D]): rows per class, the sum of
+    each class's rows, and the sum of x^T x over the live rows; a row whose label lies outside [0, C) is dropped from all three.
+    Products are exact, every entry is an fp32 sum over moments_parts(N, C, D) chains merged in a fixed tree; gram is bitwise
+    symmetric; two calls are bitwise equal.  `out`: (count, sum, gram) to write into; workspace: a contiguous fp32 device tensor
+    of at least moments_workspace(N, C, D) bytes, 16-byte aligned.  1 <= C <= 256, D % 32 == 0, 32 <= D <= 1024, N < 2^31.
+    Enqueues three launches; no host read."""
+    fname = "class_moments"
+    _view16(fname, ((x, "x", HALF_TYPES, None, False),))
+    (N, D), dev = x.shape, x.device
+    _dev_tensors(fname, dev, ((labels, "labels", torch.int32, (N,), True),), host_error=ValueError, dtype_error=ValueError)
+    if isinstance(C, bool) or int(C) != C:
+        raise ValueError(f"{fname}: C = {C!r} must be an integer")
+    C = int(C)
+    _limits16(fname, D, "N", (N,))
+    if not 1 <= C <= MOMENTS_MAX_C:
+        raise NotImplementedError(f"{fname}: C = {C}; the kernel takes 1 .. {MOMENTS_MAX_C} classes")
+    if labels is None and C != 1:
+        raise ValueError(f"{fname}: without labels every row is class 0: C must be 1, got {C}")
+    ldx = _ld16(fname, x, "x")
+    o = tuple(out) if out is not None else (None, None, None)
+    if len(o) != 3:
+        raise ValueError(f"{fname}: out must be (count, sum, gram)")
+    count = _out(fname, o[0], "count", torch.int32, (C,), dev)
+    csum = _out(fname, o[1], "sum", torch.float32, (C, D), dev)
+    gram = _out(fname, o[2], "gram", torch.float32, (D, D), dev)
+    nbytes = moments_workspace(N, C, D)
+    workspace = _workspace(fname, workspace, nbytes, torch.float32, dev, align16=True)
+    fn = _fn("cclip_class_moments", x)
+    check(fn(_p(x), c_long(ldx), c_long(N), c_int(D), _p(labels), c_int(C), _p(count), _p(csum), _p(gram), _p(workspace),
+             c_long(workspace.numel() * 4), _stream()), "cclip_class_moments")
+    return count, csum, gram
+
+
+def gauss_scores_workspace(R: int, D: int) -> int:
+    """bytes of workspace cclip_gauss_scores needs (the hi + lo image of T: 4 * 16 ceil(R / 16) * D; 0 for refused sizes)"""
+    return _query("cclip_gauss_scores_workspace", c_long, c_long(R), c_int(D))
+
+
+def gauss_scores(x, T, *, t0=None, centres=None, offset=None, want_d2: bool = False, want_z: bool = False, out=None):
+    """z = (T_hi + T_lo) x - t0 for every row of x [Q, D] (16-bit, under the contract of kmeans_assign) with T fp32 [R, D] and
+    t0 fp32 [R] or None, then with centres fp32 [C, R] and offset fp32 [C] or None:
+        d2[q, c] = sum_r (z[q, r] - centres[c, r])^2     score[q, c] = -0.5 d2[q, c] + offset[c]
+    in fp32 as include/cclip_hip.h states (cclip_gauss_scores; never the expanded form).  Returns (pred int32 [Q], lse fp32 [Q],
+    nearest int32 [Q], dmin fp32 [Q], d2 fp32 [Q, C] or None, z fp32 [Q, R] or None): argmax and logsumexp of the scores (ties to
+    the lower class, NaN lowest), argmin and min of d2; d2 and z only when asked for.  With centres=None only z is computed (the
+    PCA transform) and the first five are None.  `out`: a tuple of six tensors (or None) to write those into.  A row's outputs
+    depend on neither Q nor its position; two calls are bitwise equal.  1 <= R <= 1024, 1 <= C <= 256, D % 32 == 0,
+    32 <= D <= 1024.  Enqueues two launches; no host read."""
+    fname = "gauss_scores"
+    _dev_tensors(fname, None, ((x, "x", None, None, False), (T, "T", None, None, False)), contiguous=False)   # cuda, both operands, first
+    _view16(fname, ((x, "x", HALF_TYPES, None, False),))
+    (Q, D), dev = x.shape, x.device
+    R = _dev_tensor(fname, T, "T", torch.float32, (None, D), dev, device_error=TypeError).shape[0]
+    _dev_tensors(fname, dev, ((t0, "t0", torch.float32, (R,), True), (centres, "centres", torch.float32, (None, R), True)),
+                 host_error=ValueError, dtype_error=ValueError)
+    C = 0 if centres is None else centres.shape[0]
+    _dev_tensors(fname, dev, ((offset, "offset", torch.float32, (C,), True),), host_error=ValueError, dtype_error=ValueError)
+    if centres is None and (offset is not None or want_d2):
+        raise ValueError(f"{fname}: offset and want_d2 need centres")
+    _limits16(fname, D, "Q", (Q,))
+    if not 1 <= R <= GAUSS_MAX_R:
+        raise NotImplementedError(f"{fname}: R = {R}; the kernel takes 1 .. {GAUSS_MAX_R} transform rows")
+    if centres is not None and not 1 <= C <= GAUSS_MAX_C:
+        raise NotImplementedError(f"{fname}: C = {C}; the kernel takes 1 .. {GAUSS_MAX_C} centres")
+    ldx = _ld16(fname, x, "x")
+    o = tuple(out) if out is not None else (None,) * 6
+    if len(o) != 6:
+        raise ValueError(f"{fname}: out must be (pred, lse, nearest, dmin, d2, z), None where nothing is provided")
+    pred = lse = nearest = dmin = d2 = z = None
+    if centres is not None:
+        pred = _out(fname, o[0], "pred", torch.int32, (Q,), dev)
+        lse = _out(fname, o[1], "lse", torch.float32, (Q,), dev)
+        nearest = _out(fname, o[2], "nearest", torch.int32, (Q,), dev)
+        dmin = _out(fname, o[3], "dmin", torch.float32, (Q,), dev)
+        if want_d2 or o[4] is not None:
+            d2 = _out(fname, o[4], "d2", torch.float32, (Q, C), dev)
+    if centres is None or want_z or o[5] is not None:
+        z = _out(fname, o[5], "z", torch.float32, (Q, R), dev)
+    nbytes = gauss_scores_workspace(R, D)
+    ws = _workspace(fname, None, nbytes, torch.float32, dev)
+    fn = _fn("cclip_gauss_scores", x)
+    check(fn(_p(x), c_long(ldx), c_long(Q), c_int(D), _p(T), _p(t0), c_int(R), _p(centres), _p(offset), c_int(C), _p(pred), _p(lse),
+             _p(nearest), _p(dmin), _p(d2), _p(z), _p(ws), c_long(nbytes), _stream()), "cclip_gauss_scores")
+    return pred, lse, nearest, dmin, d2, z

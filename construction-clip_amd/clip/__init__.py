@@ -20,5 +20,6 @@ from .hdbscan import hdbscan, HDBSCANResult, mutual_reachability_mst, MSTResult 
 from .concepts import ConceptDictionary, ConceptDecomposition, ConceptProfile, decompose, concept_profile, distinctive  # noqa: F401  (sparse non-negative concept codes: what is in an embedding, in words)
 from .fewshot import CacheClassifier, confusion_matrix  # noqa: F401  (few-shot classification from the stored, labelled embeddings)
 from .probe import LinearProbe, ProbeLossFunction, ProbeFitResult  # noqa: F401  (linear probe: logistic regression on the stored embeddings)
+from .gaussian import GaussianClassifier, ClassMoments, MahalanobisScores, PCAResult, class_moments, pca  # noqa: F401  (Gaussian class models: training-free classifier, outlier scores, PCA)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

@@ -218,6 +218,17 @@ class EmbeddingIndex:
         from .concepts import decompose
         return decompose(self, dictionary, **kw)
 
+    def gaussian(self, key: str, **kw):
+        """A `GaussianClassifier` fitted on the stored rows with the labels the metadata carries under `key`
+        (clip/gaussian.py: csrc/embed_moments.hip, csrc/gauss_scores.hip).  The rows are used as stored, not copied."""
+        from .gaussian import GaussianClassifier
+        return GaussianClassifier.from_index(self, key, **kw)
+
+    def pca(self, k: int, **kw):
+        """The k leading principal components of the stored rows (clip/gaussian.py): a `PCAResult`."""
+        from .gaussian import pca
+        return pca(self, k, **kw)
+
     @torch.no_grad()
     def search_text(self, model, tokens: torch.Tensor, k: int = 10):
         return self.search(model.encode_text(tokens.to(self._buf.device)), k)

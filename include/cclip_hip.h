@@ -615,6 +615,57 @@ int cclip_concept_codes(const void* x, int64_t ldx, int64_t N, const void* c, in
                         float eta, int32_t iters, float* w, int64_t ldw, float* resid2, float* l1norm, int32_t* nnz,
                         float* delta, float* kkt, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- Gaussian class models: second moments of stored embeddings (csrc/embed_moments.hip) ---------------------------------
+ * x [N, D] bf16 (fp16 in the twin) under the contract of cclip_kmeans_assign (row stride ldx in elements, a multiple of 8, inner
+ * stride 1, 16-byte aligned; D % 32 == 0, 32 <= D <= 1024, N < 2^31); labels int32 [N], or NULL with C == 1 (every row is class
+ * 0); 1 <= C <= 256.  A row whose label lies outside [0, C) is dropped from every output.
+ *   count int32 [C] = rows per class     sum fp32 [C, D] = sum of the class's rows     gram fp32 [D, D] = sum_live x^T x
+ * Products of two 16-bit values are exact in fp32 and enter one fp32 accumulator chain per entry and part on the MFMA, rows in
+ * ascending order (both products are [onehot(labels) | x]^T x over tiles of 32 rows).  The rows are split into
+ * cclip_moments_parts(N, C, D) parts of tpp consecutive tiles; a second launch adds the parts in a fixed tree (runs of 8 in
+ * ascending order, the runs in ascending order) and writes gram[a, b] and gram[b, a] from the same value: gram is bitwise
+ * symmetric, only block pairs on and above the diagonal are computed.  Padding rows and dropped rows add exactly +0.  A NaN or
+ * Inf in column a of a live row of class c reaches row and column a of gram (its outer product: NaN * 0 is NaN) and sum[c, a],
+ * and nothing else: in the one-hot product such an element enters as zero and is recorded by an integer atomic OR, from which
+ * the merge restores NaN / +Inf / -Inf.  count is added by integer atomics.  No float atomics; every choice is a function of
+ * (N, C, D) alone; two calls are bitwise equal.  Three launches on `stream`; nothing is read on the host.
+ * workspace: at least cclip_moments_workspace(N, C, D) bytes (0 for arguments the call would refuse), 16-byte aligned, contents
+ * meaningless before and after.  With B = ceil(D / 128), J = B (B + 1) / 2 + ceil(C / 128) B jobs of one 128 x 128 block each,
+ * T = ceil(N / 32), Pmax = clamp(2^25 / (65536 J), 1, 1024), tpp = max(8, ceil(T / Pmax)), P = ceil(T / tpp) = cclip_moments_parts:
+ *   bytes = 65536 P J  (the partial blocks, at most 32 MB)  +  4 C D  (the flags)
+ * CCLIP_ERR_ARG (nothing launched, outputs untouched): a null x, count, sum, gram or workspace; labels NULL with C != 1;
+ * N <= 0 or N >= 2^31; C < 1 or C > 256; D < 32, D % 32 or D > 1024; ldx below D or not a multiple of 8; x or workspace not
+ * 16-byte aligned; a misaligned int32 / fp32 array; workspace too small. */
+int64_t cclip_moments_workspace(int64_t N, int32_t C, int32_t D);
+int32_t cclip_moments_parts(int64_t N, int32_t C, int32_t D);
+int cclip_class_moments(const void* x, int64_t ldx, int64_t N, int32_t D, const int32_t* labels, int32_t C, int32_t* count,
+                        float* sum, float* gram, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- Gaussian class models: transform, distances to centres, scores (csrc/gauss_scores.hip) -------------------------------
+ * x [Q, D] 16-bit under the contract above; T fp32 [R, D] contiguous, 1 <= R <= 1024 (padded to 16 inside); t0 fp32 [R] or
+ * NULL (= 0); centres fp32 [C, R] contiguous with 1 <= C <= 256, or NULL with C == 0; offset fp32 [C] or NULL (= 0).
+ * T enters the MFMA as the 16-bit pair hi = round16(T), lo = round16(T - hi) - the pair of W in cclip_probe_forward - written
+ * by a small launch into the workspace:
+ *   z[q, r]     = acc - t0[r]; acc is ONE fp32 accumulator chain that takes x * hi, then x * lo, of every k-step d = 0, 32, ..
+ *   d2[q, c]    = sum_r (z[q, r] - centres[c, r])^2   fp32, r ascending; subtract, multiply, add - the expansion
+ *                 |z|^2 - 2 z.m + |m|^2 is NOT used: it cancels once T is an ill-conditioned whitening
+ *   score[q, c] = -0.5 d2[q, c] + offset[c]
+ * Per row (each [Q] contiguous): pred int32 = argmax_c score (equal scores go to the LOWER class, NaN ranks lowest);
+ * lse fp32 = log sum_c exp score by a running maximum; nearest int32 = argmax_c (-d2) under the same rule; dmin = d2[q, nearest].
+ * d2 fp32 [Q, C] and z fp32 [Q, R] are written only where the pointer is not NULL.  With centres == NULL only z is written
+ * (required then; offset and d2 must be NULL): the PCA transform.  A work-group keeps its rows' z in LDS between the stages.
+ * A row's outputs depend on neither Q nor its position; a row with a NaN gets NaN z, d2, lse and dmin, pred = nearest = 0, and
+ * touches no other row.  No atomics, no fused multiply-add; two calls are bitwise equal.  Two launches; no host read.
+ * workspace: at least cclip_gauss_scores_workspace(R, D) = 4 * 16 ceil(R / 16) * D bytes (the pair image; 0 for sizes the call
+ * would refuse), 16-byte aligned.
+ * CCLIP_ERR_ARG (nothing launched): a null x, T or workspace; centres without pred, lse, nearest or dmin, or C outside 1 .. 256;
+ * no centres and no z, or offset, d2 or C != 0 without centres; Q <= 0 or Q >= 2^31; R < 1 or R > 1024; D < 32, D % 32 or
+ * D > 1024; ldx below D or not a multiple of 8; x or workspace not 16-byte aligned; a misaligned array; workspace too small. */
+int64_t cclip_gauss_scores_workspace(int64_t R, int32_t D);
+int cclip_gauss_scores(const void* x, int64_t ldx, int64_t Q, int32_t D, const float* T, const float* t0, int32_t R,
+                       const float* centres, const float* offset, int32_t C, int32_t* pred, float* lse, int32_t* nearest,
+                       float* dmin, float* d2, float* z, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- t-SNE of stored embeddings: neighbour probabilities (csrc/tsne.hip, fp32 only) -------------------------------------
  * scores fp32 [N, k] (row stride ld >= k elements): the similarities of every row's k nearest OTHER unit rows, in any order.
  * Per row, with d2_j = 2 - 2 s_j (a negative value taken as 0) and diff_j = d2_j - min_j d2_j, all in fp32:
@@ -1135,6 +1186,11 @@ int cclip_probe_backward_f16(const void* x, int64_t ldx, int64_t N, int32_t D, c
 int cclip_concept_codes_f16(const void* x, int64_t ldx, int64_t N, const void* c, int64_t ldc, int64_t V, int32_t D, float l1,
                             float eta, int32_t iters, float* w, int64_t ldw, float* resid2, float* l1norm, int32_t* nnz,
                             float* delta, float* kkt, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cclip_class_moments_f16(const void* x, int64_t ldx, int64_t N, int32_t D, const int32_t* labels, int32_t C, int32_t* count,
+                            float* sum, float* gram, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cclip_gauss_scores_f16(const void* x, int64_t ldx, int64_t Q, int32_t D, const float* T, const float* t0, int32_t R,
+                           const float* centres, const float* offset, int32_t C, int32_t* pred, float* lse, int32_t* nearest,
+                           float* dmin, float* d2, float* z, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
