@@ -851,6 +851,63 @@ def similarity_topk(q, g, k: int, out_scores=None, out_index=None):
     return out_scores, out_index
 
 
+def similarity_topk_biased(q, g, k: int, bias, scale: float = 1.0, out_scores=None, out_index=None):
+    """Exact top-k of t[i, n] = fmaf(scale, <q[i], g[n]>, bias[n]): q, g, k and the outputs as for similarity_topk, bias a
+    contiguous fp32 [N] on q's device.  Returns (t fp32 [Q, k] descending, index int32 [Q, k]); same order on t: equal t by the
+    lower gallery index, NaN last.  bias[n] = -inf excludes row n (it can only trail the finite rows, by ascending index);
+    scale = 1 with a zero bias is similarity_topk bit for bit.  Enqueues two launches; no host read."""
+    fname = "similarity_topk_biased"
+    Q, N, D = _pair16(fname, q, "q", g, "g")
+    if not 1 <= k <= SIMILARITY_TOPK_MAX_K:
+        raise ValueError(f"{fname}: k = {k} outside the kernel's range 1 .. {SIMILARITY_TOPK_MAX_K}")
+    if k > N:
+        raise ValueError(f"{fname}: k = {k} above the gallery's {N} rows")
+    _limits16(fname, D, "Q N", (Q, N), min_d=0, max_d=SIMILARITY_TOPK_MAX_D)
+    ldq, ldg = _ld16(fname, q, "q"), _ld16(fname, g, "g")
+    fn = _fn("cclip_similarity_topk_biased", q, g)
+    _dev_tensor(fname, bias, "bias", torch.float32, (N,), q.device)
+    scale = float(scale)
+    if scale != scale:
+        raise ValueError(f"{fname}: scale is NaN")
+    out_scores = _out(fname, out_scores, "out_scores", torch.float32, (Q, k), q.device, host_error=TypeError, dtype_error=TypeError)
+    out_index = _out(fname, out_index, "out_index", torch.int32, (Q, k), q.device, host_error=TypeError, dtype_error=TypeError)
+    nbytes = similarity_topk_workspace(Q, N, k)
+    ws = _workspace(fname, None, nbytes, torch.int64, q.device)
+    check(fn(_p(q), c_long(ldq), c_int(Q), _p(g), c_long(ldg), c_long(N), c_int(D), c_int(k), _p(bias), c_float(scale),
+             _p(out_scores), _p(out_index), _p(ws), c_long(nbytes), _stream()), "cclip_similarity_topk_biased")
+    return out_scores, out_index
+
+
+def bank_lse_splits(N: int, B: int) -> int:
+    """splits of the bank cclip_bank_lse works in for this problem"""
+    return _query("cclip_bank_lse_splits", c_int, c_long(N), c_long(B))
+
+
+def bank_lse_workspace(N: int, B: int) -> int:
+    """bytes of per-split (max, sum) pairs cclip_bank_lse needs for this problem (N * splits * 8)"""
+    return _query("cclip_bank_lse_workspace", c_long, c_long(N), c_long(B))
+
+
+def bank_lse(g, bank, beta: float, *, out=None, workspace=None):
+    """lse[j] = log sum_b exp(beta * <bank[b], g[j]>) for every gallery row: g [N, D] and bank [B, D] 16-bit (same dtype) as the
+    operands of similarity_topk, each score with the bits similarity_topk returns for the pair.  Returns fp32 [N].  The B x N
+    matrix is never formed; the scratch is N * splits (max, sum) pairs (`workspace`: an int64 tensor of bank_lse_workspace
+    bytes, allocated when None).  B = 1 gives beta * score exactly; a NaN in gallery row j makes entry j NaN and no other; a
+    non-finite bank row reaches every entry.  D % 32 == 0, D <= 1024, N, B < 2^31.  Enqueues two launches; no host read."""
+    fname = "bank_lse"
+    N, B, D = _pair16(fname, g, "g", bank, "bank")
+    beta = _finite(fname, "beta", beta)
+    _limits16(fname, D, "N B", (N, B), min_d=0, max_d=SIMILARITY_TOPK_MAX_D)
+    ldg, ldb = _ld16(fname, g, "g"), _ld16(fname, bank, "bank")
+    fn = _fn("cclip_bank_lse", g, bank)
+    out = _out(fname, out, "out", torch.float32, (N,), g.device, host_error=TypeError, dtype_error=TypeError)
+    nbytes = bank_lse_workspace(N, B)
+    ws = _workspace(fname, workspace, nbytes, torch.int64, g.device)
+    check(fn(_p(g), c_long(ldg), c_long(N), _p(bank), c_long(ldb), c_long(B), c_int(D), c_float(beta), _p(out), _p(ws),
+             c_long(nbytes), _stream()), "cclip_bank_lse")
+    return out
+
+
 def similarity_range_workspace(Q: int, N: int) -> int:
     """bytes of per-(query row, gallery split) hit counts cclip_similarity_range_count fills (Q * splits * 4)"""
     return _query("cclip_similarity_range_workspace", c_long, c_int(Q), c_long(N))

@@ -12,6 +12,7 @@ from .explain import interpret_rows, text_row_scores  # noqa: F401  (the same ro
 from .explain import jet_table, relevance_overlay, text_heat_html  # noqa: F401  (attention.py:77-96, 113-143: the overlay picture)
 from .retrieval import EmbeddingIndex, retrieval_recall  # noqa: F401  (search over the embedding pickle; image <-> text R@k)
 from .retrieval import connected_components, group_split  # noqa: F401  (near-duplicate groups and leak-free held-out splits)
+from .hubness import fit_querybank, QueryBank, hubness, HubnessReport  # noqa: F401  (hubness-corrected retrieval: inverted softmax, QB-Norm, CSLS)
 from .cluster import kmeans, KMeansResult, cluster_purity, name_clusters  # noqa: F401  (spherical k-means of the unlabelled photos)
 from .tsne import tsne, TSNEResult  # noqa: F401  (a 2-D map of the stored embeddings on the kNN graph)
 from .propagate import spread_labels, LabelSpreadResult, affinity_csr  # noqa: F401  (label spreading: a few labels over the kNN graph)

@@ -107,9 +107,17 @@ class EmbeddingIndex:
         return cls(emb, dtype=dtype, metadata=captions)
 
     @torch.no_grad()
-    def search(self, queries: torch.Tensor, k: int = 10) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, queries: torch.Tensor, k: int = 10, *, querybank=None, mask: Optional[torch.Tensor] = None,
+               return_gate: bool = False):
         """queries [Q, E] (any float dtype, anywhere) -> (scores fp32 [Q, k] descending, indices int64 [Q, k]) on the device:
-        cosine similarity of the normalised 16-bit rows, equal scores by the lower index."""
+        cosine similarity of the normalised 16-bit rows, equal scores by the lower index.
+
+        querybank: a `QueryBank` (`self.querybank(bank)`, clip/hubness.py) ranks by the hubness-corrected value
+        fmaf(scale, cosine, bias[row]) instead and returns those values; with method "dis" only the queries whose raw best row
+        is in the bank's activation set do, every other query keeps its raw result bit for bit.  A bank fitted at another
+        len(index) raises ValueError.  mask: bool [N], True = leave the row out (filtered search: `labels != wanted`); such a
+        row can only appear once the other rows run out (k above their number), with score -inf.  return_gate appends a bool
+        [Q]: the queries that took the normalised path.  Without a keyword the call is the plain top-k, as ever."""
         if self._n == 0:
             raise ValueError("search: the index is empty")
         if queries.dim() == 1:
@@ -117,8 +125,19 @@ class EmbeddingIndex:
         if queries.dim() != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"search: expected [*, {self.dim}] queries, got {tuple(queries.shape)}")
         q = normalize_rows(queries, self.dtype, self._buf.device)
-        scores, index = ops.similarity_topk(q, self.features, int(k))
-        return scores, index.long()
+        if querybank is None and mask is None:
+            scores, index = ops.similarity_topk(q, self.features, int(k))
+            gate = torch.zeros(q.shape[0], device=q.device, dtype=torch.bool) if return_gate else None
+        else:
+            from .hubness import corrected_topk
+            scores, index, gate = corrected_topk(q, self.features, int(k), querybank, mask)
+        return (scores, index.long(), gate) if return_gate else (scores, index.long())
+
+    def querybank(self, bank: torch.Tensor, **kw):
+        """A `QueryBank` for the rows stored now (clip/hubness.py: csrc/embed_hub.hip), from `bank` [B, E], a sample of typical
+        queries: method "dis" (default), "is" or "csls", beta, k, activation_k.  Fit it again after `add`."""
+        from .hubness import fit_querybank
+        return fit_querybank(self, bank, **kw)
 
     @torch.no_grad()
     def range_search(self, queries: torch.Tensor, threshold: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -230,12 +249,12 @@ class EmbeddingIndex:
         return pca(self, k, **kw)
 
     @torch.no_grad()
-    def search_text(self, model, tokens: torch.Tensor, k: int = 10):
-        return self.search(model.encode_text(tokens.to(self._buf.device)), k)
+    def search_text(self, model, tokens: torch.Tensor, k: int = 10, **kw):
+        return self.search(model.encode_text(tokens.to(self._buf.device)), k, **kw)
 
     @torch.no_grad()
-    def search_image(self, model, images: torch.Tensor, k: int = 10):
-        return self.search(model.encode_image(images.to(self._buf.device)), k)
+    def search_image(self, model, images: torch.Tensor, k: int = 10, **kw):
+        return self.search(model.encode_image(images.to(self._buf.device)), k, **kw)
 
 
 def connected_components(n: int, pairs: torch.Tensor) -> torch.Tensor:
@@ -311,11 +330,14 @@ def recall_from_indices(indices: torch.Tensor, query_labels: torch.Tensor, galle
 @torch.no_grad()
 def retrieval_recall(query_features: torch.Tensor, gallery_features: torch.Tensor, ks: Sequence[int] = (1, 5, 10),
                      query_labels: Optional[torch.Tensor] = None, gallery_labels: Optional[torch.Tensor] = None,
-                     dtype: Optional[torch.dtype] = None) -> Dict[int, float]:
+                     dtype: Optional[torch.dtype] = None, bank_features: Optional[torch.Tensor] = None,
+                     **querybank_kw) -> Dict[int, float]:
     """Recall@k of retrieving `gallery_features` rows with `query_features` rows: the share of queries whose top k holds a
     gallery item with the query's label.  Default labels pair query i with gallery row i (needs Q == N); pass labels when
     several gallery rows answer one query (the reference's data repeats `violation_list` strings).  One search at max(ks),
-    the hit test on the device, one read-back of len(ks) numbers.  Every k must be <= min(64, N)."""
+    the hit test on the device, one read-back of len(ks) numbers.  Every k must be <= min(64, N).  bank_features [B, E]: a
+    sample of typical queries; the search is then the hubness-corrected one of `EmbeddingIndex.querybank(bank_features,
+    **querybank_kw)` (method, beta, k, activation_k: clip/hubness.py)."""
     Q, N = query_features.shape[0], gallery_features.shape[0]
     if (query_labels is None) != (gallery_labels is None):
         raise ValueError("retrieval_recall: give both query_labels and gallery_labels, or neither")
@@ -331,7 +353,10 @@ def retrieval_recall(query_features: torch.Tensor, gallery_features: torch.Tenso
     if tuple(gallery_labels.shape) != (N,) or tuple(query_labels.shape) != (Q,):
         raise ValueError(f"retrieval_recall: labels must be [{Q}] and [{N}], got {tuple(query_labels.shape)} and "
                          f"{tuple(gallery_labels.shape)}")
+    if bank_features is None and querybank_kw:
+        raise ValueError(f"retrieval_recall: {sorted(querybank_kw)} need bank_features")
     index = EmbeddingIndex(gallery_features, dtype=dtype)
-    _, idx = index.search(query_features, max(ks))
+    querybank = None if bank_features is None else index.querybank(bank_features, **querybank_kw)
+    _, idx = index.search(query_features, max(ks), querybank=querybank)
     r = recall_from_indices(idx, query_labels, gallery_labels, ks).tolist()
     return {k: v for k, v in zip(ks, r)}

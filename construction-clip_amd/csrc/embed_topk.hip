@@ -17,6 +17,12 @@
 // wave-uniform branch.  A score that does goes, one at a time, into the row's sorted list in LDS (all 64 lanes shift the list
 // in one step); about k ln(N / k) such inserts per row.  The lists go to the workspace: [Q][splits][k] keys.
 // Phase 2 (topk_merge_kernel): one work-group per query runs the same insert over its splits * k keys and decodes them.
+//
+// Biased form (cclip_similarity_topk_biased): the same two phases on t[q, n] = fmaf(scale, s[q, n], bias[n]) with bias fp32 [N] -
+// the hubness corrections of clip/hubness.py, and with bias = -inf filtered search.  Phase 1 is a compile-time variant of the same
+// kernel, chosen by its argument struct; the merge is shared.  A -inf t keys below every finite one and above NaN, so an
+// excluded row can only trail, by ascending index.  scale = 1, bias = 0 is the unbiased result bit for bit.
+#include <type_traits>
 #include "score_sweep.h"
 #include "../../include/cclip_hip.h"
 
@@ -28,6 +34,9 @@ struct TopkArgs {
   int Q, N, D, k;
   int splits, rows_per_split;                     // rows_per_split is a multiple of 64
   u64* ws;
+};
+struct TopkBiasedArgs : TopkArgs {
+  const float* bias; float scale;                 // bias fp32 [N]
 };
 
 __device__ __forceinline__ u64 shfl64(u64 v, int src) {
@@ -47,8 +56,11 @@ __device__ __forceinline__ unsigned list_insert(volatile u64* L, int k, int lane
 }
 
 // <KSMAX, MT, GT> as in score_tiles.h: MT query tiles of 16 rows per wave, GT gallery rows per tile
-template <int KSMAX, int MT, int GT>
-__global__ __launch_bounds__(256) void topk_partial_kernel(const TopkArgs a) {
+// Args = TopkArgs: the kernel of cclip_similarity_topk.  Args = TopkBiasedArgs ranks t = fmaf(scale, s, bias[n]) instead of s;
+// every `if constexpr (BIASED)` below compiles to nothing in the unbiased kernel.
+template <int KSMAX, int MT, int GT, class Args>
+__global__ __launch_bounds__(256) void topk_partial_kernel(const Args a) {
+  constexpr bool BIASED = std::is_same<Args, TopkBiasedArgs>::value;
   constexpr int NST = GT / 16;                    // sub-tiles of 16 gallery rows
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -85,8 +97,21 @@ __global__ __launch_bounds__(256) void topk_partial_kernel(const TopkArgs a) {
     if (base + GT < n1) mover.fetch(a.g, a.ldg, base + GT, N - 1);
     if (!active) continue;
 
+    float bs[NST];                                // the bias of this lane's gallery row of every sub-tile, loaded under the multiply
+    if constexpr (BIASED) {
+#pragma unroll
+      for (int st = 0; st < NST; ++st) bs[st] = a.bias[min(base + 16 * st + li, N - 1)];    // clamped (never selected)
+    }
     f32x4 acc[MT][NST];
     tile_multiply<KSMAX, MT, GT>(acc, af, Gs, geo, lane);
+    if constexpr (BIASED) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int st = 0; st < NST; ++st)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[mt][st][r] = __builtin_fmaf(a.scale, acc[mt][st][r], bs[st]);
+    }
 
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
@@ -182,22 +207,46 @@ extern "C" int64_t cclip_similarity_topk_workspace(int32_t Q, int64_t N, int32_t
 }
 #endif
 
-extern "C" int CCLIP_FN(cclip_similarity_topk)(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N,
-                                                int32_t D, int32_t k, float* scores, int32_t* index, void* workspace,
-                                                int64_t workspace_bytes, hipStream_t stream) {
+// the checks the two entries share; fills a
+static int topk_args(TopkArgs& a, const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D, int32_t k,
+                     float* scores, int32_t* index, void* workspace, int64_t workspace_bytes) {
   if (!q || !g || !scores || !index || !workspace) return CCLIP_ERR_ARG;
   if (Q <= 0 || !score_rows_ok(N) || k < 1 || k > 64 || k > N) return CCLIP_ERR_ARG;
   if (!score_operands_ok(q, ldq, g, ldg, D)) return CCLIP_ERR_ARG;
   if (((uintptr_t)workspace & 7) || ((uintptr_t)scores & 3) || ((uintptr_t)index & 3)) return CCLIP_ERR_ARG;
-  TopkArgs a;
   a.q = (const bf16*)q; a.g = (const bf16*)g; a.ldq = ldq; a.ldg = ldg;
   a.Q = Q; a.N = (int)N; a.D = D; a.k = k;
   topk_splits(Q, N, &a.splits, &a.rows_per_split);
   a.ws = (u64*)workspace;
   if (workspace_bytes < (int64_t)Q * a.splits * k * 8) return CCLIP_ERR_ARG;
+  return CCLIP_OK;
+}
+
+extern "C" int CCLIP_FN(cclip_similarity_topk)(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N,
+                                                int32_t D, int32_t k, float* scores, int32_t* index, void* workspace,
+                                                int64_t workspace_bytes, hipStream_t stream) {
+  TopkArgs a;
+  if (topk_args(a, q, ldq, Q, g, ldg, N, D, k, scores, index, workspace, workspace_bytes) != CCLIP_OK) return CCLIP_ERR_ARG;
   const int st = score_dispatch<false>(D, Q > 64, [&](auto s) {
     using S = decltype(s);                        // one tile, then the four waves' lists
-    return sweep_launch(topk_partial_kernel<S::KSMAX, S::MT, S::GT>, a, Q, S::MT, S::GT, D, a.splits, 1, (size_t)4 * 16 * S::MT * k * 8, stream);
+    return sweep_launch(topk_partial_kernel<S::KSMAX, S::MT, S::GT, TopkArgs>, a, Q, S::MT, S::GT, D, a.splits, 1, (size_t)4 * 16 * S::MT * k * 8, stream);
+  });
+  if (st != CCLIP_OK) return st;
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), 0, stream, (const u64*)a.ws, a.splits, k, scores, index);
+  return cclip_launch_status();
+}
+
+extern "C" int CCLIP_FN(cclip_similarity_topk_biased)(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N,
+                                                       int32_t D, int32_t k, const float* bias, float scale, float* scores,
+                                                       int32_t* index, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  TopkBiasedArgs b;
+  if (!bias || ((uintptr_t)bias & 3)) return CCLIP_ERR_ARG;
+  if (topk_args(b, q, ldq, Q, g, ldg, N, D, k, scores, index, workspace, workspace_bytes) != CCLIP_OK) return CCLIP_ERR_ARG;
+  b.bias = bias; b.scale = scale;
+  const TopkArgs& a = b;
+  const int st = score_dispatch<false>(D, Q > 64, [&](auto s) {
+    using S = decltype(s);
+    return sweep_launch(topk_partial_kernel<S::KSMAX, S::MT, S::GT, TopkBiasedArgs>, b, Q, S::MT, S::GT, D, a.splits, 1, (size_t)4 * 16 * S::MT * k * 8, stream);
   });
   if (st != CCLIP_OK) return st;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), 0, stream, (const u64*)a.ws, a.splits, k, scores, index);

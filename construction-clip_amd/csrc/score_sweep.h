@@ -1,13 +1,13 @@
 // What the streamed-score kernels on score_tiles.h share beyond its parts.
-// Host side, used by every one of them (embed_topk, embed_range, embed_kmeans assign, embed_cache, embed_probe forward,
-// lm_score, mst nearest; embed_cache_bwd takes the checks):
+// Host side, used by every one of them (embed_topk, embed_range, embed_kmeans assign, embed_hub, embed_cache, embed_probe
+// forward, lm_score, mst nearest; embed_cache_bwd takes the checks):
 //   gallery_splits  how the streamed rows are cut into splits
 //   score_dispatch  (D, wide) -> <KSMAX, MT, GT>, with or without the 768 rung
 //   sweep_launch    grid = row blocks x splits, its 2^31 guard, LDS for the tile buffers
 //   segment_of, clamp_index, score_rows_ok   the small change of the same kernels
 // (the 16-lane group butterflies are in score_key.h.)
 // Device side, used by the two kernels that score the rows of a matrix of up to 2^31 - 1 rows against a streamed one through
-// two tile buffers, embed_kmeans' assign kernel and mst's nearest kernel:
+// two tile buffers, embed_kmeans' assign kernel, embed_hub's partial kernel and mst's nearest kernel:
 //   SweepCtx        lane coordinates, geometry, the work-group's operand rows and its split [n0, n1) of the streamed rows
 //   stream_tiles    the tile loop with its one barrier per tile and the fetch hook
 //   for_subtiles    the walk over a tile's sub-tiles of 16 streamed rows

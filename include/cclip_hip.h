@@ -313,6 +313,34 @@ int cclip_similarity_topk(const void* q, int64_t ldq, int32_t Q, const void* g, 
                           int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
                           hipStream_t stream);
 
+/* The biased form: the exact top-k of t[i, n] = fmaf(scale, s[i, n], bias[n]) with bias fp32 [N] on the device (4-byte aligned)
+ * and s the score above (same bits).  scores holds t.  Same key order on t: higher t first, equal t by the LOWER gallery
+ * index, NaN last.  bias[n] = -inf excludes row n: it appears only once the finite rows run out, and then by ascending
+ * index (before any NaN).  scale = 1 with bias = 0 returns what cclip_similarity_topk returns, bit for bit.  Same workspace
+ * (cclip_similarity_topk_workspace), same two launches (the merge kernel is shared), same refusals, plus a null or
+ * misaligned bias. */
+int cclip_similarity_topk_biased(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                                 int32_t k, const float* bias, float scale, float* scores, int32_t* index, void* workspace,
+                                 int64_t workspace_bytes, hipStream_t stream);
+
+/* ---- how strongly a bank of queries points at every stored row (csrc/embed_hub.hip) -----------------------------
+ * For the gallery g [N, D] and the bank [B, D], both bf16 (fp16 in the twin) under the operand contract of
+ * cclip_similarity_topk (row strides ldg / ldb in elements), and a float beta:
+ *   lse[j] = log sum_{b < B} exp(beta * s[b, j])      fp32 [N],   s[b, j] = sum_d bank[b, d] g[j, d]
+ * with s the bits cclip_similarity_topk returns for the pair and beta * s one fp32 multiply.  The B x N matrix is never
+ * written.  The sum runs on running (max, sum of exp(t - max)) pairs: nothing above exp(0) is formed, so a large beta stays
+ * finite.  B = 1 returns beta * s exactly.  A NaN in gallery row j makes lse[j] NaN and touches no other entry; a non-finite
+ * bank row reaches every entry.  No atomics: two launches are bitwise equal.
+ * Two launches on `stream`: per-split pairs into `workspace` ([N][splits] pairs of floats, splits =
+ * cclip_bank_lse_splits(N, B), at least cclip_bank_lse_workspace(N, B) = 8 N splits bytes, 8-byte aligned, device memory the
+ * caller owns), then the merge in ascending split order.  Both queries return 0 for sizes the call would refuse.
+ * CCLIP_ERR_ARG (nothing launched): a null pointer; N or B <= 0 or >= 2^31; D <= 0, D % 32 or D > 1024; ldg or ldb below D
+ * or not a multiple of 8; g or bank not 16-byte aligned; workspace too small or misaligned; lse not 4-byte aligned. */
+int32_t cclip_bank_lse_splits(int64_t N, int64_t B);
+int64_t cclip_bank_lse_workspace(int64_t N, int64_t B);
+int cclip_bank_lse(const void* g, int64_t ldg, int64_t N, const void* bank, int64_t ldb, int64_t B, int32_t D, float beta,
+                   float* lse, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- fixed-radius search over stored embeddings (csrc/embed_range.hip) --------------------------------------
  * For the operands of cclip_similarity_topk (same contract, same score bits per pair): every pair (i, n) with
  * s[i, n] >= threshold, in CSR form.  A NaN score is never a hit, +inf is one; threshold = -inf returns every non-NaN pair.
@@ -1145,6 +1173,11 @@ int cclip_cast_f32_to_f16(const float* in, void* out, int64_t n, hipStream_t str
 int cclip_similarity_topk_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
                               int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,
                               hipStream_t stream);
+int cclip_similarity_topk_biased_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
+                                     int32_t k, const float* bias, float scale, float* scores, int32_t* index, void* workspace,
+                                     int64_t workspace_bytes, hipStream_t stream);
+int cclip_bank_lse_f16(const void* g, int64_t ldg, int64_t N, const void* bank, int64_t ldb, int64_t B, int32_t D, float beta,
+                       float* lse, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 int cclip_similarity_range_count_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
                                      float threshold, int32_t self_join, int32_t* counts, int64_t workspace_bytes,
                                      hipStream_t stream);
