@@ -2424,6 +2424,83 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, *, lr: float, beta1=0.9, beta2=
                                c_float(grad_scale), c_int(mode), _p(bf16_shadow), _stream()), "cclip_adamw_step")
 
 
+def adamw_grid(n: int) -> int:
+    """blocks of the adamw_step / adamw_step_groups launch over n elements (0 for an n they refuse)"""
+    return _query("cclip_adamw_grid", c_int, c_long(n))
+
+
+def sumsq_workspace(n: int) -> int:
+    """bytes of scratch `sumsq` needs for n elements: 4 per first-stage block (0 for an n it refuses)"""
+    return _query("cclip_sumsq_workspace", c_long, c_long(n))
+
+
+def sumsq(x, *, out=None, accumulate: bool = False, nonfinite_count=None, workspace=None):
+    """out (+)= sum of x[i]^2 over a flat fp32 device range (include/cclip_hip.h, cclip_sumsq_f32): two launches, no atomics,
+    equal bits from equal data.  out: fp32 [1] on x's device (allocated when None; read first when `accumulate`);
+    nonfinite_count: int32 [1], raised by one when out ends up inf or NaN; workspace: fp32, at least sumsq_workspace(n) bytes.
+    Returns out.  Nothing is read on the host."""
+    f = "sumsq"
+    _dev_tensor(f, x, "x", torch.float32, 1, None)
+    dev, n = x.device, x.numel()
+    if accumulate and out is None:
+        raise ValueError(f"{f}: accumulate needs the `out` to add to")
+    out = _out(f, out, "out", torch.float32, (1,), dev)
+    _dev_tensor(f, nonfinite_count, "nonfinite_count", torch.int32, (1,), dev, optional=True)
+    if n <= 0 or n % 4:
+        raise ValueError(f"{f}: x must hold a positive multiple of 4 elements, got {n}")
+    if x.data_ptr() % 16:
+        raise ValueError(f"{f}: x must be 16-byte aligned (address % 16 = {x.data_ptr() % 16})")
+    ws = _workspace(f, workspace, sumsq_workspace(n), torch.float32, dev, flat=True)
+    check(lib.cclip_sumsq_f32(_p(x), c_long(n), _p(ws), _p(out), c_int(int(accumulate)), _p(nonfinite_count), _stream()),
+          "cclip_sumsq_f32")
+    return out
+
+
+def adamw_step_groups(param, grad, exp_avg, exp_avg_sq, chunk_group, *, lrs, weight_decays, beta1=0.9, beta2=0.999, eps=1e-6,
+                      step: int = 1, correct_bias: bool = True, grad_scale: float = 1.0, mode: int = 0, bf16_shadow=None,
+                      sumsq_dev=None, max_norm=None, skip_nonfinite: bool = False, ema=None, ema_decay: float = 0.0) -> None:
+    """adamw_step with parameter groups, norm clipping from a device scalar and EMA weights, in one launch
+    (include/cclip_hip.h, cclip_adamw_step_groups).  param / grad / exp_avg / exp_avg_sq (/ ema): flat fp32 of n elements,
+    n % 4 == 0, 16-byte aligned; chunk_group: uint8 [ceil(n / 64)] on the same device, the group of every 64-element chunk of
+    THIS range (a slice of the arena's table); lrs / weight_decays: host sequences, one entry per group (at most 256) - a table
+    entry beyond them is the caller's to avoid and is not checked here (it would need a read-back).  sumsq_dev: fp32 [1], the sum
+    of squares of the unscaled gradients (`sumsq`), with max_norm finite and > 0; skip_nonfinite: a non-finite scalar makes the
+    launch write nothing.  bf16_shadow: the 16-bit copy of param (either operand dtype), rewritten in the same pass."""
+    f = "adamw_step_groups"
+    _dev_tensor(f, param, "param", torch.float32, 1, None)
+    dev, n = param.device, param.numel()
+    _dev_tensors(f, dev, ((grad, "grad", torch.float32, (n,), False), (exp_avg, "exp_avg", torch.float32, (n,), False),
+                          (exp_avg_sq, "exp_avg_sq", torch.float32, (n,), False),
+                          (chunk_group, "chunk_group", torch.uint8, ((n + 63) // 64,), False),
+                          (bf16_shadow, "bf16_shadow", HALF_TYPES, (n,), True), (sumsq_dev, "sumsq_dev", torch.float32, (1,), True),
+                          (ema, "ema", torch.float32, (n,), True)))
+    lrs, wds = [float(x) for x in lrs], [float(x) for x in weight_decays]
+    if not 1 <= len(lrs) <= 256 or len(wds) != len(lrs):
+        raise ValueError(f"{f}: lrs and weight_decays must have one entry per group, 1 to 256 groups, got {len(lrs)} and {len(wds)}")
+    if n <= 0 or n % 4:
+        raise ValueError(f"{f}: param must hold a positive multiple of 4 elements, got {n}")
+    if step < 1:
+        raise ValueError(f"{f}: step must be >= 1, got {step}")
+    if sumsq_dev is not None:
+        if max_norm is None or not 0.0 < _finite(f, "max_norm", max_norm) <= 3.4028234e38:
+            raise ValueError(f"{f}: max_norm must be finite and > 0 when sumsq_dev is given, got {max_norm}")
+    elif max_norm is not None or skip_nonfinite:
+        raise ValueError(f"{f}: max_norm and skip_nonfinite need the device scalar `sumsq_dev`")
+    if ema is not None and not 0.0 <= float(ema_decay) <= 1.0:
+        raise ValueError(f"{f}: ema_decay must lie in [0, 1], got {ema_decay}")
+    for t, nm in ((param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (ema, "ema")):
+        if t is not None and t.data_ptr() % 16:
+            raise ValueError(f"{f}: {nm} must be 16-byte aligned (address % 16 = {t.data_ptr() % 16})")
+    if bf16_shadow is not None and bf16_shadow.data_ptr() % 8:
+        raise ValueError(f"{f}: bf16_shadow must be 8-byte aligned (address % 8 = {bf16_shadow.data_ptr() % 8})")
+    G = len(lrs)
+    check(_fn("cclip_adamw_step_groups", bf16_shadow)(
+        _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), c_long(n), _p(chunk_group), (c_float * G)(*lrs), (c_float * G)(*wds),
+        c_int(G), c_float(beta1), c_float(beta2), c_float(eps), c_int(step), c_int(int(correct_bias)), c_float(grad_scale),
+        c_int(mode), _p(bf16_shadow), _p(sumsq_dev), c_float(0.0 if max_norm is None else max_norm), c_int(int(skip_nonfinite)),
+        _p(ema), c_float(ema_decay), _stream()), "cclip_adamw_step_groups")
+
+
 def transpose16_batched(src_base: torch.Tensor, dst_base: torch.Tensor, table_dev: torch.Tensor, max_tiles: int) -> None:
     """table_dev: int64 [n, 4] on the device = (src element offset, dst element offset, rows, cols) per matrix"""
     assert src_base.dtype in HALF_TYPES and dst_base.dtype == src_base.dtype and table_dev.dtype == torch.int64 and table_dev.is_cuda

@@ -897,6 +897,42 @@ int cclip_adamw_step(float* param, const float* grad, float* exp_avg, float* exp
                      float beta1, float beta2, float eps, float weight_decay, int32_t step,
                      int32_t correct_bias, float grad_scale, int32_t mode, void* bf16_shadow,
                      hipStream_t stream);
+/* cclip_adamw_step with parameter groups, a clip coefficient from a device scalar and an EMA of the new masters, one launch.
+ *   groups: chunk_group[c] (uint8, device) names the group of elements [64 c, 64 c + 64) of THIS range (the pointer is already
+ *     offset to the range's first chunk; ceil(n / 64) entries are read); lr[] / weight_decay[] are HOST arrays of n_groups
+ *     entries, copied into a by-value kernel argument at every call (no device copy, no synchronisation).  A table entry
+ *     >= n_groups is the CALLER's to avoid: the kernel does not check it; it can reach no memory outside the argument (the
+ *     argument has 256 entries, the table is uint8) and takes lr = weight_decay = 0 - the moments move, the parameter stays.
+ *   scalar: with sumsq_dev != NULL the gradient is multiplied by
+ *       grad_scale * min(1, max_norm / (|grad_scale| * sqrt(*sumsq_dev) + 1e-6))
+ *     instead of grad_scale: torch.nn.utils.clip_grad_norm_'s coefficient for gradients grad_scale * grad whose sum of squares
+ *     BEFORE the scaling is *sumsq_dev (cclip_sumsq_f32).  With skip_nonfinite != 0 and *sumsq_dev inf or NaN the launch writes
+ *     nothing at all (p, m, v, ema and shadow keep their bits); with skip_nonfinite == 0 the step is applied with whatever
+ *     coefficient results (0 for inf, 1 for NaN).
+ *   ema != NULL: ema = ema_decay * ema + (1 - ema_decay) * p_new per element (fp32, 16-byte aligned, 0 <= ema_decay <= 1).
+ *   The shadow is written as by cclip_adamw_step.  One group, sumsq_dev == NULL and ema == NULL give cclip_adamw_step's bits.
+ *   CCLIP_ERR_ARG (nothing launched): what cclip_adamw_step refuses; null chunk_group / lr / weight_decay; n_groups outside
+ *   [1, 256]; sumsq_dev with a max_norm that is not finite and > 0; ema misaligned or ema_decay outside [0, 1]. */
+int cclip_adamw_step_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                            const uint8_t* chunk_group, const float* lr, const float* weight_decay, int32_t n_groups,
+                            float beta1, float beta2, float eps, int32_t step, int32_t correct_bias, float grad_scale,
+                            int32_t mode, void* bf16_shadow, const float* sumsq_dev, float max_norm, int32_t skip_nonfinite,
+                            float* ema, float ema_decay, hipStream_t stream);
+/* blocks of the cclip_adamw_step / cclip_adamw_step_groups launch over n elements (256 threads, two float4 groups a grid
+ * stride apart per trip: a thread takes a second trip when n / 4 > 2 * 256 * blocks); 0 for an n the calls refuse */
+int32_t cclip_adamw_grid(int64_t n);
+/* out (+)= sum_i x[i]^2 over n fp32 elements (n % 4 == 0, x 16-byte aligned), fp32 only, two launches, no float atomics:
+ * stage 1 runs B = cclip_sumsq_workspace(n) / 4 = min(ceil(n / 1024), 1024) blocks of 256 threads; thread t of block b folds
+ * the float4 groups b * 256 + t, + 256 B, ... element by element into one fma chain, the block adds its chains by a 6-level
+ * butterfly and its 4 wave sums in order, and writes partials[b]; stage 2 (one block) starts from *out when accumulate != 0,
+ * else from 0, and adds partials[0 .. B) in ascending order.  Two calls on the same data give equal bits.  A NaN or an inf in
+ * x (or a square that overflows) makes *out non-finite; when *out is non-finite after the fold and nonfinite_count != NULL,
+ * one thread adds 1 to that int32 with a plain load and store.  partials: at least cclip_sumsq_workspace(n) bytes of device
+ * memory (0 for an n the call refuses), 4-byte aligned, contents undefined afterwards.
+ * CCLIP_ERR_ARG (nothing launched): null x, partials or out; n <= 0 or n % 4 != 0; x not 16-byte aligned. */
+int cclip_sumsq_f32(const float* x, int64_t n, float* partials, float* out, int32_t accumulate, int32_t* nonfinite_count,
+                    hipStream_t stream);
+int64_t cclip_sumsq_workspace(int64_t n);
 int cclip_cast_f32_to_bf16(const float* in, void* out, int64_t n, hipStream_t stream);
 /* Batched out-of-place transpose of 16-bit matrices (bf16 or fp16: elements are moved, not interpreted): for i < n_matrices,
  * dst_base[table[i].dst_off ...] as [cols, rows] = transpose of src_base[table[i].src_off ...] as [rows, cols];
@@ -1169,6 +1205,11 @@ int cclip_adamw_step_f16(float* param, const float* grad, float* exp_avg, float*
                          float beta1, float beta2, float eps, float weight_decay, int32_t step,
                          int32_t correct_bias, float grad_scale, int32_t mode, void* f16_shadow,
                          hipStream_t stream);
+int cclip_adamw_step_groups_f16(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                const uint8_t* chunk_group, const float* lr, const float* weight_decay, int32_t n_groups,
+                                float beta1, float beta2, float eps, int32_t step, int32_t correct_bias, float grad_scale,
+                                int32_t mode, void* f16_shadow, const float* sumsq_dev, float max_norm, int32_t skip_nonfinite,
+                                float* ema, float ema_decay, hipStream_t stream);
 int cclip_cast_f32_to_f16(const float* in, void* out, int64_t n, hipStream_t stream);
 int cclip_similarity_topk_f16(const void* q, int64_t ldq, int32_t Q, const void* g, int64_t ldg, int64_t N, int32_t D,
                               int32_t k, float* scores, int32_t* index, void* workspace, int64_t workspace_bytes,

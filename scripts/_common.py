@@ -82,3 +82,65 @@ def make_synthetic_annotations(out_dir: str, per_class: int = 12, size: int = 96
 
 def log_line(**kw) -> None:
     print(json.dumps(kw), flush=True)
+
+
+# ---- the fine-tuning options of the two training scripts (clip.optim.AdamW's groups, clipping, EMA; WiSE-FT) ----
+def add_optim_args(ap) -> None:
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="decoupled weight decay; biases, LayerNorms, logit_scale and the "
+                    "learned positional / class embeddings are left out of it (see --decay-all)")
+    ap.add_argument("--decay-all", action="store_true", help="one parameter group: --weight-decay on every parameter")
+    ap.add_argument("--layer-decay", type=float, default=None, help="layer-wise learning-rate decay: lr * this ** (depth from the top)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, help="clip the total gradient norm to this")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="skip a step whose gradient norm is inf or NaN")
+    ap.add_argument("--ema-decay", type=float, default=None, help="keep an EMA of the weights (with warm-up) and save it next to every "
+                    "checkpoint as <checkpoint>_ema.pt")
+    ap.add_argument("--wise-ft", type=float, default=None, metavar="ALPHA", help="at the end write (1 - ALPHA) * final + ALPHA * initial "
+                    "weights as <last checkpoint>_wise.pt")
+
+
+def make_optimizer(model, args):
+    """clip.optim.AdamW for the options of add_optim_args; without any of them it is AdamW(model, lr), today's path"""
+    from clip import optim as coptim
+    kw = {}
+    if args.layer_decay is not None:
+        kw["param_groups"] = coptim.layer_decay_groups(model, args.layer_decay, 0.0 if args.decay_all else args.weight_decay)
+        if args.decay_all:
+            kw["weight_decay"] = args.weight_decay
+            for g in kw["param_groups"]:
+                del g["weight_decay"]
+    elif args.weight_decay > 0 and not args.decay_all:
+        kw["param_groups"] = coptim.no_decay_groups(model, args.weight_decay)
+    elif args.weight_decay > 0:
+        kw["weight_decay"] = args.weight_decay
+    if args.clip_grad_norm is not None:
+        kw["max_grad_norm"] = args.clip_grad_norm
+    if args.skip_nonfinite:
+        kw["skip_nonfinite"] = True
+    if args.ema_decay is not None:
+        kw.update(ema_decay=args.ema_decay, ema_warmup=True)
+    return coptim.AdamW(model, lr=args.lr, **kw)
+
+
+def optim_log(opt) -> dict:
+    """the gradient norm and the skipped steps for a log line (one read-back each, where the optimiser keeps them)"""
+    out = {}
+    if opt.last_grad_norm is not None:
+        out["grad_norm"] = round(float(opt.last_grad_norm), 6)
+    if opt.skipped_steps is not None and opt.skip_nonfinite:
+        out["skipped_steps"] = int(opt.skipped_steps)
+    return out
+
+
+def save_side_weights(opt, model, path: str, initial=None, alpha=None) -> None:
+    """<path>_ema.pt for an optimiser that keeps an EMA; with `initial` and alpha, <path>_wise.pt: the WiSE-FT interpolation,
+    written without disturbing the model (its masters are put back)"""
+    from clip import optim as coptim
+    if opt.ema_decay is not None and opt._ema is not None:
+        torch.save({k: v.cpu() for k, v in opt.ema_state_dict().items()}, path[:-3] + "_ema.pt")
+        log_line(saved=path[:-3] + "_ema.pt")
+    if initial is not None and alpha is not None:
+        final = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        coptim.interpolate_weights(model, initial, alpha)
+        torch.save({k: v.cpu() for k, v in model.state_dict().items()}, path[:-3] + "_wise.pt")
+        coptim.interpolate_weights(model, final, 1.0)
+        log_line(saved=path[:-3] + "_wise.pt", wise_ft_alpha=alpha)

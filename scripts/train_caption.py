@@ -59,6 +59,7 @@ def main(argv=None):
     ap.add_argument("--val-seed", type=int, default=567)
     ap.add_argument("--dedup-threshold", type=float, default=None, help="with --val-fraction: keep near-duplicate embeddings "
                     "(cosine >= this, single linkage) on one side of the split; default off")
+    C.add_optim_args(ap)
     args = ap.parse_args(argv)
 
     from clip import optim as coptim
@@ -112,7 +113,8 @@ def main(argv=None):
     model = model.to(device)
     model.train()
     os.makedirs(args.out_dir, exist_ok=True)
-    opt = coptim.AdamW(model, lr=args.lr)                                                  # train.py:336
+    opt = C.make_optimizer(model, args)                                                    # train.py:336 (+ groups, clipping, EMA)
+    initial = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if args.wise_ft is not None else None
     loader = DataLoader(dataset, batch_size=args.bs, shuffle=True, drop_last=True)        # train.py:337
     sched = coptim.get_linear_schedule_with_warmup(opt, args.warmup_steps, args.epochs * len(loader))   # train.py:338-340
     step = 0
@@ -131,7 +133,7 @@ def main(argv=None):
             opt.step()
             sched.step()
             step += 1
-            C.log_line(epoch=epoch, step=step, loss=round(float(loss.detach()), 6))
+            C.log_line(epoch=epoch, step=step, loss=round(float(loss.detach()), 6), **C.optim_log(opt))
             if args.max_steps and step >= args.max_steps:
                 break
         if val_set is not None:                                                           # held-out loss: no logits, no gradient touched
@@ -142,6 +144,8 @@ def main(argv=None):
             path = os.path.join(args.out_dir, f"{args.prefix}-{epoch:03d}.pt")
             torch.save(model.state_dict(), path)
             C.log_line(saved=path)
+            last = epoch == args.epochs - 1 or bool(args.max_steps and step >= args.max_steps)
+            C.save_side_weights(opt, model, path, initial if last else None, args.wise_ft)
         if args.max_steps and step >= args.max_steps:
             break
     if tmp is not None:

@@ -70,6 +70,7 @@ def build_args():
     ap.add_argument("--distill-weight", type=float, default=1.0, help="total = hard + this * distill")
     ap.add_argument("--synthetic", action="store_true", help="generated images + labels, seeded weights, byte tokenizer")
     ap.add_argument("--seed", type=int, default=567)
+    C.add_optim_args(ap)
     return ap
 
 
@@ -140,7 +141,8 @@ def main(argv=None):
     train_dl = DataLoader(train_ds, batch_size=args.batch_size, shuffle=True, num_workers=args.workers)
     test_dl = DataLoader(test_ds, batch_size=args.batch_size, shuffle=False, num_workers=args.workers)
     model.train()
-    opt = coptim.AdamW(model, lr=args.lr)                                                   # train.py:143
+    opt = C.make_optimizer(model, args)                                                     # train.py:143 (+ groups, clipping, EMA)
+    initial = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if args.wise_ft is not None else None
     sched = coptim.get_linear_schedule_with_warmup(opt, args.warmup_steps, args.epochs * len(train_dl))   # train.py:145-147
     ce = torch.nn.CrossEntropyLoss()
     sig = bias_opt = bias_sched = None
@@ -198,7 +200,7 @@ def main(argv=None):
                 extra.update(logit_bias=round(float(sig.logit_bias.detach()), 6))
             step += 1
             C.log_line(epoch=epoch, step=step, loss=round(float(loss.detach()), 6), accuracy=round(acc, 4), lr=sched.get_last_lr()[0],
-                       **extra)
+                       **C.optim_log(opt), **extra)
             if args.max_steps and step >= args.max_steps:
                 break
         test_acc = evaluate(model, test_dl, device)
@@ -211,6 +213,8 @@ def main(argv=None):
                 side = path[:-3] + "_logit_bias.pt"
                 torch.save(sig.logit_bias.detach().cpu(), side)
                 C.log_line(saved=side)
+            last = args.epochs == epoch or bool(args.max_steps and step >= args.max_steps)
+            C.save_side_weights(opt, model, path, initial if last else None, args.wise_ft)
         if args.max_steps and step >= args.max_steps:
             break
     if tmp is not None:
