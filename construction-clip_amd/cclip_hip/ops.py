@@ -1903,6 +1903,104 @@ def relevance_overlay(rel: torch.Tensor, images: torch.Tensor, lut: torch.Tensor
                                       _p(map_out), _stream()), "cclip_relevance_overlay")
 
 
+DENSE_MAX_CLASSES, DENSE_MAX_EMBED = 255, 1024
+
+
+def _dense_operands(fname: str, tensors, ref: torch.Tensor, strided=()) -> None:
+    """The operand contract of the dense-map wrappers: cuda tensor, dtype, contiguous (row-strided for the names in `strided`),
+    on `ref`'s device - each refusal a ValueError that names the operand."""
+    for t, name, dt in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{fname}: {name} must be a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != dt:
+            raise ValueError(f"{fname}: {name} must be {dt}, got {t.dtype}")
+        if name in strided:
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{fname}: {name} must be 2-D with inner stride 1, got shape {tuple(t.shape)} strides {t.stride()}")
+        elif not t.is_contiguous():
+            raise ValueError(f"{fname}: {name} must be contiguous, got shape {tuple(t.shape)} strides {t.stride()}")
+        if t.device != ref.device:
+            raise ValueError(f"{fname}: {name} is on {t.device}, {tensors[0][1]} on {ref.device}")
+
+
+def dense_class_probs(feat: torch.Tensor, text: torch.Tensor, scale: float, patches: int, probs: torch.Tensor,
+                      logits_out: Optional[torch.Tensor] = None) -> None:
+    """Per-patch class probabilities (include/cclip_hip.h, cclip_dense_class_probs): feat fp32 [B * patches, E] (rows may be
+    strided), text fp32 [C, E], neither normalised -> probs fp32 [B, C, patches] = softmax over C of scale * cosine, class-major,
+    and, when given, logits_out of the same shape.  1 <= C <= 255, E a multiple of 4, <= 1024.  cuda tensors on one device; no
+    CPU path.  Two calls give equal bytes."""
+    fname = "dense_class_probs"
+    tensors = [(feat, "feat", torch.float32), (text, "text", torch.float32), (probs, "probs", torch.float32)]
+    if logits_out is not None:
+        tensors.append((logits_out, "logits_out", torch.float32))
+    _dense_operands(fname, tensors, feat, strided=("feat",))
+    if text.dim() != 2 or text.shape[1] != feat.shape[1]:
+        raise ValueError(f"{fname}: text must be [C, {feat.shape[1]}], got {tuple(text.shape)}")
+    M, E = feat.shape
+    C = text.shape[0]
+    if not 1 <= C <= DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: {C} classes; text must hold between 1 and {DENSE_MAX_CLASSES} rows")
+    if E < 4 or E % 4 or E > DENSE_MAX_EMBED:
+        raise ValueError(f"{fname}: feat has embedding width {E}; it must be a multiple of 4 in [4, {DENSE_MAX_EMBED}]")
+    if int(patches) != patches or patches < 1 or M < 1 or M % patches:
+        raise ValueError(f"{fname}: feat has {M} rows, not a positive multiple of patches = {patches}")
+    patches = int(patches)
+    if M > 1 and (feat.stride(0) < E or feat.stride(0) % 4):
+        raise ValueError(f"{fname}: feat must have a row stride >= {E} that is a multiple of 4, got {feat.stride(0)}")
+    if feat.data_ptr() % 16 or text.data_ptr() % 16:
+        raise ValueError(f"{fname}: feat and text must start on a 16-byte boundary")
+    B = M // patches
+    if tuple(probs.shape) != (B, C, patches):
+        raise ValueError(f"{fname}: probs must be [{B}, {C}, {patches}], got {tuple(probs.shape)}")
+    if logits_out is not None and tuple(logits_out.shape) != (B, C, patches):
+        raise ValueError(f"{fname}: logits_out must be [{B}, {C}, {patches}], got {tuple(logits_out.shape)}")
+    ldf = feat.stride(0) if M > 1 else E
+    check(lib.cclip_dense_class_probs(_p(feat), c_long(ldf), c_long(M), c_int(patches), _p(text), c_int(C), c_int(E),
+                                      c_float(float(scale)), _p(probs), _p(logits_out), _stream()), "cclip_dense_class_probs")
+
+
+def dense_label_map(probs: torch.Tensor, size: int, labels: torch.Tensor, conf: torch.Tensor, *, min_conf: float = 0.0,
+                    overlay: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None,
+                    photo: Optional[torch.Tensor] = None, alpha8: int = 256) -> None:
+    """Label map and picture of per-patch probabilities (include/cclip_hip.h, cclip_dense_label_map): probs fp32 [B, C, g, g] ->
+    labels uint8 [B, size, size] (the lowest arg-max class of the bilinearly upsampled maps, 255 below min_conf), conf fp32
+    [B, size, size], and with overlay uint8 [B, size, size, 3]: palette uint8 [256, 3] at the label, blended in integers over
+    photo uint8 [B, size, size, 3] with weight alpha8 / 256 when a photo is given.  Contiguous cuda tensors on one device; no CPU
+    path.  Two calls give equal bytes."""
+    fname = "dense_label_map"
+    tensors = [(probs, "probs", torch.float32), (labels, "labels", torch.uint8), (conf, "conf", torch.float32)]
+    for t, name in ((overlay, "overlay"), (palette, "palette"), (photo, "photo")):
+        if t is not None:
+            tensors.append((t, name, torch.uint8))
+    _dense_operands(fname, tensors, probs)
+    if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
+        raise ValueError(f"{fname}: probs must be [B, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
+    B, C, g, _ = probs.shape
+    if C > DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: probs holds {C} classes; at most {DENSE_MAX_CLASSES} (label 255 means none)")
+    if int(size) != size or not 1 <= size <= OVERLAY_MAX_SIDE or g > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: size {size}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    size = int(size)
+    if tuple(labels.shape) != (B, size, size):
+        raise ValueError(f"{fname}: labels must be [{B}, {size}, {size}], got {tuple(labels.shape)}")
+    if tuple(conf.shape) != (B, size, size):
+        raise ValueError(f"{fname}: conf must be [{B}, {size}, {size}], got {tuple(conf.shape)}")
+    if overlay is None and (photo is not None or palette is not None):
+        raise ValueError(f"{fname}: palette and photo are inputs of the overlay; give overlay too")
+    if overlay is not None:
+        if palette is None or tuple(palette.shape) != (256, 3):
+            raise ValueError(f"{fname}: palette must be uint8 [256, 3], got {None if palette is None else tuple(palette.shape)}")
+        if tuple(overlay.shape) != (B, size, size, 3):
+            raise ValueError(f"{fname}: overlay must be [{B}, {size}, {size}, 3], got {tuple(overlay.shape)}")
+        if photo is not None and tuple(photo.shape) != (B, size, size, 3):
+            raise ValueError(f"{fname}: photo must be [{B}, {size}, {size}, 3] (already at the output size), got {tuple(photo.shape)}")
+    if int(alpha8) != alpha8 or not 0 <= alpha8 <= 256:
+        raise ValueError(f"{fname}: alpha8 must be an integer in [0, 256], got {alpha8}")
+    check(lib.cclip_dense_label_map(_p(probs), c_int(B), c_int(C), c_int(g), c_int(size), c_float(float(min_conf)), _p(labels),
+                                    _p(conf), _p(palette), _p(photo), c_int(int(alpha8)), _p(overlay), _stream()),
+          "cclip_dense_label_map")
+
+
 # --------------------------------------------------------------------------------------------
 # fp8 (e4m3) inference projections
 # --------------------------------------------------------------------------------------------

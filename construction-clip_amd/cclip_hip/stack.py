@@ -170,14 +170,16 @@ class BlockStack:
     def forward(self, x: torch.Tensor, B: int, *, saved: Optional[dict] = None,
                 key_keep: Optional[torch.Tensor] = None, T: Optional[int] = None, kv_out=None,
                 cu: Optional[torch.Tensor] = None, tail_rows: Optional[torch.Tensor] = None,
-                weights_version=None, attn_probe=None) -> torch.Tensor:
+                weights_version=None, attn_probe=None, layers: Optional[int] = None) -> torch.Tensor:
         """x: fp32 [B*T, D] residual stream entering block 0; returns the stream leaving the last block.
         saved=None (inference) keeps nothing and updates x in place; otherwise x must be saved["xs"][0,0].
         kv_out = (kcache, vcache), each [L, B, Smax, D] 16-bit: every layer's keys / values of positions [0, T) are
         kept there (prefill of the KV-cached decode, see decode_step).
         attn_probe(l, q, k, key_keep): called once per layer while that layer's packed q / k rows ([M, D] views of the qkv
         buffer, which the next layer overwrites) are live - the tap ops.attention_probs reads (output_attentions).  It only
-        reads: the launches of the pass itself are the same with and without it."""
+        reads: the launches of the pass itself are the same with and without it.
+        layers (inference only): run blocks 0 .. layers-1 and return the stream that enters block `layers` (dense_tail takes it
+        from there); None = all blocks, the launch sequence of a call without the argument."""
         geo = self.geo
         D, H = geo.width, geo.heads
         Hd = geo.hidden or 4 * D
@@ -192,6 +194,7 @@ class BlockStack:
         assert cu is None or (geo.head_dim == 64 and T <= 128 and kv_out is None)
         assert attn_probe is None or (cu is None and geo.head_dim == 64)
         L = len(self.blocks)
+        assert layers is None or (saved is None and tail_rows is None and 0 <= layers <= L), "forward(layers=): inference, whole rows"
         dev = x.device
         kc = geo.linear_layout
         train = saved is not None
@@ -223,7 +226,7 @@ class BlockStack:
             partials, stats = part[:nblk * M * 2].view(nblk, M, 2), part[nblk * M * 2:].view(M, 2)
             xb = torch.empty(M, D, device=dev, dtype=self.dtype)   # 16-bit copy of the current stream rows (same row stride as the fp32 stream: one ldc per GEMM)
         have_stats = False                                     # stats / xb describe the CURRENT x_in (ln_1's input)?
-        for l, w in enumerate(self.blocks):
+        for l, w in enumerate(self.blocks if layers is None else self.blocks[:layers]):
             duet.interleave_point()                            # (two towers launching side by side take turns block by block)
             if train:
                 row = bf[l]
@@ -323,6 +326,51 @@ class BlockStack:
                 ops.gemm_bf16(g, w.w_proj, b_kcontig=kc, bias=w.b_proj, residual=x_mid, out_f32=x_out, M=M)
             x = x_out
         return x
+
+    # ------------------------------------------------------------------ dense tail
+    DENSE_MODES = ("value", "qq", "kk")
+
+    def dense_tail(self, x: torch.Tensor, B: int, mode: str = "value", T: Optional[int] = None) -> torch.Tensor:
+        """The LAST block as training-free dense CLIP runs it (inference only): x fp32 [B*T, D] is the stream entering it
+        (forward(..., layers=L-1)); returns fp32 [B*T, D], every row's own feature instead of a stream in which only the class
+        row was trained to mean something.  With xn = ln_1(x) and v = xn W_v^T + b_v (rows 2D:3D of w_qkv):
+          "value"  a = v                                       MaskCLIP (Zhou et al. 2022): no query / key path at all
+          "qq"     a = softmax(q q^T / sqrt(64)) v per head    self-self attention (SCLIP / ClearCLIP style)
+          "kk"     a = softmax(k k^T / sqrt(64)) v
+        and the result is a W_o^T + b_o: no residual, no MLP.  Existing launchers only; nothing is saved, x is not written."""
+        geo = self.geo
+        if mode not in self.DENSE_MODES:
+            raise ValueError(f"dense_tail: mode must be one of {self.DENSE_MODES}, got {mode!r}")
+        if geo.head_dim != 64 or not geo.linear_layout:
+            raise RuntimeError("dense_tail: needs 64-wide heads and nn.Linear weight layout "
+                               f"(head_dim {geo.head_dim}, linear_layout {geo.linear_layout})")
+        if self.fp8:
+            raise RuntimeError("dense_tail: the dense path has no fp8 projections; call fp8_projections(False) first")
+        D, H = geo.width, geo.heads
+        T = T or geo.tokens
+        M = B * T
+        assert x.shape == (M, D) and x.dtype == torch.float32
+        w = self.blocks[-1]
+        dev = x.device
+        attn = mode != "value"
+        bf = torch.empty(M, (4 if attn else 2) * D, device=dev, dtype=self.dtype)         # xn | v | q or k | a
+        xn, v = bf[:, 0:D], bf[:, D:2 * D]
+
+        def rows(r0):                                                                     # a row slice of the packed in_proj
+            return w.w_qkv[r0:r0 + D], (w.b_qkv[r0:r0 + D] if w.b_qkv is not None else None)
+
+        ops.layernorm_fwd(x, w.ln1_w, w.ln1_b, rows=M, out_bf16=xn)
+        wv, bv = rows(2 * D)
+        ops.gemm_bf16(xn, wv, b_kcontig=True, bias=bv, out_bf16=v, M=M)
+        a = v
+        if attn:
+            s, a = bf[:, 2 * D:3 * D], bf[:, 3 * D:4 * D]
+            ws, bs = rows(0 if mode == "qq" else D)
+            ops.gemm_bf16(xn, ws, b_kcontig=True, bias=bs, out_bf16=s, M=M)
+            ops.attention_fwd(s, s, v, a, B=B, T=T, H=H, causal=False)
+        out = torch.empty(M, D, device=dev, dtype=torch.float32)
+        ops.gemm_bf16(a, w.w_o, b_kcontig=True, bias=w.b_o, out_f32=out, M=M)
+        return out
 
     # ------------------------------------------------------------------ KV-cached decode
     def decode_step(self, x: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, pos: int) -> torch.Tensor:

@@ -23,4 +23,5 @@ from .fewshot import CacheClassifier, confusion_matrix  # noqa: F401  (few-shot 
 from .probe import LinearProbe, ProbeLossFunction, ProbeFitResult  # noqa: F401  (linear probe: logistic regression on the stored embeddings)
 from .gaussian import GaussianClassifier, ClassMoments, MahalanobisScores, PCAResult, class_moments, pca  # noqa: F401  (Gaussian class models: training-free classifier, outlier scores, PCA)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)
+from .dense import segment, dense_features, DenseResult, default_palette  # noqa: F401  (dense zero-shot maps: per-patch class probabilities, label maps)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

@@ -253,6 +253,26 @@ class CLIP(nn.Module):
         return self
 
     # -- image tower ----------------------------------------------------------------------------
+    def _patch_rows(self, image: torch.Tensor):
+        """im2col and conv1 as one GEMM: (patches 16-bit [B*T, KPAD], patch_out fp32 [B*T, D]) - the rows vit_embed_ln takes."""
+        ar, geo = self._arena, self.geo
+        dev = image.device
+        T, D, P = geo.vision_tokens, geo.vision_width, geo.vision_patch_size
+        M = image.shape[0] * T
+        img = image.detach().to(torch.float32).contiguous()
+        KP = 3 * P * P
+        KPAD = (KP + 7) // 8 * 8                   # P = 14: 588 -> 592, rows stay 16-byte aligned for the GEMM's DMA
+        patches = torch.empty(M, KPAD, device=dev, dtype=self.compute_dtype)
+        ops.patchify(img, patches, P)
+        w16 = ar.b["visual.conv1.weight"].view(D, KP)
+        if KPAD != KP:
+            wp = torch.zeros(D, KPAD, device=dev, dtype=self.compute_dtype)
+            wp[:, :KP].copy_(w16)
+            w16 = wp
+        patch_out = torch.empty(M, D, device=dev, dtype=torch.float32)
+        ops.gemm_bf16(patches, w16, out_f32=patch_out)
+        return patches, patch_out
+
     def _image_forward(self, image: torch.Tensor, train: bool):
         self._ensure_runtime()
         ar, geo, st = self._arena, self.geo, self._rt["vis"]
@@ -266,18 +286,7 @@ class CLIP(nn.Module):
                 raise RuntimeError("encode_image: empty batch in a training step")
             return torch.empty(0, geo.embed_dim, device=dev, dtype=torch.float32), None
         M = B * T
-        img = image.detach().to(torch.float32).contiguous()
-        KP = 3 * P * P
-        KPAD = (KP + 7) // 8 * 8                   # P = 14: 588 -> 592, rows stay 16-byte aligned for the GEMM's DMA
-        patches = torch.empty(M, KPAD, device=dev, dtype=self.compute_dtype)
-        ops.patchify(img, patches, P)
-        w16 = ar.b["visual.conv1.weight"].view(D, KP)
-        if KPAD != KP:
-            wp = torch.zeros(D, KPAD, device=dev, dtype=self.compute_dtype)
-            wp[:, :KP].copy_(w16)
-            w16 = wp
-        patch_out = torch.empty(M, D, device=dev, dtype=torch.float32)
-        ops.gemm_bf16(patches, w16, out_f32=patch_out)
+        patches, patch_out = self._patch_rows(image)
         p = ar.params
         saved = st.alloc_saved(B, dev) if train else None
         x = saved["xs"][0, 0] if train else torch.empty(M, D, device=dev, dtype=torch.float32)
@@ -286,7 +295,7 @@ class CLIP(nn.Module):
         ops.vit_embed_ln(patch_out, p["visual.class_embedding"].data, p["visual.positional_embedding"].data,
                          p["visual.ln_pre.weight"].data, p["visual.ln_pre.bias"].data, x, rows=M, T=T, x0=x0,
                          mean=st0[0] if train else None, rstd=st0[1] if train else None)
-        rows = (torch.arange(B, device=dev, dtype=torch.int32) * T).contiguous()
+        rows =(torch.arange(B, device=dev, dtype=torch.int32) * T).contiguous()
         tail = self._tail_rows()
         xo = st.forward(x, B, saved=saved, tail_rows=rows.long() if tail else None,     # tail: [B, D], the class rows only
                         weights_version=ar.shadow_gen)     # moves with every rewrite of the shadows, the fused optimiser's included
@@ -541,6 +550,43 @@ class CLIP(nn.Module):
             self._ensure_runtime()
             return _ImageTower.apply(self, image, *[self._arena.params[n] for n in self._rt["vis_names"]])
         return self._image_forward_lanes(image)
+
+    def encode_image_dense(self, image: torch.Tensor, mode: str = "value") -> torch.Tensor:
+        """One feature per PATCH in the joint embedding space, fp32 [B, grid, grid, embed_dim], not normalised - what
+        training-free dense CLIP classifies (clip/dense.py; MaskCLIP, Zhou et al. 2022).  Blocks 0 .. L-2 run as in encode_image;
+        the last block is BlockStack.dense_tail(mode) ("value": out_proj of each patch's own value vector; "qq" / "kk": self-self
+        attention), then ln_post and visual.proj on every patch row (the class row is dropped).  Inference only; keeps no state:
+        encode_image returns the same bytes before and after."""
+        _require_cuda(image, "encode_image_dense")
+        self._ensure_runtime()
+        ar, geo, st = self._arena, self.geo, self._rt["vis"]
+        ar.refresh_shadows()
+        dev = image.device
+        B, T, D, g = image.shape[0], geo.vision_tokens, geo.vision_width, geo.grid
+        if tuple(image.shape[1:]) != (3, geo.image_resolution, geo.image_resolution):
+            raise RuntimeError(f"encode_image_dense: expected [N,3,{geo.image_resolution},{geo.image_resolution}], got {tuple(image.shape)}")
+        if mode not in st.DENSE_MODES:
+            raise ValueError(f"encode_image_dense: mode must be one of {st.DENSE_MODES}, got {mode!r}")
+        if st.fp8:
+            raise RuntimeError("encode_image_dense: the dense path has no fp8 projections; call fp8_projections(False) first")
+        if B == 0:
+            return torch.empty(0, g, g, geo.embed_dim, device=dev, dtype=torch.float32)
+        M, P = B * T, g * g
+        p = ar.params
+        with torch.no_grad():
+            _, patch_out = self._patch_rows(image)
+            x = torch.empty(M, D, device=dev, dtype=torch.float32)
+            ops.vit_embed_ln(patch_out, p["visual.class_embedding"].data, p["visual.positional_embedding"].data,
+                             p["visual.ln_pre.weight"].data, p["visual.ln_pre.bias"].data, x, rows=M, T=T, x0=None, mean=None, rstd=None)
+            x = st.forward(x, B, layers=len(st.blocks) - 1)
+            y = st.dense_tail(x, B, mode)
+            j = torch.arange(B * P, device=dev, dtype=torch.int32)
+            rows = (j + j // P + 1).contiguous()                      # patch j of image b is row b T + 1 + (j - b P): no class rows
+            post = torch.empty(B * P, D, device=dev, dtype=torch.float32)
+            ops.layernorm_fwd(y, p["visual.ln_post.weight"].data, p["visual.ln_post.bias"].data, rows=B * P, row_index=rows, out_f32=post)
+            feat = torch.empty(B * P, geo.embed_dim, device=dev, dtype=torch.float32)
+            ops.gemm_f32(post, p["visual.proj"].data.t(), feat)       # exact fp32, as the pooled row's projection (DESIGN.md 6.29)
+        return feat.view(B, g, g, geo.embed_dim)
 
     def _image_forward_lanes(self, image: torch.Tensor, streams=None) -> torch.Tensor:
         """Inference: a large batch runs as TWO half batches side by side on two HIP streams - independent kernels fill each

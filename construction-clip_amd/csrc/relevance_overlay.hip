@@ -24,31 +24,10 @@
 #include "../../include/cclip_hip.h"
 
 #pragma clang fp contract(off)
+#include "bilinear.h"                                       // ov_axis, ov_coord, ov_bil (shared with dense_classes.hip)
 
 #define OV_THREADS 1024
 #define OV_WAVES (OV_THREADS / 64)
-
-struct ov_axis { int i0, i1; float w; };
-
-// source samples and weight of output index i on an axis of L source samples (scale = L / S)
-__device__ __forceinline__ ov_axis ov_coord(int i, float scale, int L) {
-  float s = __builtin_fmaf(scale, (float)i + 0.5f, -0.5f);
-  s = s > 0.0f ? s : 0.0f;
-  ov_axis a;
-  a.i0 = (int)s;
-  if (a.i0 > L - 1) a.i0 = L - 1;                           // s < L - 0.5 in exact arithmetic; never leave the source
-  a.i1 = a.i0 + 1 < L ? a.i0 + 1 : L - 1;
-  a.w = s - (float)a.i0;
-  return a;
-}
-
-__device__ __forceinline__ float ov_bil(const float* __restrict__ src, int ld, ov_axis ay, ov_axis ax) {
-  const float* r0 = src + (long)ay.i0 * ld;
-  const float* r1 = src + (long)ay.i1 * ld;
-  const float p00 = r0[ax.i0], p01 = r0[ax.i1], p10 = r1[ax.i0], p11 = r1[ax.i1];
-  const float w1 = ax.w, w0 = 1.0f - w1, h1 = ay.w, h0 = 1.0f - h1;
-  return h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11);
-}
 
 struct ov_geom {
   const float* rel; const float* img;                       // this overlay's grid and image

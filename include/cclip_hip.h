@@ -1131,6 +1131,35 @@ int cclip_gpt2_beam_search_batch(const cclip_beam_batch_desc* d, hipStream_t str
 int cclip_relevance_overlay(const float* rel, int32_t N, int32_t g, const float* images, int64_t image_stride, int32_t R,
                             const float* lut, int32_t S, uint8_t* out, float* map_out, hipStream_t stream);
 
+/* ---- dense zero-shot maps ------------------------------------------------------------------------
+ * Per-patch class probabilities and the label map / picture made from them (csrc/dense_classes.hip); all fp32, no fp16 twin.
+ *
+ * cclip_dense_class_probs: feat [M][E] with row stride ldf (floats), M = B * P patch rows, image b owns rows b P .. b P + P - 1;
+ *   text [C][E] contiguous.  Neither side needs unit rows:
+ *     cos[m][c] = <feat_m, text_c> / (|feat_m| |text_c|), taken as 0 when either norm is 0 (no epsilon is added to a norm, as
+ *                 in cclip_l2norm_fwd; a zero feature row therefore gets the uniform distribution instead of NaN)
+ *     probs[b][c][p] = softmax over c of scale * cos[b P + p][c]        class-major [B][C][P]: probs[b][c] is one g x g map
+ *   logits_out: NULL, or [B][C][P] that receives scale * cos.  One wave per row, the text staged through LDS in tiles, fp32
+ *   accumulation in a fixed order, no atomics: two calls give equal bytes.
+ *   CCLIP_ERR_ARG: a null pointer; M < 1, P < 1 or M not a multiple of P; C outside [1, 255]; E outside [4, 1024] or not a
+ *   multiple of 4; ldf < E or not a multiple of 4; feat or text not 16-byte aligned.
+ *
+ * cclip_dense_label_map: probs [B][C][g][g]; every class map is upsampled to S x S with cclip_relevance_overlay's bil()
+ *   (F.interpolate(mode="bilinear", align_corners=False)), its source coordinate ((2 i + 1) g - S) / (2 S) formed in integers
+ *   so that the weights are one rounding from exact, and per output pixel
+ *     conf   [B][S][S] fp32  = the largest upsampled probability
+ *     labels [B][S][S] uint8 = the LOWEST class index that reaches it, 255 when conf < min_conf
+ *   overlay (NULL, or uint8 [B][S][S][3]; needs palette uint8 [256][3], row 255 = the colour of "no class"):
+ *     palette[label][ch] without a photo; with photo (uint8 [B][S][S][3], already S x S)
+ *     (photo * (256 - a8) + palette[label][ch] * a8 + 128) >> 8, a8 an integer in [0, 256] - exact given the labels.
+ *   labels, overlay and photo may have any alignment; C in [1, 255]; 1 <= g, S <= CCLIP_OVERLAY_MAX_SIDE.  No atomics: two
+ *   calls give equal bytes. */
+int cclip_dense_class_probs(const float* feat, int64_t ldf, int64_t M, int32_t P, const float* text, int32_t C, int32_t E,
+                            float scale, float* probs, float* logits_out, hipStream_t stream);
+int cclip_dense_label_map(const float* probs, int32_t B, int32_t C, int32_t g, int32_t S, float min_conf, uint8_t* labels,
+                          float* conf, const uint8_t* palette, const uint8_t* photo, int32_t a8, uint8_t* overlay,
+                          hipStream_t stream);
+
 /* ---- CLIP-guided caption selection ---------------------------------------------------------------
  * K candidate captions for each of N images, scored against the image (CLIPScore, Hessel et al. 2021), optionally against the
  * image's reference captions (RefCLIPScore), and ranked - one launch, one work-group per image (csrc/caption_select.hip).

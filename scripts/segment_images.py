@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Dense zero-shot maps straight from image files: where in each photo is which class (`clip.segment`: training-free dense CLIP on
+the image tower's per-patch features; csrc/dense_classes.hip).  The classes are --prompts, or with --types the caption / violation
+type lists of the reference (the keys of CLIP_prefix_caption/parse_coco.py's caption_type and violation_type, as predict_clip.py's
+default prompts and describe_images.py use them).  One JSON line per image: the share of pixels per class ("none" last), the
+class with the largest area, the mean confidence; --png DIR also writes the label colours blended over the photo.
+
+    python scripts/segment_images.py photos/ --checkpoint clip.pt --prompts "a worker without a helmet" scaffold ground --png maps
+    python scripts/segment_images.py --synthetic --png /tmp/maps                     # offline: seeded model, generated images"""
+from __future__ import annotations
+
+import argparse
+import os
+import tempfile
+
+import _common as C
+import torch
+
+from describe_images import SYNTHETIC_TYPES, SYNTHETIC_VIOLATIONS
+from explain_images import list_images
+
+
+def build_parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("images", nargs="*", help="image files and / or directories of them")
+    ap.add_argument("--model", default="ViT-B/32")
+    ap.add_argument("--checkpoint", default=None, help="fine-tuned CLIP state dict")
+    ap.add_argument("--prompts", nargs="+", default=None, help="one class per prompt (default: violation status, predict.py:39)")
+    ap.add_argument("--types", choices=("caption", "violation"), default=None, help="use the caption / violation type list as the classes")
+    ap.add_argument("--mode", choices=("value", "qq", "kk"), default="value", help="the last block's dense tail (clip.segment)")
+    ap.add_argument("--size", type=int, default=None, help="side of the label map (default: the model's input resolution)")
+    ap.add_argument("--min-conf", type=float, default=0.0, help="pixels whose best probability is lower get no class")
+    ap.add_argument("--temperature", type=float, default=None, help="factor on the cosines (default: the model's logit scale)")
+    ap.add_argument("--alpha", type=float, default=0.5, help="--png: weight of the label colour over the photo")
+    ap.add_argument("--bs", type=int, default=16, help="images per clip.segment call")
+    ap.add_argument("--png", default=None, metavar="DIR", help="write one overlay PNG per image here")
+    ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--n_images", type=int, default=3, help="--synthetic: images to segment")
+    return ap
+
+
+def class_prompts(args):
+    if args.prompts:
+        return list(args.prompts)
+    if args.types == "caption":
+        return list(SYNTHETIC_TYPES) if args.synthetic else ["status", "violation"]
+    if args.types == "violation":
+        return list(SYNTHETIC_VIOLATIONS) if args.synthetic else list(C.CLASSES)
+    return ["violation", "status"]
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    import clip
+    from PIL import Image
+    device = torch.device("cuda:0")
+    tmp = None
+    if args.synthetic:
+        tmp = tempfile.TemporaryDirectory()
+        C.make_synthetic_annotations(tmp.name, per_class=1 + (args.n_images - 1) // len(C.CLASSES))
+        d = os.path.join(tmp.name, "images")
+        files = [os.path.join(d, f) for f in sorted(os.listdir(d))][:args.n_images]
+        args.model = "test-tiny"
+    else:
+        files = list_images(args.images)
+    if not files:
+        raise SystemExit("no images given (or --synthetic)")
+    model, preprocess = clip.load(args.model, device=device, jit=False)
+    if args.checkpoint:
+        model.load_state_dict(torch.load(args.checkpoint, map_location="cpu", weights_only=True))
+    model.eval()
+    prompts = class_prompts(args)
+    with torch.no_grad():
+        text = model.encode_text(C.get_tokenize(model)(prompts).to(device)).float()      # once for every image
+    S = args.size or model.geo.image_resolution
+    if args.png:
+        os.makedirs(args.png, exist_ok=True)
+    out = []
+    for i in range(0, len(files), args.bs):
+        chunk = files[i:i + args.bs]
+        pics = [Image.open(f).convert("RGB") for f in chunk]
+        image = torch.stack([preprocess(p) for p in pics]).to(device)
+        res = clip.segment(model, image, text, mode=args.mode, size=S, min_conf=args.min_conf, temperature=args.temperature)
+        fractions, top = res.area_fractions().cpu(), res.top_class()
+        mean_conf = res.conf.flatten(1).mean(dim=1).cpu()
+        overlay = None
+        if args.png:
+            import numpy as np
+            photo = torch.stack([torch.from_numpy(np.asarray(p.resize((S, S), Image.BILINEAR)).copy()) for p in pics])
+            overlay = res.overlay(photo=photo, alpha=args.alpha).cpu().numpy()
+        for j, f in enumerate(chunk):
+            line = dict(file=f, classes=prompts, area=[round(v, 6) for v in fractions[j].tolist()],
+                        top_class=None if top[j] is None else prompts[top[j]], mean_conf=round(float(mean_conf[j]), 5))
+            if overlay is not None:
+                line["png"] = os.path.join(args.png, f"{i + j:05d}_{os.path.splitext(os.path.basename(f))[0]}.png")
+                Image.fromarray(overlay[j]).save(line["png"])
+            C.log_line(**line)
+            out.append(line)
+    if tmp is not None:
+        tmp.cleanup()
+    return out
+
+
+if __name__ == "__main__":
+    main()
