@@ -2001,6 +2001,63 @@ def dense_label_map(probs: torch.Tensor, size: int, labels: torch.Tensor, conf: 
           "cclip_dense_label_map")
 
 
+DENSE_MAX_WINDOWS = 65535
+
+
+def dense_stitch(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: int, labels: torch.Tensor, conf: torch.Tensor, *,
+                 min_conf: float = 0.0, cover: Optional[torch.Tensor] = None, overlay: Optional[torch.Tensor] = None,
+                 palette: Optional[torch.Tensor] = None, photo: Optional[torch.Tensor] = None, alpha8: int = 256) -> None:
+    """Stitch the class maps of K windows into one picture (include/cclip_hip.h, cclip_dense_stitch): probs fp32 [K, C, g, g], map
+    set k sampled window-locally over boxes[k] = (x0, y0, x1, y1) (int32 [K, 4], cuda) and averaged, in ascending k, over the
+    windows that cover a pixel -> labels uint8 [height, width] (255: below min_conf, or no window), conf fp32 [height, width],
+    cover uint8 [height, width] (windows per pixel, saturating) and overlay uint8 [height, width, 3] as dense_label_map makes
+    it (palette uint8 [256, 3], photo uint8 [height, width, 3]).  The boxes are NOT read back: an empty, inverted or oversized
+    box covers nothing, one that hangs over the edge covers what lies inside, and no box value leads the kernel outside probs.
+    Contiguous cuda tensors on one device; no CPU path.  Two calls give equal bytes."""
+    fname = "dense_stitch"
+    tensors = [(probs, "probs", torch.float32), (boxes, "boxes", torch.int32), (labels, "labels", torch.uint8),
+               (conf, "conf", torch.float32)]
+    for t, name in ((cover, "cover"), (overlay, "overlay"), (palette, "palette"), (photo, "photo")):
+        if t is not None:
+            tensors.append((t, name, torch.uint8))
+    _dense_operands(fname, tensors, probs)
+    if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
+        raise ValueError(f"{fname}: probs must be [K, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
+    K, C, g, _ = probs.shape
+    if K > DENSE_MAX_WINDOWS:
+        raise ValueError(f"{fname}: probs holds {K} windows; at most {DENSE_MAX_WINDOWS}")
+    if C > DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: probs holds {C} classes; at most {DENSE_MAX_CLASSES} (label 255 means none)")
+    if tuple(boxes.shape) != (K, 4):
+        raise ValueError(f"{fname}: boxes must be [{K}, 4] as (x0, y0, x1, y1), got {tuple(boxes.shape)}")
+    if int(height) != height or int(width) != width or not 1 <= height <= OVERLAY_MAX_SIDE or not 1 <= width <= OVERLAY_MAX_SIDE \
+            or g > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: height {height}, width {width}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    H, W = int(height), int(width)
+    if tuple(labels.shape) != (H, W):
+        raise ValueError(f"{fname}: labels must be [{H}, {W}], got {tuple(labels.shape)}")
+    if tuple(conf.shape) != (H, W):
+        raise ValueError(f"{fname}: conf must be [{H}, {W}], got {tuple(conf.shape)}")
+    if cover is not None and tuple(cover.shape) != (H, W):
+        raise ValueError(f"{fname}: cover must be [{H}, {W}], got {tuple(cover.shape)}")
+    if overlay is None and (photo is not None or palette is not None):
+        raise ValueError(f"{fname}: palette and photo are inputs of the overlay; give overlay too")
+    if overlay is not None:
+        if palette is None or tuple(palette.shape) != (256, 3):
+            raise ValueError(f"{fname}: palette must be uint8 [256, 3], got {None if palette is None else tuple(palette.shape)}")
+        if tuple(overlay.shape) != (H, W, 3):
+            raise ValueError(f"{fname}: overlay must be [{H}, {W}, 3], got {tuple(overlay.shape)}")
+        if photo is not None and tuple(photo.shape) != (H, W, 3):
+            raise ValueError(f"{fname}: photo must be [{H}, {W}, 3] (already at the output size), got {tuple(photo.shape)}")
+    if int(alpha8) != alpha8 or not 0 <= alpha8 <= 256:
+        raise ValueError(f"{fname}: alpha8 must be an integer in [0, 256], got {alpha8}")
+    if probs.data_ptr() % 4 or conf.data_ptr() % 4 or boxes.data_ptr() % 4:
+        raise ValueError(f"{fname}: probs, conf and boxes must start on a 4-byte boundary")
+    check(lib.cclip_dense_stitch(_p(probs), c_int(K), c_int(C), c_int(g), _p(boxes), c_int(H), c_int(W), c_float(float(min_conf)),
+                                 _p(labels), _p(conf), _p(cover), _p(palette), _p(photo), c_int(int(alpha8)), _p(overlay), _stream()),
+          "cclip_dense_stitch")
+
+
 # --------------------------------------------------------------------------------------------
 # fp8 (e4m3) inference projections
 # --------------------------------------------------------------------------------------------

@@ -24,4 +24,5 @@ from .probe import LinearProbe, ProbeLossFunction, ProbeFitResult  # noqa: F401 
 from .gaussian import GaussianClassifier, ClassMoments, MahalanobisScores, PCAResult, class_moments, pca  # noqa: F401  (Gaussian class models: training-free classifier, outlier scores, PCA)
 from .regions import encode_regions, classify_regions  # noqa: F401  (embed / zero-shot-classify every detector box of a photo)
 from .dense import segment, dense_features, DenseResult, default_palette  # noqa: F401  (dense zero-shot maps: per-patch class probabilities, label maps)
+from .dense import segment_photo, plan_windows, PhotoDenseResult, label_boxes  # noqa: F401  (whole photos: sliding windows stitched in one launch)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

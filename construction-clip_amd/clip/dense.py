@@ -13,13 +13,20 @@ score it q.q^T or k.k^T, so that a patch attends to patches like itself.  `CLIP.
 
 both in csrc/dense_classes.hip.  The classes are a short fixed list here (the reference's caption_type / violation_type), which
 is exactly the setting the method is for.  HIP only: there is no CPU path.
+
+Whole photos.  The tower sees a square at its own resolution; a multi-megapixel, non-square site photo goes through
+sliding-window inference, as MaskCLIP, SCLIP and ClearCLIP are evaluated: `plan_windows` lays overlapping squares over the
+photo (several sizes for a multi-scale ensemble), `segment_photo` runs the tower on all of them and ops.dense_stitch
+(csrc/dense_stitch.hip) averages the class probabilities where windows overlap, straight into the photo-sized label map,
+confidence map and picture.  `segment(size=(height, width))` is the one-window case: a non-square label map.
 """
 from __future__ import annotations
 
 import colorsys
 from dataclasses import dataclass
-from typing import Callable, List, Optional, Sequence, Union
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 
 from cclip_hip import ops
@@ -61,9 +68,12 @@ class DenseResult:
     def overlay(self, photo: Optional[torch.Tensor] = None, alpha: float = 0.5, palette: Optional[torch.Tensor] = None) -> torch.Tensor:
         """uint8 [B, S, S, 3]: the palette colour of every pixel's label - over `photo` (uint8 [B, S, S, 3] or [S, S, 3], already
         at the map's size) with weight a8 / 256, a8 = round(256 alpha), as (photo (256 - a8) + colour a8 + 128) >> 8.  The labels
-        and conf are recomputed by the same launch and come out as they are."""
+        and conf are recomputed by the same launch and come out as they are.  A result of segment(size=(height, width)) works the
+        same way, S, S read as height, width: one dense_stitch launch per image."""
         B, S = self.labels.shape[0], self.labels.shape[1]
         dev = self.probs.device
+        if self.labels.shape[2] != S:
+            return self._overlay_rect(photo, alpha, palette)
         if not 0.0 <= alpha <= 1.0:
             raise ValueError(f"overlay: alpha must lie in [0, 1], got {alpha}")
         pal = default_palette(self.n_classes) if palette is None else palette
@@ -80,6 +90,18 @@ class DenseResult:
         out = torch.empty(B, S, S, 3, device=dev, dtype=torch.uint8)
         ops.dense_label_map(self.probs, S, torch.empty_like(self.labels), torch.empty_like(self.conf), min_conf=self.min_conf,
                             overlay=out, palette=pal.to(dev).contiguous(), photo=photo, alpha8=int(round(256 * alpha)))
+        return out
+
+    def _overlay_rect(self, photo, alpha, palette) -> torch.Tensor:
+        B, H, W = self.labels.shape
+        dev = self.probs.device
+        pal, photo, a8 = _overlay_inputs(alpha, palette, self.n_classes, photo, (B, H, W, 3), dev)
+        out = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8)
+        box = _device_boxes(np.array([[0, 0, W, H]]), dev)
+        lab, conf = torch.empty(H, W, device=dev, dtype=torch.uint8), torch.empty(H, W, device=dev, dtype=torch.float32)
+        for b in range(B):
+            ops.dense_stitch(self.probs[b:b + 1], box, H, W, lab, conf, min_conf=self.min_conf, overlay=out[b], palette=pal,
+                             photo=None if photo is None else photo[b], alpha8=a8)
         return out
 
     def area_fractions(self) -> torch.Tensor:
@@ -118,22 +140,233 @@ def class_features(model, classes: Union[torch.Tensor, Sequence[str]], tokenize:
 
 
 def segment(model, image: torch.Tensor, classes: Union[torch.Tensor, Sequence[str]], *, mode: str = "value",
-            size: Optional[int] = None, min_conf: float = 0.0, temperature: Optional[float] = None,
+            size: Union[None, int, Tuple[int, int]] = None, min_conf: float = 0.0, temperature: Optional[float] = None,
             tokenize: Optional[Callable] = None) -> DenseResult:
     """Label every pixel of `image` ([B, 3, R, R], preprocessed) with one of `classes` ([C, E] features or C prompt strings,
-    1 <= C <= 255).  size: side of the label map (default: the model's input resolution).  temperature: the factor on the
-    cosines before the softmax (default exp(model.logit_scale)).  Pixels whose best probability is below min_conf get 255."""
+    1 <= C <= 255).  size: side of the label map (default: the model's input resolution), or (height, width) for a map that
+    is not square - the class maps are then stretched over it, each axis with its own scale (one ops.dense_stitch launch per
+    image, one window covering the map).  temperature: the factor on the cosines before the softmax (default
+    exp(model.logit_scale)).  Pixels whose best probability is below min_conf get 255."""
     text, names = class_features(model, classes, tokenize)
     feats = dense_features(model, image, mode)
     B, g, _, E = feats.shape
     C = text.shape[0]
     dev = feats.device
-    S = model.geo.image_resolution if size is None else int(size)
+    rect = isinstance(size, (tuple, list))
+    if rect:
+        if len(size) != 2:
+            raise ValueError(f"segment: size must be an int or (height, width), got {size!r}")
+        H, W = int(size[0]), int(size[1])
+    else:
+        H = W = model.geo.image_resolution if size is None else int(size)
     scale = float(model.logit_scale.detach().exp()) if temperature is None else float(temperature)
     probs = torch.empty(B, C, g, g, device=dev, dtype=torch.float32)
-    labels = torch.empty(B, S, S, device=dev, dtype=torch.uint8)
-    conf = torch.empty(B, S, S, device=dev, dtype=torch.float32)
+    labels = torch.empty(B, H, W, device=dev, dtype=torch.uint8)
+    conf = torch.empty(B, H, W, device=dev, dtype=torch.float32)
     if B > 0:
         ops.dense_class_probs(feats.view(B * g * g, E), text, scale, g * g, probs.view(B, C, g * g))
-        ops.dense_label_map(probs, S, labels, conf, min_conf=min_conf)
+        if rect:
+            box = _device_boxes(np.array([[0, 0, W, H]]), dev)
+            for b in range(B):
+                ops.dense_stitch(probs[b:b + 1], box, H, W, labels[b], conf[b], min_conf=min_conf)
+        else:
+            ops.dense_label_map(probs, H, labels, conf, min_conf=min_conf)
     return DenseResult(probs=probs, labels=labels, conf=conf, class_names=names, min_conf=float(min_conf))
+
+
+# ---- whole photos: sliding windows, stitched ---------------------------------------------------
+def _device_boxes(boxes: np.ndarray, dev) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.int32)).to(dev)
+
+
+def _overlay_inputs(alpha, palette, n_classes, photo, shape, dev):
+    """(palette on the device, photo on the device or None, a8) of an overlay of `shape` = ([B,] H, W, 3), checked"""
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"overlay: alpha must lie in [0, 1], got {alpha}")
+    pal = default_palette(n_classes) if palette is None else palette
+    if not isinstance(pal, torch.Tensor) or pal.dtype != torch.uint8 or tuple(pal.shape) != (256, 3):
+        raise ValueError("overlay: palette must be a uint8 [256, 3] tensor")
+    if photo is not None:
+        if isinstance(photo, np.ndarray):
+            photo = torch.from_numpy(np.ascontiguousarray(photo))
+        if not isinstance(photo, torch.Tensor) or photo.dtype != torch.uint8:
+            raise ValueError(f"overlay: photo must be a uint8 tensor {list(shape)}")
+        if len(shape) == 4 and photo.dim() == 3:
+            photo = photo.unsqueeze(0).expand(shape[0], -1, -1, -1)
+        if tuple(photo.shape) != tuple(shape):
+            raise ValueError(f"overlay: photo must be {list(shape)} (resize it to the map first), got {tuple(photo.shape)}")
+        photo = photo.to(dev).contiguous()
+    return pal.to(dev).contiguous(), photo, int(round(256 * alpha))
+
+
+def _plan_one(width: int, height: int, window: int, stride: Optional[int]) -> np.ndarray:
+    if int(window) != window or window < 2:
+        raise ValueError(f"plan_windows: window must be an integer >= 2, got {window}")
+    window = int(window)
+    stride = window // 2 if stride is None else stride
+    if int(stride) != stride or stride < 1:
+        raise ValueError(f"plan_windows: stride must be an integer >= 1, got {stride}")
+    if stride > window:
+        raise ValueError(f"plan_windows: stride {stride} exceeds window {window}: pixels between two windows would be covered by none")
+    side = min(window, width, height)
+    step = min(int(stride), side)                 # a window clipped to a small photo keeps the lattice free of holes
+
+    def starts(length):
+        last = length - side
+        s = list(range(0, last + 1, step))
+        if s[-1] != last:
+            s.append(last)                        # the last row / column, shifted back flush with the edge
+        return s
+
+    xs, ys = starts(width), starts(height)
+    return np.array([[x, y, x + side, y + side] for y in ys for x in xs], dtype=np.int64).reshape(-1, 4)
+
+
+def plan_windows(width: int, height: int, window, stride=None) -> np.ndarray:
+    """int64 [K, 4] (x0, y0, x1, y1): square windows of side min(window, width, height) on a `stride` lattice (default
+    window // 2; never more than the side), row-major, the last row and column shifted back flush with the photo's edge
+    (MMSegmentation's "slide" mode): every pixel is covered and no window leaves the photo.  `window` may be a sequence of sizes
+    (a multi-scale ensemble): the lists are concatenated in the order given, and `stride` is then a sequence of the same length
+    or None.  ValueError: window < 2, stride < 1, stride > window (holes), an empty photo."""
+    if int(width) != width or int(height) != height or width < 1 or height < 1:
+        raise ValueError(f"plan_windows: the photo must be at least 1 x 1, got {width} x {height}")
+    width, height = int(width), int(height)
+    if isinstance(window, (list, tuple, np.ndarray)):
+        wins = list(window)
+        if not wins:
+            raise ValueError("plan_windows: no window size given")
+        if stride is None:
+            strides = [None] * len(wins)
+        elif isinstance(stride, (list, tuple, np.ndarray)) and len(stride) == len(wins):
+            strides = list(stride)
+        else:
+            raise ValueError(f"plan_windows: with {len(wins)} window sizes, stride must be None or a sequence of {len(wins)}, got {stride!r}")
+        return np.concatenate([_plan_one(width, height, w, s) for w, s in zip(wins, strides)], axis=0)
+    if isinstance(stride, (list, tuple, np.ndarray)):
+        raise ValueError(f"plan_windows: one window size takes one stride, got {stride!r}")
+    return _plan_one(width, height, window, stride)
+
+
+def label_boxes(labels, c: int, min_area: int = 1) -> List[Tuple[int, int, int, int]]:
+    """(x0, y0, x1, y1) of every 4-connected component of label `c` in the [H, W] map with at least min_area pixels, in the order
+    of each component's first pixel (row-major).  Host side, numpy only: the runs of `c` in every row, joined to the runs they
+    touch in the row above by union-find."""
+    lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    if lab.ndim != 2:
+        raise ValueError(f"class_boxes: labels must be [H, W], got {lab.shape}")
+    H, W = lab.shape
+    parent: List[int] = []
+    runs = []                                      # (y, x0, x1) per run id
+
+    def find(i):
+        while parent[i] != i:
+            parent[i] = parent[parent[i]]
+            i = parent[i]
+        return i
+
+    prev: List[int] = []
+    for y in range(H):
+        m = np.concatenate(([0], (lab[y] == c).astype(np.int8), [0]))
+        d = np.diff(m)
+        cur = []
+        for x0, x1 in zip(np.flatnonzero(d == 1).tolist(), np.flatnonzero(d == -1).tolist()):
+            i = len(parent)
+            parent.append(i)
+            runs.append((y, x0, x1))
+            for j in prev:
+                if runs[j][1] < x1 and x0 < runs[j][2]:                      # share a column: 4-connected
+                    a, b = find(i), find(j)
+                    if a != b:
+                        parent[max(a, b)] = min(a, b)                        # the root is the component's first run
+            cur.append(i)
+        prev = cur
+    comps = {}
+    for i, (y, x0, x1) in enumerate(runs):
+        r = find(i)
+        bx = comps.get(r)
+        comps[r] = [x0, y, x1, y + 1, x1 - x0] if bx is None else [min(bx[0], x0), bx[1], max(bx[2], x1), y + 1, bx[4] + x1 - x0]
+    return [(b[0], b[1], b[2], b[3]) for _, b in sorted(comps.items()) if b[4] >= min_area]
+
+
+@dataclass
+class PhotoDenseResult:
+    probs: torch.Tensor                  # fp32 [K, C, g, g]: the class maps of every window
+    boxes: torch.Tensor                  # int64 [K, 4] (CPU): the windows, (x0, y0, x1, y1) in photo pixels
+    labels: torch.Tensor                 # uint8 [H, W]; 255 = none
+    conf: torch.Tensor                   # fp32 [H, W]
+    cover: torch.Tensor                  # uint8 [H, W]: windows per pixel (saturating at 255)
+    class_names: Optional[List[str]]
+    min_conf: float = 0.0
+
+    @property
+    def n_classes(self) -> int:
+        return self.probs.shape[1]
+
+    def overlay(self, photo=None, alpha: float = 0.5, palette: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 [H, W, 3]: the palette colour of every pixel's label, over `photo` (the uint8 [H, W, 3] photo itself) with weight
+        round(256 alpha) / 256 when one is given.  Re-runs the stitch launch, as DenseResult.overlay re-runs its own."""
+        H, W = self.labels.shape
+        dev = self.probs.device
+        pal, photo, a8 = _overlay_inputs(alpha, palette, self.n_classes, photo, (H, W, 3), dev)
+        out = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+        ops.dense_stitch(self.probs, _device_boxes(self.boxes.numpy(), dev), H, W, torch.empty_like(self.labels),
+                         torch.empty_like(self.conf), min_conf=self.min_conf, overlay=out, palette=pal, photo=photo, alpha8=a8)
+        return out
+
+    def area_fractions(self) -> torch.Tensor:
+        """fp64 [C + 1]: the share of pixels per class, "none" last; integer counts divided once by H * W: they sum to 1."""
+        C = self.n_classes
+        lab = self.labels.reshape(-1).long()
+        lab = torch.where(lab == NONE_LABEL, torch.full_like(lab, C), lab)
+        return torch.bincount(lab, minlength=C + 1).double() / lab.numel()
+
+    def top_class(self) -> Optional[int]:
+        """the class with the largest area, None when no pixel has a class"""
+        fr = self.area_fractions()[:-1].cpu()
+        return int(fr.argmax()) if float(fr.max()) > 0 else None
+
+    def class_boxes(self, c: int, min_area: int = 1) -> List[Tuple[int, int, int, int]]:
+        """bounding boxes (x0, y0, x1, y1) of the 4-connected components of label c (`label_boxes`): what classify_regions takes"""
+        return label_boxes(self.labels, c, min_area)
+
+
+def segment_photo(model, image, classes: Union[torch.Tensor, Sequence[str]], *, window=None, stride=None, mode: str = "value",
+                  min_conf: float = 0.0, temperature: Optional[float] = None, batch: int = 64, preprocess=None,
+                  tokenize: Optional[Callable] = None) -> PhotoDenseResult:
+    """Label every pixel of one photo of ANY size (a PIL RGB image or a uint8 HWC array / tensor) by sliding-window inference:
+    `plan_windows(width, height, window, stride)` (window: default the model's input resolution; a sequence = multi-scale),
+    `DevicePreprocess.regions` for all K crops in one upload, `encode_image_dense` in chunks of `batch` windows, one
+    ops.dense_class_probs per chunk into one [K, C, g, g] buffer, and ONE ops.dense_stitch at the photo's H x W.  A window that
+    the region kernels cannot reduce (check_downscale) is a ValueError that names its size.  Results are not promised to be
+    bitwise independent of `batch` (the GEMM tile choice may follow the row count)."""
+    from .preprocess_device import DevicePreprocess, check_downscale
+    dev = model.logit_scale.device
+    R = model.geo.image_resolution
+    pre = DevicePreprocess(R, dev) if preprocess is None else preprocess
+    if not isinstance(pre, DevicePreprocess) or pre.n_px != R:
+        raise ValueError(f"segment_photo: preprocess must be a DevicePreprocess of the model's resolution {R}")
+    if int(batch) != batch or batch < 1:
+        raise ValueError(f"segment_photo: batch must be an integer >= 1, got {batch}")
+    arr = DevicePreprocess._pixels(image)
+    if arr is None:
+        raise ValueError(f"segment_photo: a PIL image must have mode RGB, got {image.mode} (convert it first)")
+    H, W = int(arr.shape[0]), int(arr.shape[1])
+    boxes = plan_windows(W, H, R if window is None else window, stride)
+    check_downscale(boxes, R)
+    text, names = class_features(model, classes, tokenize)
+    C, K = text.shape[0], boxes.shape[0]
+    scale = float(model.logit_scale.detach().exp()) if temperature is None else float(temperature)
+    crops = pre.regions(arr, boxes)                                           # [K, 3, R, R], one upload
+    probs = None
+    for i in range(0, K, int(batch)):
+        feats = dense_features(model, crops[i:i + batch], mode)
+        b, g, _, E = feats.shape
+        if probs is None:
+            probs = torch.empty(K, C, g, g, device=dev, dtype=torch.float32)
+        ops.dense_class_probs(feats.view(b * g * g, E), text, scale, g * g, probs[i:i + b].view(b, C, g * g))
+    labels = torch.empty(H, W, device=dev, dtype=torch.uint8)
+    conf = torch.empty(H, W, device=dev, dtype=torch.float32)
+    cover = torch.empty(H, W, device=dev, dtype=torch.uint8)
+    ops.dense_stitch(probs, _device_boxes(boxes, dev), H, W, labels, conf, min_conf=min_conf, cover=cover)
+    return PhotoDenseResult(probs=probs, boxes=torch.from_numpy(boxes), labels=labels, conf=conf, cover=cover, class_names=names,
+                            min_conf=float(min_conf))

@@ -1160,6 +1160,33 @@ int cclip_dense_label_map(const float* probs, int32_t B, int32_t C, int32_t g, i
                           float* conf, const uint8_t* palette, const uint8_t* photo, int32_t a8, uint8_t* overlay,
                           hipStream_t stream);
 
+/* cclip_dense_stitch (csrc/dense_stitch.hip): K class-map sets probs [K][C][g][g], set k the dense head's answer for the window
+ *   boxes[k] = (x0, y0, x1, y1) (int32 [K][4], on the device) of one H x W picture, stitched into the picture's label map,
+ *   confidence map and picture in one launch.  Sliding windows, a multi-scale list of squares, or one rectangle over a
+ *   non-square picture are all lists of boxes.
+ *   Coverage: window k covers pixel (x, y) when x0 <= x < x1, y0 <= y < y1, 1 <= x1 - x0 <= CCLIP_OVERLAY_MAX_SIDE and
+ *     1 <= y1 - y0 <= CCLIP_OVERLAY_MAX_SIDE, the sides formed without 32-bit overflow.  An empty, inverted or oversized box
+ *     covers nothing; a box may hang over the picture's edge.  The launcher cannot see the boxes: the kernel itself reads
+ *     nothing outside probs and boxes for ANY box values.
+ *   Sample: s_kc = bil of probs[k][c] at the window-local position (y - y0, x - x0), align_corners=False, the y axis with
+ *     scale g / (y1 - y0) and the x axis with g / (x1 - x0), coordinates formed in integers as in cclip_dense_label_map.
+ *   Average: over the n covering windows k1 < k2 < .. in ascending k, u_c = ((s_k1c + s_k2c) + ..) / (float)n - the sum seeded
+ *     with the first sample, fp32 adds left to right, one division also when n = 1.
+ *     conf   [H][W] fp32  = max_c u_c;   0 when n = 0
+ *     labels [H][W] uint8 = the LOWEST class reaching conf, 255 when conf < min_conf or n = 0
+ *     cover  NULL, or [H][W] uint8 = min(n, 255)
+ *     overlay NULL, or uint8 [H][W][3]: cclip_dense_label_map's integer formula on the label (palette [256][3], photo NULL or
+ *     uint8 [H][W][3], a8 in [0, 256]).
+ *   For K = 1, H = W = S and the box (0, 0, S, S), labels, conf and overlay equal cclip_dense_label_map's bit for bit.  There is
+ *   no cap on how many windows cover a pixel.  One launch, no atomics, nothing depends on the launch geometry: two calls give
+ *   equal bytes.
+ *   CCLIP_ERR_ARG, nothing launched: probs, boxes, labels or conf NULL; K outside [1, 65535]; C outside [1, 255]; g, H or W
+ *   outside [1, CCLIP_OVERLAY_MAX_SIDE]; overlay without palette, photo without overlay, a8 outside [0, 256]; probs, conf or
+ *   boxes not 4-byte aligned.  labels, cover, overlay and photo may have any alignment. */
+int cclip_dense_stitch(const float* probs, int32_t K, int32_t C, int32_t g, const int32_t* boxes, int32_t H, int32_t W,
+                       float min_conf, uint8_t* labels, float* conf, uint8_t* cover, const uint8_t* palette, const uint8_t* photo,
+                       int32_t a8, uint8_t* overlay, hipStream_t stream);
+
 /* ---- CLIP-guided caption selection ---------------------------------------------------------------
  * K candidate captions for each of N images, scored against the image (CLIPScore, Hessel et al. 2021), optionally against the
  * image's reference captions (RefCLIPScore), and ranked - one launch, one work-group per image (csrc/caption_select.hip).

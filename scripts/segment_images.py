@@ -4,8 +4,12 @@ the image tower's per-patch features; csrc/dense_classes.hip).  The classes are 
 type lists of the reference (the keys of CLIP_prefix_caption/parse_coco.py's caption_type and violation_type, as predict_clip.py's
 default prompts and describe_images.py use them).  One JSON line per image: the share of pixels per class ("none" last), the
 class with the largest area, the mean confidence; --png DIR also writes the label colours blended over the photo.
+With --window (and / or --stride) every photo is segmented at its OWN size by sliding windows (`clip.segment_photo`: overlapping
+crops through the tower, probabilities averaged where they overlap, csrc/dense_stitch.hip); several --window sizes make a
+multi-scale ensemble.  The JSON line then also carries "windows", "height" and "width", and the PNG has the photo's size.
 
     python scripts/segment_images.py photos/ --checkpoint clip.pt --prompts "a worker without a helmet" scaffold ground --png maps
+    python scripts/segment_images.py photos/ --checkpoint clip.pt --window 224 448 --max-side 2048 --png maps
     python scripts/segment_images.py --synthetic --png /tmp/maps                     # offline: seeded model, generated images"""
 from __future__ import annotations
 
@@ -34,6 +38,10 @@ def build_parser():
     ap.add_argument("--alpha", type=float, default=0.5, help="--png: weight of the label colour over the photo")
     ap.add_argument("--bs", type=int, default=16, help="images per clip.segment call")
     ap.add_argument("--png", default=None, metavar="DIR", help="write one overlay PNG per image here")
+    ap.add_argument("--window", type=int, nargs="+", default=None, metavar="N",
+                    help="sliding windows of side N over each photo at its own size (several: multi-scale); default with --stride: the model's resolution")
+    ap.add_argument("--stride", type=int, default=None, help="step of the window lattice (default: half of each window)")
+    ap.add_argument("--max-side", type=int, default=None, metavar="M", help="--window: first shrink a photo whose longer side exceeds M")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=3, help="--synthetic: images to segment")
     return ap
@@ -47,6 +55,37 @@ def class_prompts(args):
     if args.types == "violation":
         return list(SYNTHETIC_VIOLATIONS) if args.synthetic else list(C.CLASSES)
     return ["violation", "status"]
+
+
+def photos(args, model, files, prompts, text):
+    """--window / --stride: one clip.segment_photo per photo, at the photo's size"""
+    import clip
+    from PIL import Image
+    from clip.preprocess_device import DevicePreprocess
+    windows = list(args.window) if args.window else [model.geo.image_resolution]
+    window = windows if len(windows) > 1 else windows[0]
+    stride = None if args.stride is None else ([args.stride] * len(windows) if len(windows) > 1 else args.stride)
+    pre = DevicePreprocess(model.geo.image_resolution, text.device)
+    out = []
+    for i, f in enumerate(files):
+        pic = Image.open(f).convert("RGB")
+        if args.max_side and max(pic.size) > args.max_side:
+            k = args.max_side / max(pic.size)
+            pic = pic.resize((max(1, round(pic.size[0] * k)), max(1, round(pic.size[1] * k))), Image.BICUBIC)
+        res = clip.segment_photo(model, pic, text, window=window, stride=stride, mode=args.mode, min_conf=args.min_conf,
+                                 temperature=args.temperature, batch=args.bs, preprocess=pre)
+        top = res.top_class()
+        line = dict(file=f, classes=prompts, area=[round(v, 6) for v in res.area_fractions().tolist()],
+                    top_class=None if top is None else prompts[top], mean_conf=round(float(res.conf.mean()), 5),
+                    windows=int(res.boxes.shape[0]), height=int(res.labels.shape[0]), width=int(res.labels.shape[1]))
+        if args.png:
+            import numpy as np
+            photo = torch.from_numpy(np.asarray(pic, dtype=np.uint8).copy())
+            line["png"] = os.path.join(args.png, f"{i:05d}_{os.path.splitext(os.path.basename(f))[0]}.png")
+            Image.fromarray(res.overlay(photo=photo, alpha=args.alpha).cpu().numpy()).save(line["png"])
+        C.log_line(**line)
+        out.append(line)
+    return out
 
 
 def main(argv=None):
@@ -75,6 +114,13 @@ def main(argv=None):
     S = args.size or model.geo.image_resolution
     if args.png:
         os.makedirs(args.png, exist_ok=True)
+    if args.window is not None or args.stride is not None:
+        out = photos(args, model, files, prompts, text)
+        if tmp is not None:
+            tmp.cleanup()
+        return out
+    if args.max_side is not None:
+        raise SystemExit("--max-side needs --window")
     out = []
     for i in range(0, len(files), args.bs):
         chunk = files[i:i + args.bs]
