@@ -1860,6 +1860,23 @@ def roi_resample_v_norm(tmp: torch.Tensor, desc_host: torch.Tensor, desc: torch.
 OVERLAY_MAX_SIDE = 16384
 
 
+def _cuda_operands(fname: str, tensors, ref: torch.Tensor, strided=()) -> None:
+    """The operand contract of the overlay and dense-map wrappers: cuda tensor, dtype, contiguous (row-strided for the names in
+    `strided`), on `ref`'s device - each refusal a ValueError that names the operand."""
+    for t, name, dt in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{fname}: {name} must be a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != dt:
+            raise ValueError(f"{fname}: {name} must be {dt}, got {t.dtype}")
+        if name in strided:
+            if t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"{fname}: {name} must be 2-D with inner stride 1, got shape {tuple(t.shape)} strides {t.stride()}")
+        elif not t.is_contiguous():
+            raise ValueError(f"{fname}: {name} must be contiguous, got shape {tuple(t.shape)} strides {t.stride()}")
+        if t.device != ref.device:
+            raise ValueError(f"{fname}: {name} is on {t.device}, {tensors[0][1]} on {ref.device}")
+
+
 def relevance_overlay(rel: torch.Tensor, images: torch.Tensor, lut: torch.Tensor, size: int, out: torch.Tensor,
                       map_out: Optional[torch.Tensor] = None) -> None:
     """N relevance overlays in one launch (include/cclip_hip.h, cclip_relevance_overlay): rel fp32 [N, g*g], images fp32
@@ -1869,15 +1886,7 @@ def relevance_overlay(rel: torch.Tensor, images: torch.Tensor, lut: torch.Tensor
     tensors = [(rel, "rel", torch.float32), (images, "images", torch.float32), (lut, "lut", torch.float32), (out, "out", torch.uint8)]
     if map_out is not None:
         tensors.append((map_out, "map_out", torch.float32))
-    for t, name, dt in tensors:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"relevance_overlay: {name} must be a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
-        if t.dtype != dt:
-            raise ValueError(f"relevance_overlay: {name} must be {dt}, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"relevance_overlay: {name} must be contiguous, got shape {tuple(t.shape)} strides {t.stride()}")
-        if t.device != rel.device:
-            raise ValueError(f"relevance_overlay: {name} is on {t.device}, rel on {rel.device}")
+    _cuda_operands("relevance_overlay", tensors, rel)
     if rel.dim() != 2 or rel.shape[0] < 1:
         raise ValueError(f"relevance_overlay: rel must be [N, g*g] with N >= 1, got {tuple(rel.shape)}")
     N, P = rel.shape
@@ -1906,23 +1915,6 @@ def relevance_overlay(rel: torch.Tensor, images: torch.Tensor, lut: torch.Tensor
 DENSE_MAX_CLASSES, DENSE_MAX_EMBED = 255, 1024
 
 
-def _dense_operands(fname: str, tensors, ref: torch.Tensor, strided=()) -> None:
-    """The operand contract of the dense-map wrappers: cuda tensor, dtype, contiguous (row-strided for the names in `strided`),
-    on `ref`'s device - each refusal a ValueError that names the operand."""
-    for t, name, dt in tensors:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"{fname}: {name} must be a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
-        if t.dtype != dt:
-            raise ValueError(f"{fname}: {name} must be {dt}, got {t.dtype}")
-        if name in strided:
-            if t.dim() != 2 or t.stride(1) != 1:
-                raise ValueError(f"{fname}: {name} must be 2-D with inner stride 1, got shape {tuple(t.shape)} strides {t.stride()}")
-        elif not t.is_contiguous():
-            raise ValueError(f"{fname}: {name} must be contiguous, got shape {tuple(t.shape)} strides {t.stride()}")
-        if t.device != ref.device:
-            raise ValueError(f"{fname}: {name} is on {t.device}, {tensors[0][1]} on {ref.device}")
-
-
 def dense_class_probs(feat: torch.Tensor, text: torch.Tensor, scale: float, patches: int, probs: torch.Tensor,
                       logits_out: Optional[torch.Tensor] = None) -> None:
     """Per-patch class probabilities (include/cclip_hip.h, cclip_dense_class_probs): feat fp32 [B * patches, E] (rows may be
@@ -1933,7 +1925,7 @@ def dense_class_probs(feat: torch.Tensor, text: torch.Tensor, scale: float, patc
     tensors = [(feat, "feat", torch.float32), (text, "text", torch.float32), (probs, "probs", torch.float32)]
     if logits_out is not None:
         tensors.append((logits_out, "logits_out", torch.float32))
-    _dense_operands(fname, tensors, feat, strided=("feat",))
+    _cuda_operands(fname, tensors, feat, strided=("feat",))
     if text.dim() != 2 or text.shape[1] != feat.shape[1]:
         raise ValueError(f"{fname}: text must be [C, {feat.shape[1]}], got {tuple(text.shape)}")
     M, E = feat.shape
@@ -1959,6 +1951,27 @@ def dense_class_probs(feat: torch.Tensor, text: torch.Tensor, scale: float, patc
                                       c_float(float(scale)), _p(probs), _p(logits_out), _stream()), "cclip_dense_class_probs")
 
 
+def _label_outputs(fname: str, shape, labels, conf, cover, overlay, palette, photo, alpha8) -> None:
+    """The output side of dense_label_map and dense_stitch, `shape` = (B, S, S) or (H, W): labels, conf and (when given) cover of
+    that shape, overlay and photo of that shape + [3], palette [256, 3] with an overlay and neither it nor a photo without,
+    alpha8 in [0, 256]."""
+    for t, name in ((labels, "labels"), (conf, "conf"), (cover, "cover")):
+        if t is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{fname}: {name} must be {list(shape)}, got {tuple(t.shape)}")
+    if overlay is None and (photo is not None or palette is not None):
+        raise ValueError(f"{fname}: palette and photo are inputs of the overlay; give overlay too")
+    if overlay is not None:
+        pic = [*shape, 3]
+        if palette is None or tuple(palette.shape) != (256, 3):
+            raise ValueError(f"{fname}: palette must be uint8 [256, 3], got {None if palette is None else tuple(palette.shape)}")
+        if tuple(overlay.shape) != tuple(pic):
+            raise ValueError(f"{fname}: overlay must be {pic}, got {tuple(overlay.shape)}")
+        if photo is not None and tuple(photo.shape) != tuple(pic):
+            raise ValueError(f"{fname}: photo must be {pic} (already at the output size), got {tuple(photo.shape)}")
+    if int(alpha8) != alpha8 or not 0 <= alpha8 <= 256:
+        raise ValueError(f"{fname}: alpha8 must be an integer in [0, 256], got {alpha8}")
+
+
 def dense_label_map(probs: torch.Tensor, size: int, labels: torch.Tensor, conf: torch.Tensor, *, min_conf: float = 0.0,
                     overlay: Optional[torch.Tensor] = None, palette: Optional[torch.Tensor] = None,
                     photo: Optional[torch.Tensor] = None, alpha8: int = 256) -> None:
@@ -1972,7 +1985,7 @@ def dense_label_map(probs: torch.Tensor, size: int, labels: torch.Tensor, conf: 
     for t, name in ((overlay, "overlay"), (palette, "palette"), (photo, "photo")):
         if t is not None:
             tensors.append((t, name, torch.uint8))
-    _dense_operands(fname, tensors, probs)
+    _cuda_operands(fname, tensors, probs)
     if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
         raise ValueError(f"{fname}: probs must be [B, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
     B, C, g, _ = probs.shape
@@ -1981,21 +1994,7 @@ def dense_label_map(probs: torch.Tensor, size: int, labels: torch.Tensor, conf: 
     if int(size) != size or not 1 <= size <= OVERLAY_MAX_SIDE or g > OVERLAY_MAX_SIDE:
         raise ValueError(f"{fname}: size {size}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
     size = int(size)
-    if tuple(labels.shape) != (B, size, size):
-        raise ValueError(f"{fname}: labels must be [{B}, {size}, {size}], got {tuple(labels.shape)}")
-    if tuple(conf.shape) != (B, size, size):
-        raise ValueError(f"{fname}: conf must be [{B}, {size}, {size}], got {tuple(conf.shape)}")
-    if overlay is None and (photo is not None or palette is not None):
-        raise ValueError(f"{fname}: palette and photo are inputs of the overlay; give overlay too")
-    if overlay is not None:
-        if palette is None or tuple(palette.shape) != (256, 3):
-            raise ValueError(f"{fname}: palette must be uint8 [256, 3], got {None if palette is None else tuple(palette.shape)}")
-        if tuple(overlay.shape) != (B, size, size, 3):
-            raise ValueError(f"{fname}: overlay must be [{B}, {size}, {size}, 3], got {tuple(overlay.shape)}")
-        if photo is not None and tuple(photo.shape) != (B, size, size, 3):
-            raise ValueError(f"{fname}: photo must be [{B}, {size}, {size}, 3] (already at the output size), got {tuple(photo.shape)}")
-    if int(alpha8) != alpha8 or not 0 <= alpha8 <= 256:
-        raise ValueError(f"{fname}: alpha8 must be an integer in [0, 256], got {alpha8}")
+    _label_outputs(fname, (B, size, size), labels, conf, None, overlay, palette, photo, alpha8)
     check(lib.cclip_dense_label_map(_p(probs), c_int(B), c_int(C), c_int(g), c_int(size), c_float(float(min_conf)), _p(labels),
                                     _p(conf), _p(palette), _p(photo), c_int(int(alpha8)), _p(overlay), _stream()),
           "cclip_dense_label_map")
@@ -2020,7 +2019,7 @@ def dense_stitch(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: i
     for t, name in ((cover, "cover"), (overlay, "overlay"), (palette, "palette"), (photo, "photo")):
         if t is not None:
             tensors.append((t, name, torch.uint8))
-    _dense_operands(fname, tensors, probs)
+    _cuda_operands(fname, tensors, probs)
     if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
         raise ValueError(f"{fname}: probs must be [K, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
     K, C, g, _ = probs.shape
@@ -2034,23 +2033,7 @@ def dense_stitch(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: i
             or g > OVERLAY_MAX_SIDE:
         raise ValueError(f"{fname}: height {height}, width {width}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
     H, W = int(height), int(width)
-    if tuple(labels.shape) != (H, W):
-        raise ValueError(f"{fname}: labels must be [{H}, {W}], got {tuple(labels.shape)}")
-    if tuple(conf.shape) != (H, W):
-        raise ValueError(f"{fname}: conf must be [{H}, {W}], got {tuple(conf.shape)}")
-    if cover is not None and tuple(cover.shape) != (H, W):
-        raise ValueError(f"{fname}: cover must be [{H}, {W}], got {tuple(cover.shape)}")
-    if overlay is None and (photo is not None or palette is not None):
-        raise ValueError(f"{fname}: palette and photo are inputs of the overlay; give overlay too")
-    if overlay is not None:
-        if palette is None or tuple(palette.shape) != (256, 3):
-            raise ValueError(f"{fname}: palette must be uint8 [256, 3], got {None if palette is None else tuple(palette.shape)}")
-        if tuple(overlay.shape) != (H, W, 3):
-            raise ValueError(f"{fname}: overlay must be [{H}, {W}, 3], got {tuple(overlay.shape)}")
-        if photo is not None and tuple(photo.shape) != (H, W, 3):
-            raise ValueError(f"{fname}: photo must be [{H}, {W}, 3] (already at the output size), got {tuple(photo.shape)}")
-    if int(alpha8) != alpha8 or not 0 <= alpha8 <= 256:
-        raise ValueError(f"{fname}: alpha8 must be an integer in [0, 256], got {alpha8}")
+    _label_outputs(fname, (H, W), labels, conf, cover, overlay, palette, photo, alpha8)
     if probs.data_ptr() % 4 or conf.data_ptr() % 4 or boxes.data_ptr() % 4:
         raise ValueError(f"{fname}: probs, conf and boxes must start on a 4-byte boundary")
     check(lib.cclip_dense_stitch(_p(probs), c_int(K), c_int(C), c_int(g), _p(boxes), c_int(H), c_int(W), c_float(float(min_conf)),

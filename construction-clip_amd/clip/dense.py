@@ -53,6 +53,23 @@ def dense_features(model, image: torch.Tensor, mode: str = "value") -> torch.Ten
     return model.encode_image_dense(image, mode=mode)
 
 
+def _area_fractions(labels: torch.Tensor, n_classes: int) -> torch.Tensor:
+    """fp64 [..., C + 1] of uint8 labels [..., H, W]: per map the share of pixels of every class, "none" (255) last.  The counts
+    are integers (scatter_add_ of ones), each divided once by H * W: a map's shares sum to 1."""
+    n = labels.shape[-2] * labels.shape[-1]
+    lab = labels.reshape(-1, n).long()
+    lab = torch.where(lab == NONE_LABEL, torch.full_like(lab, n_classes), lab)
+    counts = torch.zeros(lab.shape[0], n_classes + 1, device=lab.device, dtype=torch.long)
+    counts.scatter_add_(1, lab, torch.ones_like(lab))
+    return (counts.double() / n).reshape(*labels.shape[:-2], n_classes + 1)
+
+
+def _top_classes(fractions: torch.Tensor) -> List[Optional[int]]:
+    """per row of area fractions [..., C + 1] the class with the largest area, None when no pixel has a class"""
+    fr = fractions.reshape(-1, fractions.shape[-1])[:, :-1].cpu()
+    return [int(r.argmax()) if float(r.max()) > 0 else None for r in fr]
+
+
 @dataclass
 class DenseResult:
     probs: torch.Tensor                  # fp32 [B, C, g, g]
@@ -70,55 +87,25 @@ class DenseResult:
         at the map's size) with weight a8 / 256, a8 = round(256 alpha), as (photo (256 - a8) + colour a8 + 128) >> 8.  The labels
         and conf are recomputed by the same launch and come out as they are.  A result of segment(size=(height, width)) works the
         same way, S, S read as height, width: one dense_stitch launch per image."""
-        B, S = self.labels.shape[0], self.labels.shape[1]
-        dev = self.probs.device
-        if self.labels.shape[2] != S:
-            return self._overlay_rect(photo, alpha, palette)
-        if not 0.0 <= alpha <= 1.0:
-            raise ValueError(f"overlay: alpha must lie in [0, 1], got {alpha}")
-        pal = default_palette(self.n_classes) if palette is None else palette
-        if not isinstance(pal, torch.Tensor) or pal.dtype != torch.uint8 or tuple(pal.shape) != (256, 3):
-            raise ValueError("overlay: palette must be a uint8 [256, 3] tensor")
-        if photo is not None:
-            if not isinstance(photo, torch.Tensor) or photo.dtype != torch.uint8:
-                raise ValueError("overlay: photo must be a uint8 tensor [B, S, S, 3] or [S, S, 3]")
-            if photo.dim() == 3:
-                photo = photo.unsqueeze(0).expand(B, -1, -1, -1)
-            if tuple(photo.shape) != (B, S, S, 3):
-                raise ValueError(f"overlay: photo must be [{B}, {S}, {S}, 3] (resize it to the map first), got {tuple(photo.shape)}")
-            photo = photo.to(dev).contiguous()
-        out = torch.empty(B, S, S, 3, device=dev, dtype=torch.uint8)
-        ops.dense_label_map(self.probs, S, torch.empty_like(self.labels), torch.empty_like(self.conf), min_conf=self.min_conf,
-                            overlay=out, palette=pal.to(dev).contiguous(), photo=photo, alpha8=int(round(256 * alpha)))
-        return out
-
-    def _overlay_rect(self, photo, alpha, palette) -> torch.Tensor:
         B, H, W = self.labels.shape
         dev = self.probs.device
         pal, photo, a8 = _overlay_inputs(alpha, palette, self.n_classes, photo, (B, H, W, 3), dev)
         out = torch.empty(B, H, W, 3, device=dev, dtype=torch.uint8)
-        box = _device_boxes(np.array([[0, 0, W, H]]), dev)
-        lab, conf = torch.empty(H, W, device=dev, dtype=torch.uint8), torch.empty(H, W, device=dev, dtype=torch.float32)
-        for b in range(B):
-            ops.dense_stitch(self.probs[b:b + 1], box, H, W, lab, conf, min_conf=self.min_conf, overlay=out[b], palette=pal,
-                             photo=None if photo is None else photo[b], alpha8=a8)
+        lab, conf = torch.empty_like(self.labels), torch.empty_like(self.conf)
+        if H != W:
+            _stretch_maps(self.probs, lab, conf, self.min_conf, overlay=out, palette=pal, photo=photo, alpha8=a8)
+        else:
+            ops.dense_label_map(self.probs, H, lab, conf, min_conf=self.min_conf, overlay=out, palette=pal, photo=photo, alpha8=a8)
         return out
 
     def area_fractions(self) -> torch.Tensor:
-        """fp64 [B, C + 1]: the share of pixels per class, "none" last.  Pixel COUNTS are integers (bincount), each divided once
-        by S * S: a row sums to 1."""
-        B = self.labels.shape[0]
-        C = self.n_classes
-        lab = self.labels.reshape(B, -1).long()
-        lab = torch.where(lab == NONE_LABEL, torch.full_like(lab, C), lab)
-        counts = torch.zeros(B, C + 1, device=lab.device, dtype=torch.long)
-        counts.scatter_add_(1, lab, torch.ones_like(lab))
-        return counts.double() / lab.shape[1]
+        """fp64 [B, C + 1]: the share of pixels per class, "none" last.  Pixel COUNTS are integers, each divided once by S * S:
+        a row sums to 1."""
+        return _area_fractions(self.labels, self.n_classes)
 
     def top_class(self) -> List[Optional[int]]:
         """per image the class with the largest area, None when no pixel has a class"""
-        fr = self.area_fractions()[:, :-1].cpu()
-        return [int(r.argmax()) if float(r.max()) > 0 else None for r in fr]
+        return _top_classes(self.area_fractions())
 
 
 def class_features(model, classes: Union[torch.Tensor, Sequence[str]], tokenize: Optional[Callable] = None):
@@ -166,9 +153,7 @@ def segment(model, image: torch.Tensor, classes: Union[torch.Tensor, Sequence[st
     if B > 0:
         ops.dense_class_probs(feats.view(B * g * g, E), text, scale, g * g, probs.view(B, C, g * g))
         if rect:
-            box = _device_boxes(np.array([[0, 0, W, H]]), dev)
-            for b in range(B):
-                ops.dense_stitch(probs[b:b + 1], box, H, W, labels[b], conf[b], min_conf=min_conf)
+            _stretch_maps(probs, labels, conf, min_conf)
         else:
             ops.dense_label_map(probs, H, labels, conf, min_conf=min_conf)
     return DenseResult(probs=probs, labels=labels, conf=conf, class_names=names, min_conf=float(min_conf))
@@ -197,6 +182,16 @@ def _overlay_inputs(alpha, palette, n_classes, photo, shape, dev):
             raise ValueError(f"overlay: photo must be {list(shape)} (resize it to the map first), got {tuple(photo.shape)}")
         photo = photo.to(dev).contiguous()
     return pal.to(dev).contiguous(), photo, int(round(256 * alpha))
+
+
+def _stretch_maps(probs, labels, conf, min_conf, overlay=None, palette=None, photo=None, alpha8=256) -> None:
+    """probs [B, C, g, g] stretched over labels / conf [B, H, W] (and overlay / photo [B, H, W, 3]), each axis with its own scale:
+    one ops.dense_stitch launch per image, one window covering the map."""
+    B, H, W = labels.shape
+    box = _device_boxes(np.array([[0, 0, W, H]]), probs.device)
+    for b in range(B):
+        ops.dense_stitch(probs[b:b + 1], box, H, W, labels[b], conf[b], min_conf=min_conf, overlay=None if overlay is None else overlay[b],
+                         palette=palette, photo=None if photo is None else photo[b], alpha8=alpha8)
 
 
 def _plan_one(width: int, height: int, window: int, stride: Optional[int]) -> np.ndarray:
@@ -315,15 +310,11 @@ class PhotoDenseResult:
 
     def area_fractions(self) -> torch.Tensor:
         """fp64 [C + 1]: the share of pixels per class, "none" last; integer counts divided once by H * W: they sum to 1."""
-        C = self.n_classes
-        lab = self.labels.reshape(-1).long()
-        lab = torch.where(lab == NONE_LABEL, torch.full_like(lab, C), lab)
-        return torch.bincount(lab, minlength=C + 1).double() / lab.numel()
+        return _area_fractions(self.labels, self.n_classes)
 
     def top_class(self) -> Optional[int]:
         """the class with the largest area, None when no pixel has a class"""
-        fr = self.area_fractions()[:-1].cpu()
-        return int(fr.argmax()) if float(fr.max()) > 0 else None
+        return _top_classes(self.area_fractions())[0]
 
     def class_boxes(self, c: int, min_area: int = 1) -> List[Tuple[int, int, int, int]]:
         """bounding boxes (x0, y0, x1, y1) of the 4-connected components of label c (`label_boxes`): what classify_regions takes"""

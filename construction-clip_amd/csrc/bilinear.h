@@ -1,7 +1,8 @@
 // F.interpolate(mode="bilinear", align_corners=False) of one fp32 plane, as the pixel kernels take it (relevance_overlay.hip,
-// dense_classes.hip): s = max((i + 0.5) * L / S - 0.5, 0), i0 = floor(s), i1 = min(i0 + 1, L - 1), weight s - i0; separable in
-// y and x; the identity when L == S.  Include it BELOW the file's `#pragma clang fp contract(off)`: both kernels need a sample
-// to come out the same wherever the expression is inlined.
+// dense_classes.hip, dense_stitch.hip): s = max((i + 0.5) * L / S - 0.5, 0), i0 = floor(s), i1 = min(i0 + 1, L - 1), weight
+// s - i0; separable in y and x; the identity when L == S.  Include it BELOW the file's `#pragma clang fp contract(off)`: every
+// kernel needs a sample to come out the same wherever the expression is inlined.  (What the two dense kernels do with their
+// samples - pick a label, store it, paint it - is label_pixels.h.)
 #pragma once
 
 struct ov_axis { int i0, i1; float w; };

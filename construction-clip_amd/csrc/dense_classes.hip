@@ -16,12 +16,10 @@
 // cclip_dense_label_map.  probs [B][C][g][g] -> per output pixel of the S x S picture the bilinear sample u_c of every class map
 // (bilinear.h: F.interpolate(mode="bilinear", align_corners=False), the source coordinate formed in integers - conf is held to
 // 1e-6 of float64, which the fp32 coordinate product misses at grid 24), conf = max_c u_c, label = the FIRST class that reaches
-// it (a later class replaces the best only when strictly greater), 255 when conf < min_conf; and optionally the picture:
-// palette[label], or (photo * (256 - a8) + palette[label] * a8 + 128) >> 8 per byte over a photo of the output size - integer
-// arithmetic, exact given the labels.  A thread owns FOUR consecutive pixels of the flat [B * S * S] stream: its labels are one
-// dword, its conf one float4, its picture bytes three dwords - from dword-aligned addresses whatever S is (picture b starts at
-// byte b * S * S, 25 for S = 5), as long as the buffer itself is aligned; the last, partial group and a misaligned buffer are
-// stored element by element.  Vector stores only, no atomics.
+// it (a later class replaces the best only when strictly greater), 255 when conf < min_conf; and optionally the picture, the
+// label's palette colour alone or blended in integers over a photo of the output size.  The selection rule, the ownership of
+// the flat [B * S * S] stream (four consecutive pixels per thread), every store and the picture's formula are label_pixels.h's,
+// shared with dense_stitch.hip: the kernel here is the per-pixel class loop and one call.
 #include "cclip_common.h"
 #include "../../include/cclip_hip.h"
 
@@ -29,7 +27,7 @@
 #define DC_ROWS (DC_THREADS / 64)                           // feature rows per work-group: one per wave
 #define DC_TILE 16                                          // classes per LDS tile at E <= 512
 #define DC_TILE_FLOATS 8192                                 // 32 KB
-#define DC_MAX_C 255
+#define DC_MAX_C 255                                        // label_pixels.h's cap (asserted below), inside the 4 * 64 logit slots
 #define DC_MAX_E 1024
 
 __device__ __forceinline__ float dc_dot4(float4 a, float4 b, float acc) {
@@ -141,31 +139,27 @@ extern "C" int cclip_dense_class_probs(const float* feat, int64_t ldf, int64_t M
 // ---- label map ---------------------------------------------------------------------------------
 #pragma clang fp contract(off)
 #include "bilinear.h"
+#include "label_pixels.h"
 
-#define DL_THREADS 256
+static_assert(DC_MAX_C == LP_MAX_C, "dense_class_probs must not make more classes than a label can name");
 
 struct dl_args {
   const float* probs; int B, C, g, S;
-  float min_conf;
-  uint8_t* labels; float* conf;
-  const uint8_t* palette; const uint8_t* photo; int a8; uint8_t* overlay;   // palette / overlay may be null, photo too
+  lp_out out;
 };
 
-__global__ __launch_bounds__(DL_THREADS) void dense_label_map_kernel(const dl_args a) {
+__global__ __launch_bounds__(LP_THREADS) void dense_label_map_kernel(const dl_args a) {
   __shared__ unsigned char pal[256 * 3];
-  const int tid = threadIdx.x;
-  if (a.overlay) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pal[tid + DL_THREADS * i] = a.palette[tid + DL_THREADS * i];
-  }
+  lp_load_palette(pal, a.out);
   __syncthreads();
   const long plane = (long)a.S * a.S, npix = plane * a.B;
-  const long p0 = ((long)blockIdx.x * DL_THREADS + tid) * 4;
+  const long p0 = lp_first_pixel();
   if (p0 >= npix) return;
-  const int n = npix - p0 < 4 ? (int)(npix - p0) : 4;       // pixels of this thread: 4, fewer in the stream's last group
+  const int n = lp_live(p0, npix);
   const long gg = (long)a.g * a.g;
 
   unsigned lab[4];
+  const unsigned nocov[4] = {0u, 0u, 0u, 0u};               // (a.out.cover is null: never stored)
   float cf[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -175,82 +169,27 @@ __global__ __launch_bounds__(DL_THREADS) void dense_label_map_kernel(const dl_ar
       const int y = (int)(r / a.S), x = (int)(r - (long)y * a.S);
       const ov_axis ay = ov_coord_exact(y, a.g, a.S), ax = ov_coord_exact(x, a.g, a.S);
       const float* src = a.probs + b * a.C * gg;
-      float best = ov_bil(src, a.g, ay, ax);
-      int arg = 0;
-      for (int c = 1; c < a.C; ++c) {
-        const float u = ov_bil(src + c * gg, a.g, ay, ax);
-        if (u > best) { best = u; arg = c; }                // strictly greater: an exact tie stays with the lower class
-      }
-      lab[i] = best < a.min_conf ? 255u : (unsigned)arg;
-      cf[i] = best;
+      lp_pick pk = lp_seed(ov_bil(src, a.g, ay, ax));
+      for (int c = 1; c < a.C; ++c) lp_offer(pk, c, ov_bil(src + c * gg, a.g, ay, ax));
+      lab[i] = lp_label(pk, a.out.min_conf);
+      cf[i] = pk.best;
     }
   }
-
-  const bool whole = n == 4;
-  uint8_t* lo = a.labels + p0;
-  if (whole && !((uintptr_t)a.labels & 3)) {
-    *(unsigned*)lo = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < n) lo[i] = (uint8_t)lab[i];
-  }
-  float* co = a.conf + p0;
-  if (whole && !((uintptr_t)a.conf & 15)) {
-    *(float4*)co = make_float4(cf[0], cf[1], cf[2], cf[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < n) co[i] = cf[i];
-  }
-  if (!a.overlay) return;
-
-  // the 12 picture bytes of the four pixels as three little-endian dwords
-  unsigned w[3] = {0u, 0u, 0u};
-  if (a.photo) {
-    const uint8_t* ph = a.photo + 3 * p0;
-    if (whole && !((uintptr_t)a.photo & 3)) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) w[k] = ((const unsigned*)ph)[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 12; ++k)
-        if (k < 3 * n) w[k >> 2] |= (unsigned)ph[k] << (8 * (k & 3));
-    }
-  }
-  unsigned o[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const unsigned col = pal[lab[k / 3] * 3 + k % 3];
-    const unsigned src = (w[k >> 2] >> (8 * (k & 3))) & 255u;
-    const unsigned v = a.photo ? (src * (unsigned)(256 - a.a8) + col * (unsigned)a.a8 + 128u) >> 8 : col;
-    o[k >> 2] |= v << (8 * (k & 3));
-  }
-  uint8_t* oo = a.overlay + 3 * p0;
-  if (whole && !((uintptr_t)a.overlay & 3)) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ((unsigned*)oo)[k] = o[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 12; ++k)
-      if (k < 3 * n) oo[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
-  }
+  lp_store_quad(a.out, pal, p0, n, lab, cf, nocov);
 }
 
 extern "C" int cclip_dense_label_map(const float* probs, int32_t B, int32_t C, int32_t g, int32_t S, float min_conf, uint8_t* labels,
                                      float* conf, const uint8_t* palette, const uint8_t* photo, int32_t a8, uint8_t* overlay,
                                      hipStream_t stream) {
-  if (!probs || !labels || !conf || B < 1 || C < 1 || C > DC_MAX_C || g < 1 || g > CCLIP_OVERLAY_MAX_SIDE || S < 1 ||
-      S > CCLIP_OVERLAY_MAX_SIDE)
+  if (!probs || B < 1 || C < 1 || C > LP_MAX_C || g < 1 || g > CCLIP_OVERLAY_MAX_SIDE || S < 1 || S > CCLIP_OVERLAY_MAX_SIDE)
     return CCLIP_ERR_ARG;
-  if ((overlay && !palette) || (photo && !overlay) || a8 < 0 || a8 > 256) return CCLIP_ERR_ARG;
-  if (((uintptr_t)probs | (uintptr_t)conf) & 3) return CCLIP_ERR_ARG;
-  const int64_t npix = (int64_t)B * S * S;
-  const int64_t blocks = (npix + 4 * DL_THREADS - 1) / (4 * DL_THREADS);
-  if (blocks > 0x7fffffff) return CCLIP_ERR_ARG;
   dl_args a;
-  a.probs = probs; a.B = B; a.C = C; a.g = g; a.S = S; a.min_conf = min_conf; a.labels = labels; a.conf = conf;
-  a.palette = palette; a.photo = photo; a.a8 = a8; a.overlay = overlay;
-  hipLaunchKernelGGL(dense_label_map_kernel, dim3((unsigned)blocks), dim3(DL_THREADS), 0, stream, a);
+  a.probs = probs; a.B = B; a.C = C; a.g = g; a.S = S;
+  a.out = lp_out{labels, conf, nullptr, palette, photo, a8, overlay, min_conf};
+  if (!lp_out_ok(a.out) || ((uintptr_t)probs & 3)) return CCLIP_ERR_ARG;
+  const int64_t npix = (int64_t)B * S * S;
+  const int64_t blocks = (npix + LP_PIX - 1) / LP_PIX;
+  if (blocks > 0x7fffffff) return CCLIP_ERR_ARG;
+  hipLaunchKernelGGL(dense_label_map_kernel, dim3((unsigned)blocks), dim3(LP_THREADS), 0, stream, a);
   return cclip_launch_status();
 }

@@ -10,12 +10,12 @@
 // makes the kernel read outside probs.  With the n covering windows k1 < k2 < .. in ascending k
 //     u_c = ((s_k1c + s_k2c) + ..) / (float)n       seeded with the first sample, fp32 adds left to right, ONE division (n = 1 too)
 //     conf = max_c u_c, label = the lowest class reaching it (strictly greater replaces), 255 when conf < min_conf;
-//     n = 0: label 255, conf 0;  cover = min(n, 255);  picture bytes: dense_classes.hip's integer formula on the label.
-// For K = 1, H = W = S and box (0, 0, S, S) this is dense_label_map's arithmetic, bit for bit (x / 1.0f == x).
+//     n = 0: label 255, conf 0;  cover = min(n, 255);  picture bytes: label_pixels.h's integer formula on the label.
+// For K = 1, H = W = S and box (0, 0, S, S) this is dense_label_map's arithmetic, bit for bit (x / 1.0f == x): the selection
+// rule, the ownership of the flat [H * W] stream (four consecutive pixels per thread) and every store are label_pixels.h's,
+// shared with dense_classes.hip.
 //
-// Ownership is dense_label_map's: a thread owns FOUR consecutive pixels of the flat [H * W] stream (one dword of labels and of
-// cover, one float4 of conf, three dwords of picture), the last partial group and misaligned buffers go element by element.  A
-// work-group's 1024 pixels lie in a band of rows ylo .. yhi (inside columns xlo .. xhi when the band is one row).  The group first
+// A work-group's 1024 pixels lie in a band of rows ylo .. yhi (inside columns xlo .. xhi when the band is one row).  The group first
 // scans the K boxes once, 256 at a time, and compacts IN ASCENDING k (wave ballot + a prefix over the four waves) the windows
 // that meet the band into an LDS list of DS_LIST entries; a thread then walks that list, not all K.  When more than DS_LIST
 // windows meet the band the group walks all K boxes from global memory instead (the same code, the same order, the same bytes).
@@ -28,20 +28,16 @@
 
 #pragma clang fp contract(off)
 #include "bilinear.h"
+#include "label_pixels.h"
 
-#define DS_THREADS 256
-#define DS_PIX (4 * DS_THREADS)                             // pixels per work-group
 #define DS_LIST 512                                         // LDS list entries: 10 KB
 #define DS_FAST 4                                           // covering windows per pixel whose axes stay in registers
-#define DS_MAX_C 255
 #define DS_MAX_K 65535
 
 struct ds_args {
   const float* probs; int K, C, g;
   const int* boxes; int H, W;
-  float min_conf;
-  uint8_t* labels; float* conf; uint8_t* cover;
-  const uint8_t* palette; const uint8_t* photo; int a8; uint8_t* overlay;
+  lp_out out;
 };
 
 struct ds_box { int x0, y0, x1, y1; };
@@ -63,20 +59,17 @@ __device__ __forceinline__ ds_box ds_load_box(const int* __restrict__ boxes, int
   return b;
 }
 
-__global__ __launch_bounds__(DS_THREADS) void dense_stitch_kernel(const ds_args a) {
+__global__ __launch_bounds__(LP_THREADS) void dense_stitch_kernel(const ds_args a) {
   __shared__ unsigned char pal[256 * 3];
   __shared__ ds_box lbox[DS_LIST];
   __shared__ int lk[DS_LIST];
-  __shared__ int wcnt[DS_THREADS / 64];
+  __shared__ int wcnt[LP_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (a.overlay) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pal[tid + DS_THREADS * i] = a.palette[tid + DS_THREADS * i];
-  }
+  lp_load_palette(pal, a.out);                              // (the scan's barriers come before any read of pal)
 
   const long npix = (long)a.H * a.W;
-  const long g0 = (long)blockIdx.x * DS_PIX;                // first pixel of the group; < npix by the grid's size
-  const long g1 = (g0 + DS_PIX < npix ? g0 + DS_PIX : npix) - 1;
+  const long g0 = (long)blockIdx.x * LP_PIX;                // first pixel of the group; < npix by the grid's size
+  const long g1 = (g0 + LP_PIX < npix ? g0 + LP_PIX : npix) - 1;
   const int ylo = (int)(g0 / a.W), yhi = (int)(g1 / a.W);
   const bool one_row = ylo == yhi;
   const int xlo = one_row ? (int)(g0 - (long)ylo * a.W) : 0;
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(DS_THREADS) void dense_stitch_kernel(const ds_args 
 
   // the windows that meet the band, in ascending k (all quantities block-uniform)
   int total = 0;
-  for (int base = 0; base < a.K; base += DS_THREADS) {
+  for (int base = 0; base < a.K; base += LP_THREADS) {
     const int k = base + tid;
     bool hit = false;
     ds_box b = {0, 0, 0, 0};
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(DS_THREADS) void dense_stitch_kernel(const ds_args 
     int pos = total + __popcll(m & ((1ull << lane) - 1ull));
     int sum = 0;
 #pragma unroll
-    for (int w = 0; w < DS_THREADS / 64; ++w) {
+    for (int w = 0; w < LP_THREADS / 64; ++w) {
       const int c = wcnt[w];
       if (w < wave) pos += c;
       sum += c;
@@ -110,9 +103,9 @@ __global__ __launch_bounds__(DS_THREADS) void dense_stitch_kernel(const ds_args 
   const bool listed = total <= DS_LIST;                     // otherwise: walk all K boxes from global memory
   const int L = listed ? total : a.K;
 
-  const long p0 = g0 + (long)tid * 4;
+  const long p0 = lp_first_pixel();                         // g0 + 4 tid
   if (p0 >= npix) return;
-  const int n_px = npix - p0 < 4 ? (int)(npix - p0) : 4;    // pixels of this thread: 4, fewer in the stream's last group
+  const int n_px = lp_live(p0, npix);
   const long gg = (long)a.g * a.g, cgg = gg * a.C;
 
   unsigned lab[4], cov[4];
@@ -148,8 +141,7 @@ __global__ __launch_bounds__(DS_THREADS) void dense_stitch_kernel(const ds_args 
     if (n == 0) continue;
 
     const float fn = (float)n;
-    float best = 0.0f;
-    int arg = 0;
+    lp_pick pk = lp_seed(0.0f);
     for (int c = 0; c < a.C; ++c) {
       const float* pc = a.probs + c * gg;
       float s = ov_bil(pc + f[0].k * cgg, a.g, f[0].ay, f[0].ax);
@@ -165,88 +157,30 @@ __global__ __launch_bounds__(DS_THREADS) void dense_stitch_kernel(const ds_args 
         }
       }
       const float u = s / fn;
-      if (c == 0 || u > best) { best = u; arg = c; }        // strictly greater: an exact tie stays with the lower class
+      if (c == 0) pk = lp_seed(u);                          // class 0 seeds whatever its value, as in dense_label_map; offering
+      else lp_offer(pk, c, u);                              // it to a -inf start would part from that on a NaN or -inf sample
     }
-    lab[i] = best < a.min_conf ? 255u : (unsigned)arg;
-    cf[i] = best;
+    lab[i] = lp_label(pk, a.out.min_conf);
+    cf[i] = pk.best;
     cov[i] = n < 255 ? (unsigned)n : 255u;
   }
 
-  const bool whole = n_px == 4;
-  uint8_t* lo = a.labels + p0;
-  if (whole && !((uintptr_t)a.labels & 3)) {
-    *(unsigned*)lo = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < n_px) lo[i] = (uint8_t)lab[i];
-  }
-  if (a.cover) {
-    uint8_t* vo = a.cover + p0;
-    if (whole && !((uintptr_t)a.cover & 3)) {
-      *(unsigned*)vo = cov[0] | (cov[1] << 8) | (cov[2] << 16) | (cov[3] << 24);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < n_px) vo[i] = (uint8_t)cov[i];
-    }
-  }
-  float* co = a.conf + p0;
-  if (whole && !((uintptr_t)a.conf & 15)) {
-    *(float4*)co = make_float4(cf[0], cf[1], cf[2], cf[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < n_px) co[i] = cf[i];
-  }
-  if (!a.overlay) return;
-
-  // the 12 picture bytes of the four pixels as three little-endian dwords (dense_label_map's formula)
-  unsigned w[3] = {0u, 0u, 0u};
-  if (a.photo) {
-    const uint8_t* ph = a.photo + 3 * p0;
-    if (whole && !((uintptr_t)a.photo & 3)) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) w[k] = ((const unsigned*)ph)[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 12; ++k)
-        if (k < 3 * n_px) w[k >> 2] |= (unsigned)ph[k] << (8 * (k & 3));
-    }
-  }
-  unsigned o[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const unsigned col = pal[lab[k / 3] * 3 + k % 3];
-    const unsigned src = (w[k >> 2] >> (8 * (k & 3))) & 255u;
-    const unsigned v = a.photo ? (src * (unsigned)(256 - a.a8) + col * (unsigned)a.a8 + 128u) >> 8 : col;
-    o[k >> 2] |= v << (8 * (k & 3));
-  }
-  uint8_t* oo = a.overlay + 3 * p0;
-  if (whole && !((uintptr_t)a.overlay & 3)) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ((unsigned*)oo)[k] = o[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 12; ++k)
-      if (k < 3 * n_px) oo[k] = (uint8_t)(o[k >> 2] >> (8 * (k & 3)));
-  }
+  lp_store_quad(a.out, pal, p0, n_px, lab, cf, cov);
 }
 
 extern "C" int cclip_dense_stitch(const float* probs, int32_t K, int32_t C, int32_t g, const int32_t* boxes, int32_t H, int32_t W,
                                   float min_conf, uint8_t* labels, float* conf, uint8_t* cover, const uint8_t* palette,
                                   const uint8_t* photo, int32_t a8, uint8_t* overlay, hipStream_t stream) {
-  if (!probs || !boxes || !labels || !conf || K < 1 || K > DS_MAX_K || C < 1 || C > DS_MAX_C || g < 1 || g > CCLIP_OVERLAY_MAX_SIDE ||
-      H < 1 || H > CCLIP_OVERLAY_MAX_SIDE || W < 1 || W > CCLIP_OVERLAY_MAX_SIDE)
+  if (!probs || !boxes || K < 1 || K > DS_MAX_K || C < 1 || C > LP_MAX_C || g < 1 || g > CCLIP_OVERLAY_MAX_SIDE || H < 1 ||
+      H > CCLIP_OVERLAY_MAX_SIDE || W < 1 || W > CCLIP_OVERLAY_MAX_SIDE)
     return CCLIP_ERR_ARG;
-  if ((overlay && !palette) || (photo && !overlay) || a8 < 0 || a8 > 256) return CCLIP_ERR_ARG;
-  if (((uintptr_t)probs | (uintptr_t)conf | (uintptr_t)boxes) & 3) return CCLIP_ERR_ARG;
-  const int64_t npix = (int64_t)H * W;
-  const int64_t blocks = (npix + DS_PIX - 1) / DS_PIX;
-  if (blocks > 0x7fffffff) return CCLIP_ERR_ARG;
   ds_args a;
-  a.probs = probs; a.K = K; a.C = C; a.g = g; a.boxes = boxes; a.H = H; a.W = W; a.min_conf = min_conf;
-  a.labels = labels; a.conf = conf; a.cover = cover; a.palette = palette; a.photo = photo; a.a8 = a8; a.overlay = overlay;
-  hipLaunchKernelGGL(dense_stitch_kernel, dim3((unsigned)blocks), dim3(DS_THREADS), 0, stream, a);
+  a.probs = probs; a.K = K; a.C = C; a.g = g; a.boxes = boxes; a.H = H; a.W = W;
+  a.out = lp_out{labels, conf, cover, palette, photo, a8, overlay, min_conf};
+  if (!lp_out_ok(a.out) || (((uintptr_t)probs | (uintptr_t)boxes) & 3)) return CCLIP_ERR_ARG;
+  const int64_t npix = (int64_t)H * W;
+  const int64_t blocks = (npix + LP_PIX - 1) / LP_PIX;
+  if (blocks > 0x7fffffff) return CCLIP_ERR_ARG;
+  hipLaunchKernelGGL(dense_stitch_kernel, dim3((unsigned)blocks), dim3(LP_THREADS), 0, stream, a);
   return cclip_launch_status();
 }

@@ -1133,6 +1133,7 @@ int cclip_relevance_overlay(const float* rel, int32_t N, int32_t g, const float*
 
 /* ---- dense zero-shot maps ------------------------------------------------------------------------
  * Per-patch class probabilities and the label map / picture made from them (csrc/dense_classes.hip); all fp32, no fp16 twin.
+ * How a pixel's label is chosen, stored and painted is csrc/label_pixels.h, one writer for this kernel and cclip_dense_stitch.
  *
  * cclip_dense_class_probs: feat [M][E] with row stride ldf (floats), M = B * P patch rows, image b owns rows b P .. b P + P - 1;
  *   text [C][E] contiguous.  Neither side needs unit rows:
@@ -1175,8 +1176,8 @@ int cclip_dense_label_map(const float* probs, int32_t B, int32_t C, int32_t g, i
  *     conf   [H][W] fp32  = max_c u_c;   0 when n = 0
  *     labels [H][W] uint8 = the LOWEST class reaching conf, 255 when conf < min_conf or n = 0
  *     cover  NULL, or [H][W] uint8 = min(n, 255)
- *     overlay NULL, or uint8 [H][W][3]: cclip_dense_label_map's integer formula on the label (palette [256][3], photo NULL or
- *     uint8 [H][W][3], a8 in [0, 256]).
+ *     overlay NULL, or uint8 [H][W][3]: the integer formula stated for cclip_dense_label_map on the label (palette [256][3],
+ *     photo NULL or uint8 [H][W][3], a8 in [0, 256]) - the same code, csrc/label_pixels.h.
  *   For K = 1, H = W = S and the box (0, 0, S, S), labels, conf and overlay equal cclip_dense_label_map's bit for bit.  There is
  *   no cap on how many windows cover a pixel.  One launch, no atomics, nothing depends on the launch geometry: two calls give
  *   equal bytes.
