@@ -2041,6 +2041,77 @@ def dense_stitch(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: i
           "cclip_dense_stitch")
 
 
+COMPONENTS_GROUP = 1024
+
+
+def _component_maps(fname: str, labels, maps):
+    """The label map of the component wrappers, uint8 [B, H, W], and the per-pixel maps (t, name, dtype) of the same shape:
+    cuda tensor, dtype, contiguous, one device, then the shapes and the size limits.  Returns (B, H, W)."""
+    _cuda_operands(fname, [(labels, "labels", torch.uint8)] + [m for m in maps if m[0] is not None], labels)
+    if labels.dim() != 3 or min(labels.shape) < 1:
+        raise ValueError(f"{fname}: labels must be [B, H, W] with no empty dimension, got {tuple(labels.shape)}")
+    B, H, W = labels.shape
+    if H > OVERLAY_MAX_SIDE or W > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: height {H}, width {W}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    if B * H * W > 2 ** 31 - 1:
+        raise ValueError(f"{fname}: labels holds {B * H * W} pixels; flat indices are int32, at most {2 ** 31 - 1}")
+    for t, name, _ in maps:
+        if t is not None and tuple(t.shape) != (B, H, W):
+            raise ValueError(f"{fname}: {name} must be {[B, H, W]}, got {tuple(t.shape)}")
+    return B, H, W
+
+
+def label_components(labels: torch.Tensor, connectivity: int, root: torch.Tensor, ids: torch.Tensor, count: torch.Tensor,
+                     workspace: torch.Tensor) -> None:
+    """Connected components of a batch of label maps (include/cclip_hip.h, cclip_label_components): labels uint8 [B, H, W], 255 =
+    none, joined over 4- or 8-neighbours of equal label inside one image -> root int32 [B, H, W] (the flat index of the
+    component's first pixel, -1 for none), ids int32 [B, H, W] (0 .. n - 1 in ascending order of root, -1 for none), count int32
+    [1] (n, left on the device).  workspace: int32, at least ceil(B H W / COMPONENTS_GROUP) elements.  Contiguous cuda tensors
+    on one device; no CPU path.  Two calls give equal bytes."""
+    fname = "label_components"
+    B, H, W = _component_maps(fname, labels, [(root, "root", torch.int32), (ids, "ids", torch.int32)])
+    _cuda_operands(fname, [(labels, "labels", torch.uint8), (count, "count", torch.int32), (workspace, "workspace", torch.int32)], labels)
+    if connectivity not in (4, 8):
+        raise ValueError(f"{fname}: connectivity must be 4 or 8, got {connectivity!r}")
+    if count.numel() != 1:
+        raise ValueError(f"{fname}: count must hold one element, got {tuple(count.shape)}")
+    need = (B * H * W + COMPONENTS_GROUP - 1) // COMPONENTS_GROUP
+    if workspace.numel() < need:
+        raise ValueError(f"{fname}: workspace must hold at least {need} int32 elements, got {workspace.numel()}")
+    check(lib.cclip_label_components(_p(labels), c_int(B), c_int(H), c_int(W), c_int(int(connectivity)), _p(root), _p(ids), _p(count),
+                                     _p(workspace), c_long(workspace.numel()), _stream()), "cclip_label_components")
+
+
+def component_stats(labels: torch.Tensor, root: torch.Tensor, ids: torch.Tensor, n: int, label: torch.Tensor, image: torch.Tensor,
+                    first: torch.Tensor, area: torch.Tensor, box: torch.Tensor, *, conf: Optional[torch.Tensor] = None,
+                    qsum: Optional[torch.Tensor] = None) -> None:
+    """Per-component statistics of a labelling (include/cclip_hip.h, cclip_component_stats): labels uint8, root / ids int32
+    [B, H, W] as label_components left them and n = its count, read by the caller -> label uint8 [n], image, first, area int32
+    [n], box int32 [n, 4] (x0, y0, x1, y1; half-open, image coordinates) and, with conf fp32 [B, H, W], qsum int64 [n]: the sum of
+    the 16.16 fixed-point confidences (never negative: at most 2^44).  n = 0 launches nothing.  Contiguous cuda tensors on one
+    device; no CPU path.  Two calls give equal bytes."""
+    fname = "component_stats"
+    B, H, W = _component_maps(fname, labels, [(root, "root", torch.int32), (ids, "ids", torch.int32), (conf, "conf", torch.float32)])
+    outs = [(label, "label", torch.uint8), (image, "image", torch.int32), (first, "first", torch.int32), (area, "area", torch.int32),
+            (box, "box", torch.int32)]
+    if qsum is not None:
+        outs.append((qsum, "qsum", torch.int64))
+    _cuda_operands(fname, [(labels, "labels", torch.uint8)] + outs, labels)
+    if (conf is None) != (qsum is None):
+        raise ValueError(f"{fname}: conf and qsum go together; give both or neither")
+    if int(n) != n or not 0 <= n <= B * H * W:
+        raise ValueError(f"{fname}: n must be an integer in [0, {B * H * W}], got {n!r}")
+    n = int(n)
+    for t, name, _ in outs:
+        want = (n, 4) if name == "box" else (n,)
+        if tuple(t.shape) != want:
+            raise ValueError(f"{fname}: {name} must be {list(want)}, got {tuple(t.shape)}")
+    if n == 0:
+        return
+    check(lib.cclip_component_stats(_p(labels), _p(conf), _p(root), _p(ids), c_int(B), c_int(H), c_int(W), c_int(n), _p(label),
+                                    _p(image), _p(first), _p(area), _p(box), _p(qsum), _stream()), "cclip_component_stats")
+
+
 # --------------------------------------------------------------------------------------------
 # fp8 (e4m3) inference projections
 # --------------------------------------------------------------------------------------------

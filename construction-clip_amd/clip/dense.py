@@ -107,6 +107,16 @@ class DenseResult:
         """per image the class with the largest area, None when no pixel has a class"""
         return _top_classes(self.area_fractions())
 
+    def components(self, connectivity: int = 4) -> "ComponentsResult":
+        """the connected components of the label maps with their mean confidences (`label_components`), image by image"""
+        return label_components(self.labels, self.conf, connectivity=connectivity)
+
+    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
+                  connectivity: int = 4) -> List[dict]:
+        """one record per connected component: components(connectivity).instances(...) with this result's class names"""
+        return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
+                                                       class_names=self.class_names)
+
 
 def class_features(model, classes: Union[torch.Tensor, Sequence[str]], tokenize: Optional[Callable] = None):
     """(fp32 [C, E] class embeddings on the model's device, class names or None): a feature tensor passes through; a list of
@@ -283,6 +293,87 @@ def label_boxes(labels, c: int, min_area: int = 1) -> List[Tuple[int, int, int, 
     return [(b[0], b[1], b[2], b[3]) for _, b in sorted(comps.items()) if b[4] >= min_area]
 
 
+# ---- instances: connected components on the device ----------------------------------------------
+@dataclass
+class ComponentsResult:
+    """The connected components of a label map (`label_components`).  Component i is numbered in the order of its first pixel
+    (image by image, row-major), which is the order `label_boxes` returns boxes in."""
+    ids: torch.Tensor                    # int32, the labels' shape: the component number of every pixel, -1 = none
+    root: torch.Tensor                   # int32, the labels' shape: the flat index of the component's first pixel, -1 = none
+    n: int
+    label: torch.Tensor                  # uint8 [n] (CPU): the class
+    image: torch.Tensor                  # int32 [n] (CPU): the batch index
+    first: torch.Tensor                  # int32 [n] (CPU): the flat index of the first pixel
+    area: torch.Tensor                   # int32 [n] (CPU): pixels
+    boxes: torch.Tensor                  # int32 [n, 4] (CPU): (x0, y0, x1, y1), half-open, in the image's own coordinates
+    score: Optional[torch.Tensor]        # fp64 [n] (CPU): the mean confidence, None without conf
+    qsum: Optional[torch.Tensor] = None  # int64 [n] (CPU): the sum of the 16.16 fixed-point confidences behind `score`
+    connectivity: int = 4
+
+    def boxes_of(self, c: int, min_area: int = 1, image: int = 0) -> List[Tuple[int, int, int, int]]:
+        """the boxes of class c's components in one image with at least min_area pixels: what label_boxes(labels[image], c,
+        min_area) returns for connectivity 4, in the same order"""
+        keep = (self.label == c) & (self.image == image) & (self.area >= min_area)
+        return [tuple(b) for b in self.boxes[keep].tolist()]
+
+    def mask(self, i: int) -> torch.Tensor:
+        """bool map of the ids' shape (on the device): the pixels of component i"""
+        if not 0 <= i < self.n:
+            raise IndexError(f"mask: component {i} of {self.n}")
+        return self.ids == i
+
+    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
+                  class_names: Optional[Sequence[str]] = None) -> List[dict]:
+        """one dict {"image", "class", "name", "box", "area", "score"} per component with at least min_area pixels, a mean
+        confidence of at least min_score (not applied when there is no conf) and a class in `classes` (None: any), in id order.
+        name is class_names[class], None without names; score is None without conf."""
+        want = None if classes is None else {int(c) for c in classes}
+        out = []
+        for i in range(self.n):
+            c, area = int(self.label[i]), int(self.area[i])
+            score = None if self.score is None else float(self.score[i])
+            if area < min_area or (want is not None and c not in want) or (score is not None and score < min_score):
+                continue
+            out.append({"image": int(self.image[i]), "class": c, "name": None if class_names is None else class_names[c],
+                        "box": tuple(self.boxes[i].tolist()), "area": area, "score": score})
+        return out
+
+
+def label_components(labels: torch.Tensor, conf: Optional[torch.Tensor] = None, *, connectivity: int = 4) -> ComponentsResult:
+    """The connected components of a label map, on the device (csrc/label_components.hip): labels uint8 [H, W] or [B, H, W], 255 =
+    none; pixels of equal label that are 4-neighbours (or 8-neighbours) inside one image belong together.  With conf (fp32, the
+    labels' shape) every component also gets its mean confidence, an exact integer sum of 16.16 fixed-point values divided
+    once in fp64.  ops.label_components, ONE device -> host read (the count, which sizes the statistics), ops.component_stats;
+    the per-component statistics come back as CPU tensors.  HIP only: a CPU tensor raises."""
+    fname = "label_components"
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise ValueError(f"{fname}: labels must be a cuda tensor, got {getattr(labels, 'device', type(labels))} (no CPU path)")
+    if labels.dim() not in (2, 3):
+        raise ValueError(f"{fname}: labels must be [H, W] or [B, H, W], got {tuple(labels.shape)}")
+    if conf is not None and (not isinstance(conf, torch.Tensor) or tuple(conf.shape) != tuple(labels.shape)):
+        raise ValueError(f"{fname}: conf must be a tensor of the labels' shape {list(labels.shape)}, got {tuple(getattr(conf, 'shape', ()))}")
+    shape = labels.shape
+    lab3 = labels.reshape(-1, shape[-2], shape[-1]) if labels.dim() == 2 else labels
+    conf3 = None if conf is None else conf.reshape(lab3.shape)
+    dev = labels.device
+    root = torch.empty(lab3.shape, device=dev, dtype=torch.int32)
+    ids = torch.empty(lab3.shape, device=dev, dtype=torch.int32)
+    count = torch.empty(1, device=dev, dtype=torch.int32)
+    workspace = torch.empty(max(1, (lab3.numel() + ops.COMPONENTS_GROUP - 1) // ops.COMPONENTS_GROUP), device=dev, dtype=torch.int32)
+    ops.label_components(lab3, connectivity, root, ids, count, workspace)
+    n = int(count.item())                                                     # the one read that sizes what follows
+    label = torch.empty(n, device=dev, dtype=torch.uint8)
+    image, first, area = (torch.empty(n, device=dev, dtype=torch.int32) for _ in range(3))
+    box = torch.empty(n, 4, device=dev, dtype=torch.int32)
+    qsum = None if conf3 is None else torch.empty(n, device=dev, dtype=torch.int64)
+    ops.component_stats(lab3, root, ids, n, label, image, first, area, box, conf=conf3, qsum=qsum)
+    area_c = area.cpu()
+    qsum_c = None if qsum is None else qsum.cpu()
+    score = None if qsum_c is None else qsum_c.double() / (65536.0 * area_c.double())
+    return ComponentsResult(ids=ids.reshape(shape), root=root.reshape(shape), n=n, label=label.cpu(), image=image.cpu(),
+                            first=first.cpu(), area=area_c, boxes=box.cpu(), score=score, qsum=qsum_c, connectivity=int(connectivity))
+
+
 @dataclass
 class PhotoDenseResult:
     probs: torch.Tensor                  # fp32 [K, C, g, g]: the class maps of every window
@@ -319,6 +410,16 @@ class PhotoDenseResult:
     def class_boxes(self, c: int, min_area: int = 1) -> List[Tuple[int, int, int, int]]:
         """bounding boxes (x0, y0, x1, y1) of the 4-connected components of label c (`label_boxes`): what classify_regions takes"""
         return label_boxes(self.labels, c, min_area)
+
+    def components(self, connectivity: int = 4) -> ComponentsResult:
+        """the connected components of the label map with their mean confidences, on the device (`label_components`)"""
+        return label_components(self.labels, self.conf, connectivity=connectivity)
+
+    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
+                  connectivity: int = 4) -> List[dict]:
+        """one record per connected component: components(connectivity).instances(...) with this result's class names"""
+        return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
+                                                       class_names=self.class_names)
 
 
 def segment_photo(model, image, classes: Union[torch.Tensor, Sequence[str]], *, window=None, stride=None, mode: str = "value",

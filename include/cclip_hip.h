@@ -1188,6 +1188,43 @@ int cclip_dense_stitch(const float* probs, int32_t K, int32_t C, int32_t g, cons
                        float min_conf, uint8_t* labels, float* conf, uint8_t* cover, const uint8_t* palette, const uint8_t* photo,
                        int32_t a8, uint8_t* overlay, hipStream_t stream);
 
+/* cclip_label_components (csrc/label_components.hip): the connected components of labels uint8 [B][H][W], 255 = "none".
+ *   Two pixels are joined when they lie in the same image, carry the same label other than 255 and are 4-neighbours
+ *   (connectivity 4) or 8-neighbours (connectivity 8); components are the classes of the transitive closure.  Nothing joins
+ *   across the images of the batch, nothing wraps from the end of a row to the start of the next.  With the flat index
+ *   p = (b H + y) W + x:
+ *     root  [B][H][W] int32 = the flat index of the component's FIRST pixel in row-major order, -1 where the label is 255
+ *     ids   [B][H][W] int32 = the component's number: 0 .. n - 1 in ascending order of root, -1 for "none"
+ *     count [1]       int32 = n, on the device
+ *   workspace: int32 [workspace_ints], workspace_ints >= ceil(B H W / CCLIP_COMPONENTS_GROUP) (the per-group root counts);
+ *   `ids` holds the union-find parents until the numbering overwrites it.  root, ids, count and workspace must not overlap.
+ *   Label equivalence with integer atomicMin, the smaller index always wins: root and ids are canonical forms that do not
+ *   depend on the order in which atomics land, so two calls give equal bytes.  Six launches; no kernel waits for another
+ *   work-group, every loop moves to strictly smaller indices.
+ *   CCLIP_ERR_ARG, nothing launched: a NULL pointer; B < 1; H or W outside [1, CCLIP_OVERLAY_MAX_SIDE]; B H W > 2^31 - 1 (formed
+ *   in 64 bits); connectivity other than 4 or 8; root, ids, count or workspace not 4-byte aligned; workspace_ints too small.
+ *   labels may have any alignment.
+ *
+ * cclip_component_stats: what each of the n components is, from the labelling above (the caller reads count first; n sizes the
+ *   outputs).  For component i < n:
+ *     label[i] uint8, image[i] int32 (the batch index), first[i] int32 (its root index), area[i] int32 (pixels),
+ *     box[i] int32 x 4 = (x0, y0, x1, y1), half-open, in the image's own coordinates,
+ *     qsum[i] uint64 = the sum over the component's pixels of q(conf), conf fp32 [B][H][W]:
+ *       q(v) = (v >= 0) ? min(65536, (uint32)(v * 65536.0f + 0.5f)) : 0, NaN gives 0 (fp32 operations, each rounded once);
+ *       the mean confidence is qsum / (65536 area).  conf and qsum are given together or both NULL.
+ *   Integer sums, minima and maxima by 32- and 64-bit integer atomics, after the pixels of a wave that share a component have
+ *   been combined: two calls give equal bytes.  Pixels whose id lies outside [0, n) are passed over.  n == 0 returns CCLIP_OK
+ *   with nothing launched and the outputs neither checked nor touched.
+ *   CCLIP_ERR_ARG, nothing launched: labels, root or ids NULL; with n > 0 a NULL label, image, first, area or box; conf without
+ *   qsum or qsum without conf; the shape limits above; n < 0 or n > B H W; an int32 / fp32 pointer not 4-byte aligned, qsum
+ *   not 8-byte aligned.  labels and label may have any alignment. */
+#define CCLIP_COMPONENTS_GROUP 1024
+int cclip_label_components(const uint8_t* labels, int32_t B, int32_t H, int32_t W, int32_t connectivity, int32_t* root,
+                           int32_t* ids, int32_t* count, int32_t* workspace, int64_t workspace_ints, hipStream_t stream);
+int cclip_component_stats(const uint8_t* labels, const float* conf, const int32_t* root, const int32_t* ids, int32_t B, int32_t H,
+                          int32_t W, int32_t n, uint8_t* label, int32_t* image, int32_t* first, int32_t* area, int32_t* box,
+                          uint64_t* qsum, hipStream_t stream);
+
 /* ---- CLIP-guided caption selection ---------------------------------------------------------------
  * K candidate captions for each of N images, scored against the image (CLIPScore, Hessel et al. 2021), optionally against the
  * image's reference captions (RefCLIPScore), and ranked - one launch, one work-group per image (csrc/caption_select.hip).

@@ -7,6 +7,8 @@ class with the largest area, the mean confidence; --png DIR also writes the labe
 With --window (and / or --stride) every photo is segmented at its OWN size by sliding windows (`clip.segment_photo`: overlapping
 crops through the tower, probabilities averaged where they overlap, csrc/dense_stitch.hip); several --window sizes make a
 multi-scale ensemble.  The JSON line then also carries "windows", "height" and "width", and the PNG has the photo's size.
+With --instances the line gains "instances": one record {"class", "name", "box", "area", "score"} per connected component of the
+label map (`clip.label_components`, csrc/label_components.hip), filtered by --min-area / --min-score, joined by --connectivity.
 
     python scripts/segment_images.py photos/ --checkpoint clip.pt --prompts "a worker without a helmet" scaffold ground --png maps
     python scripts/segment_images.py photos/ --checkpoint clip.pt --window 224 448 --max-side 2048 --png maps
@@ -42,6 +44,10 @@ def build_parser():
                     help="sliding windows of side N over each photo at its own size (several: multi-scale); default with --stride: the model's resolution")
     ap.add_argument("--stride", type=int, default=None, help="step of the window lattice (default: half of each window)")
     ap.add_argument("--max-side", type=int, default=None, metavar="M", help="--window: first shrink a photo whose longer side exceeds M")
+    ap.add_argument("--instances", action="store_true", help="add one record per connected component of the label map")
+    ap.add_argument("--min-area", type=int, default=1, help="--instances: drop components of fewer pixels")
+    ap.add_argument("--min-score", type=float, default=0.0, help="--instances: drop components of a lower mean confidence")
+    ap.add_argument("--connectivity", type=int, choices=(4, 8), default=4, help="--instances: which neighbours join")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=3, help="--synthetic: images to segment")
     return ap
@@ -55,6 +61,13 @@ def class_prompts(args):
     if args.types == "violation":
         return list(SYNTHETIC_VIOLATIONS) if args.synthetic else list(C.CLASSES)
     return ["violation", "status"]
+
+
+def instance_records(comps, args, prompts, image=None):
+    """--instances: a ComponentsResult as JSON-ready records (of one image of a batch when `image` is given)"""
+    recs = comps.instances(min_area=args.min_area, min_score=args.min_score, class_names=prompts)
+    return [{"class": r["class"], "name": r["name"], "box": list(r["box"]), "area": r["area"], "score": round(r["score"], 6)}
+            for r in recs if image is None or r["image"] == image]
 
 
 def photos(args, model, files, prompts, text):
@@ -78,6 +91,8 @@ def photos(args, model, files, prompts, text):
         line = dict(file=f, classes=prompts, area=[round(v, 6) for v in res.area_fractions().tolist()],
                     top_class=None if top is None else prompts[top], mean_conf=round(float(res.conf.mean()), 5),
                     windows=int(res.boxes.shape[0]), height=int(res.labels.shape[0]), width=int(res.labels.shape[1]))
+        if args.instances:
+            line["instances"] = instance_records(res.components(args.connectivity), args, prompts)
         if args.png:
             import numpy as np
             photo = torch.from_numpy(np.asarray(pic, dtype=np.uint8).copy())
@@ -134,9 +149,12 @@ def main(argv=None):
             import numpy as np
             photo = torch.stack([torch.from_numpy(np.asarray(p.resize((S, S), Image.BILINEAR)).copy()) for p in pics])
             overlay = res.overlay(photo=photo, alpha=args.alpha).cpu().numpy()
+        comps = res.components(args.connectivity) if args.instances else None
         for j, f in enumerate(chunk):
             line = dict(file=f, classes=prompts, area=[round(v, 6) for v in fractions[j].tolist()],
                         top_class=None if top[j] is None else prompts[top[j]], mean_conf=round(float(mean_conf[j]), 5))
+            if comps is not None:
+                line["instances"] = instance_records(comps, args, prompts, image=j)
             if overlay is not None:
                 line["png"] = os.path.join(args.png, f"{i + j:05d}_{os.path.splitext(os.path.basename(f))[0]}.png")
                 Image.fromarray(overlay[j]).save(line["png"])
