@@ -17,7 +17,7 @@
 //   2. the four waves' partials meet in LDS and are added ((p0 + p1) + p2) + p3; every wave applies the prox to the whole
 //      16 MT x 32 block (redundantly: each needs all of it as an operand), one wave per row tile stores w_{k+1}
 //   3. acc[d, row] += c^T[d, v] (-y_{k+1})[v, row] over the wave's columns            (MFMA, A from the SAME LDS tile through
-//      ds_read_b64_tr_b16, B = -y_{k+1} as hi + lo) - acc started the sweep as x
+//      ds_read_b64_tr_b16 - score_pair.h's tile_frag_tr -, B = -y_{k+1} as hi + lo) - acc started the sweep as x
 // The columns are split over the four waves in runs of ceil(D / 128) k-steps of 32 (a wave beyond D only helps to load), the
 // rows are not: a wave holds all 16 MT rows of its columns, as fp32 accumulators AND as the 16-bit pair the next sweep's first
 // product reads.  That is 2 x MT x KSW x 8 registers: 128 at <KSW, MT> = <4, 2> (D <= 512, 32 rows) and <8, 1> (D <= 1024, 16 rows).
@@ -27,7 +27,7 @@
 // index inside a k-step is permuted (k = 4 h + r  <->  d = 32 ks + 16 h + 4 g + r) so that a lane's accumulators ARE its B
 // operand: no shuffle, no LDS round trip between the sweeps.
 //
-// Operand form.  r and -y enter the MFMA as hi = round16(v), lo = round16(v - hi); one accumulator chain takes hi then lo of
+// Operand form.  r and -y enter the MFMA as hi = round16(v), lo = round16(v - hi) (split16); one accumulator chain takes hi then lo of
 // every k-step in ascending order.  w is fp32; w_{k+1} is written over w_{k-1} (two buffers, [N, V] each: the caller's w and the
 // workspace; the last iteration writes the caller's).  Padding concepts (V up to the tile) are loaded as copies of the last
 // row, their operand is a selected 0, their weights are never written and never counted.
@@ -36,7 +36,7 @@
 // every float read-out of that row NaN (nnz counts w > 0, so 0) and touches no other row - a row lives on one lane column of
 // every product.  A row's outputs are a function of (the row, c, l1, eta, iters) alone; no atomics, no fused multiply-add, one
 // summation order: two calls are bitwise equal.
-#include "score_sweep.h"
+#include "score_pair.h"
 #include "../../include/cclip_hip.h"
 
 // the sums below are written out operation by operation: no fused multiply-add may be formed from them
@@ -74,15 +74,6 @@ __device__ __forceinline__ void concept_store4(float* row, int v0, int V, f32x4 
 #pragma unroll
   for (int r = 0; r < 4; ++r)
     if (v0 + r < V) row[v0 + r] = v[r];
-}
-
-// attention_tiles.h's frag_tr on score_tiles.h's image (embed_probe.hip's probe_frag_tr).  Needs EXEC all ones.
-__device__ __forceinline__ bf16x8 concept_frag_tr(const char* tile, const TileGeom& geo, int rowblk0, int rowblk1, int dt, int lane) {
-  const int qq = (lane >> 2) & 3, p = lane & 3;
-  const int chunk = 2 * dt + (p >> 1), sub = 8 * (p & 1);
-  const bf16x4 lo = lds_read_tr16(tile + geo.off(rowblk0 + qq, chunk) + sub);
-  const bf16x4 hi = lds_read_tr16(tile + geo.off(rowblk1 + qq, chunk) + sub);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // <KSMAX, KSW, MT>: k-steps of 32 a tile row has at most (D <= 32 KSMAX); k-steps a wave owns at most (D <= 128 KSW); row tiles
@@ -136,12 +127,7 @@ __global__ __launch_bounds__(256) void concept_codes_kernel(const ConceptArgs a)
       for (int i = 0; i < KSW; ++i) {
         if (i >= nown) continue;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float v = acc[mt][2 * i + (j >> 2)][j & 3];
-          const bf16 hi = (bf16)v;
-          rhi[mt][i][j] = hi;
-          rlo[mt][i][j] = (bf16)(v - (float)hi);
-        }
+        for (int j = 0; j < 8; ++j) split16(acc[mt][2 * i + (j >> 2)][j & 3], rhi[mt][i], rlo[mt][i], j);
       }
   };
 
@@ -246,9 +232,7 @@ __global__ __launch_bounds__(256) void concept_codes_kernel(const ConceptArgs a)
               wn[r] = w1;
               const float yn = last_it ? w1 : w1 + betan * (w1 - wk);
               const float ny = okv ? -yn : 0.0f;                  // selected: a padding concept adds nothing
-              const bf16 hi = (bf16)ny;
-              nyhi[mt][4 * st + r] = hi;
-              nylo[mt][4 * st + r] = (bf16)(ny - (float)hi);
+              split16(ny, nyhi[mt], nylo[mt], 4 * st + r);
             }
           }
           // T == 0 leaves w = 0 to the closing sweep; otherwise the closing sweep writes nothing
@@ -263,7 +247,7 @@ __global__ __launch_bounds__(256) void concept_codes_kernel(const ConceptArgs a)
         if (i >= nown) continue;                  // (wave-uniform)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-          const bf16x8 ct = concept_frag_tr(tile, geo, 4 * g, 16 + 4 * g, 2 * (ks0 + i) + h, lane);
+          const bf16x8 ct = tile_frag_tr(tile, geo, 4 * g, 16 + 4 * g, 2 * (ks0 + i) + h, lane);
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             acc[mt][2 * i + h] = CCLIP_MFMA_16x16x32(ct, nyhi[mt], acc[mt][2 * i + h]);
@@ -323,7 +307,7 @@ struct ConceptGeom {
 
 // of (N, V, D) alone
 static inline bool concept_geom(int64_t N, int64_t V, int32_t D, ConceptGeom& g) {
-  if (!score_rows_ok(N) || V < 1 || V > CONCEPT_MAX_V || D < 32 || (D & 31) || D > 1024) return false;
+  if (!score_rows_ok(N) || V < 1 || V > CONCEPT_MAX_V || !score_dim_ok(D)) return false;
   g.mt = D <= 512 ? 2 : 1;
   g.blocks = (N + 16 * g.mt - 1) / (16 * g.mt);
   g.ldw2 = (V + 3) / 4 * 4;
@@ -336,8 +320,6 @@ static int concept_launch(const ConceptArgs& a, const ConceptGeom& g, hipStream_
   const size_t lds = (size_t)2 * CONCEPT_GT * a.D * 2 + (size_t)4 * MT * 2 * 64 * 16;
   return score_launch(concept_codes_kernel<KSMAX, KSW, MT>, (unsigned)g.blocks, lds, a, stream);
 }
-
-static inline bool concept_finite(float v) { return v == v && v < __builtin_huge_valf() && v > -__builtin_huge_valf(); }
 
 }  // namespace CCLIP_NS
 using namespace CCLIP_NS;
@@ -358,7 +340,7 @@ extern "C" int CCLIP_FN(cclip_concept_codes)(const void* x, int64_t ldx, int64_t
   if (!concept_geom(N, V, D, g) || !score_operands_ok(x, ldx, c, ldc, D)) return CCLIP_ERR_ARG;
   if (ldw < V || (ldw & 3) || (((uintptr_t)w | (uintptr_t)workspace) & 15)) return CCLIP_ERR_ARG;
   if (((uintptr_t)resid2 | (uintptr_t)l1norm | (uintptr_t)nnz | (uintptr_t)delta | (uintptr_t)kkt) & 3) return CCLIP_ERR_ARG;
-  if (!concept_finite(l1) || !concept_finite(eta) || l1 < 0.0f || eta < 0.0f || iters < 0) return CCLIP_ERR_ARG;
+  if (!score_finite(l1) || !score_finite(eta) || l1 < 0.0f || eta < 0.0f || iters < 0) return CCLIP_ERR_ARG;
   if (workspace_bytes < g.total) return CCLIP_ERR_ARG;
   ConceptArgs a;
   a.x = (const bf16*)x; a.c = (const bf16*)c; a.ldx = ldx; a.ldc = ldc;

@@ -35,7 +35,7 @@
 //
 // cclip_coreset_greedy enqueues the m launches of a whole selection from one C loop (the pattern of decode_driver.hip),
 // alternating the two partial buffers: the host cost of a pick is a launch, not a ctypes round trip, and nothing is read back.
-#include "score_key.h"
+#include "score_tiles.h"
 #include "../../include/cclip_hip.h"
 
 // the sums below are written out operation by operation: no fused multiply-add may be formed from them
@@ -200,7 +200,7 @@ static bool coreset_state_ok(CoresetArgs& a, const void* x, int64_t ldx, int64_t
                              int32_t* owner) {
   if (!x || !mind || !owner) return false;
   if (N <= 0 || N > 0x7fffffffLL) return false;
-  if (D < 32 || (D & 31) || D > 1024 || (ldx & 7) || ldx < D || ((uintptr_t)x & 15)) return false;
+  if (!score_dim_ok(D) || !score_operand_ok(x, ldx, D)) return false;
   if (((uintptr_t)weight & 3) || ((uintptr_t)mind & 3) || ((uintptr_t)owner & 3)) return false;
   a.x = (const bf16*)x; a.ldx = ldx; a.N = (int)N; a.D = D;
   a.weight = weight; a.mind = mind; a.owner = owner;

@@ -14,8 +14,8 @@
 // 16 x 16 score tile has the query on the accumulator row (4 g + r) and the stored row on the lane (li).  That is the B operand
 // layout of the second product  dG^T[d, n] = sum_q Qm^T[d, q] w[q, n]  over k = the 32 queries of the tile (element j of lane
 // group g: query 16 (j >> 2) + 4 g + (j & 3), the same k order on both operands), whose A operand Qm^T comes from the SAME LDS
-// image through the transposed read ds_read_b64_tr_b16 (frag_tr below; the scheme of attention.hip's dV^T = dO^T P).  Every
-// address of that read is a chunk offset (multiple of 16) plus 0 or 8: 8-byte aligned.  All branches around it are wave-uniform.
+// image through the transposed read ds_read_b64_tr_b16 (score_pair.h's tile_frag_tr; the scheme of attention.hip's
+// dV^T = dO^T P).  All branches around it are wave-uniform.
 //
 // w as a 16-bit operand.  w is fp32 in the accumulators.  It is scaled by a power of two 2^-e taken from max|dA| (a small
 // reduction launch in front; e = the exponent of the maximum, so |dA| 2^-e < 1 and fp16 does not go subnormal where dA is of
@@ -35,7 +35,7 @@
 // the variant depends on anything but Np and D: two launches are bitwise equal.
 // The kernels index class_off / class_len with clamped cursors only: whatever the two arrays hold, no access leaves q, g, dA,
 // the workspace or dG.
-#include "score_sweep.h"
+#include "score_pair.h"
 #include "../../include/cclip_hip.h"
 
 // the sums below are written out operation by operation: no fused multiply-add may be formed from them, so that every
@@ -58,16 +58,6 @@ struct CacheBwdArgs {
   const float* amax; int nparts;                  // partial maxima of |dA|
   float* dG;                                      // [Np][D]
 };
-
-// A-operand fragment of X^T (columns 16 dt .. 16 dt + 15 of the tile image as MFMA rows) over 8 tile rows given as two 4-row
-// blocks: attention_tiles.h's frag_tr on score_tiles.h's image.  Needs EXEC all ones.
-__device__ __forceinline__ bf16x8 tile_frag_tr(const char* tile, const TileGeom& geo, int rowblk0, int rowblk1, int dt, int lane) {
-  const int qq = (lane >> 2) & 3, p = lane & 3;
-  const int chunk = 2 * dt + (p >> 1), sub = 8 * (p & 1);
-  const bf16x4 lo = lds_read_tr16(tile + geo.off(rowblk0 + qq, chunk) + sub);
-  const bf16x4 hi = lds_read_tr16(tile + geo.off(rowblk1 + qq, chunk) + sub);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // partial maxima of |dA| (NaN is ignored by fmaxf); block b writes part[b]
 __global__ __launch_bounds__(256) void cache_bwd_amax_kernel(const float* __restrict__ dA, long n, float* __restrict__ part) {
@@ -132,11 +122,7 @@ __global__ __launch_bounds__(256) void cache_bwd_kernel(const CacheBwdArgs a) {
     __syncthreads();                              // tile `base` is whole; every wave has left the tile before last (this buffer's next content)
     if (t + 1 < ntiles) mover.fetch(a.q, a.ldq, base + GT, Q - 1);
     if (!active) continue;                        // (wave-uniform)
-    // the LDS addresses of a tile are recomputed per tile from an opaque copy of the lane number: hoisted out of the tile loop
-    // (2 KSMAX + 2 NDT swizzled addresses) they would cost more registers than the accumulator
-    int lane_t = lane;
-    asm volatile("" : "+v"(lane_t));
-    const int li_t = lane_t & 15, g_t = lane_t >> 4;
+    const int lane_t = opaque_lane(lane);         // the tile's LDS addresses are formed per tile (score_pair.h)
 
     // this lane's queries base + 16 st + 4 g + r: their dA (scaled, exact) and excluded rows
     float da[2][4];
@@ -151,17 +137,8 @@ __global__ __launch_bounds__(256) void cache_bwd_kernel(const CacheBwdArgs a) {
       }
 
     // s^T: query on the accumulator row, stored row on the lane; one chain over d
-    f32x4 s[2];
-    s[0] = s[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KSMAX; ++ks) {
-      if (ks >= geo.nks) continue;
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const bf16x8 qf = *(const bf16x8*)(Qs + geo.off(16 * st + li_t, 4 * ks + g_t));
-        s[st] = CCLIP_MFMA_16x16x32(qf, gf[0][ks], s[st]);
-      }
-    }
+    f32x4 s[1][2];
+    tile_scores_t<KSMAX, 1>(s, gf, Qs, geo, lane_t);
 
     bf16x8 whi, wlo;
 #pragma unroll
@@ -169,36 +146,24 @@ __global__ __launch_bounds__(256) void cache_bwd_kernel(const CacheBwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qi = base + 16 * st + 4 * g + r;
-        const float x = (s[st][r] - 1.0f) * a.beta;
+        const float x = (s[0][st][r] - 1.0f) * a.beta;
         const bool take = live && qi < Q && row != excl[st][r];
         const float w = take ? da[st][r] * __expf(x) : 0.0f;      // selected, not multiplied: a masked NaN stays out
-        const bf16 hi = (bf16)w;
-        whi[4 * st + r] = hi;
-        wlo[4 * st + r] = (bf16)(w - (float)hi);
+        split16(w, whi, wlo, 4 * st + r);
       }
 
     // dG^T[d, n] += Qm^T[d, q] w[q, n] over the 32 queries of the tile: k index = (st, g, r) on both operands
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      if (16 * (dt0 + dt) >= D) continue;         // (wave-uniform)
-      const bf16x8 qt = tile_frag_tr(Qs, geo, 4 * g_t, 16 + 4 * g_t, dt0 + dt, lane_t);
-      acc[dt] = CCLIP_MFMA_16x16x32(qt, whi, acc[dt]);
-      acc[dt] = CCLIP_MFMA_16x16x32(qt, wlo, acc[dt]);
-    }
+    tr_accumulate<NDT>(acc, Qs, geo, dt0, D, whi, wlo, lane_t);
   }
 
   // lane (li, g) holds dG[row][16 dt + 4 g .. + 3]; a padding row is +0.0f whatever the accumulator's sign
   if (row < Np) {
-    float* out = a.dG + (long)row * D + 4 * g;
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      const int d = 16 * (dt0 + dt);
-      if (d >= D) continue;
+    store_dt_columns<NDT>(a.dG + (long)row * D + 4 * g, dt0, D, [&](int dt) CCLIP_SWEEP_INLINE {
       f32x4 v;
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = live ? acc[dt][r] * up : 0.0f;
-      *(f32x4*)(out + d) = v;
-    }
+      return v;
+    });
   }
 }
 

@@ -201,6 +201,7 @@ __global__ __launch_bounds__(256) void kmeans_finish_kernel(const UpdateArgs a, 
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     if (tid + 256 * j < D) ss += s[j] * s[j];
+  // (score_key.h's block_sum4, kept open-coded here: profiles/score_pair_refactor_ab.txt)
   ss = wave_sum(ss);                              // xor butterfly: every lane holds the same bits
   if ((tid & 63) == 0) wsum[wave] = ss;
   __syncthreads();
@@ -239,7 +240,7 @@ extern "C" int CCLIP_FN(cclip_kmeans_assign)(const void* x, int64_t ldx, int64_t
 
 #ifndef CCLIP_F16
 extern "C" int64_t cclip_kmeans_update_workspace(int64_t N, int64_t K, int32_t D) {
-  if (!score_rows_ok(N) || !score_rows_ok(K) || D < 32 || (D & 31) || D > 1024) return 0;
+  if (!score_rows_ok(N) || !score_rows_ok(K) || !score_dim_ok(D)) return 0;
   return (update_slabs(N) + K) * D * 4;
 }
 #endif
@@ -250,7 +251,7 @@ extern "C" int CCLIP_FN(cclip_kmeans_update)(const void* x, int64_t ldx, int64_t
                                               hipStream_t stream) {
   if (!x || !order || !seg_off || !prev_c || !out_c || !out_norm || !workspace) return CCLIP_ERR_ARG;
   if (!score_rows_ok(N) || !score_rows_ok(K)) return CCLIP_ERR_ARG;
-  if (D < 32 || (D & 31) || D > 1024 || (ldx & 7) || ldx < D || ((uintptr_t)x & 15)) return CCLIP_ERR_ARG;
+  if (!score_dim_ok(D) || !score_operand_ok(x, ldx, D)) return CCLIP_ERR_ARG;
   if (ldp < D || ldo < D || ((uintptr_t)prev_c & 1) || ((uintptr_t)out_c & 1)) return CCLIP_ERR_ARG;
   if (((uintptr_t)order & 3) || ((uintptr_t)seg_off & 3) || ((uintptr_t)out_norm & 3) || ((uintptr_t)workspace & 3)) return CCLIP_ERR_ARG;
   const int64_t nslabs = update_slabs(N);

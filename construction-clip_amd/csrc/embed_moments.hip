@@ -4,7 +4,7 @@
 // class 0.  No N x D fp32 copy, no float atomics.
 //
 // Both products are [onehot(y) | X]^T X.  The k index of the MFMA is the ROW of x on both operands, so both are transposed reads
-// (ds_read_b64_tr_b16) of one row-major LDS tile of 32 rows - the read of step (3) of concept_codes.hip.  Products of two 16-bit
+// (ds_read_b64_tr_b16) of one row-major LDS tile of 32 rows - score_pair.h's tile_frag_tr on a [32][128] image.  Products of two 16-bit
 // values are exact in fp32: no hi + lo pair.  The one-hot operand is built in registers from the tile's labels (compared, never
 // used as an address).
 //
@@ -19,12 +19,12 @@
 // as zero and is recorded instead, by an integer atomic OR into flags[y_n, a] (1 NaN, 2 +Inf, 4 -Inf); the merge turns the flags
 // back into the value an fp32 sum would have had.  count is an LDS histogram per part, added by integer atomics.
 //
-// Order.  The rows are split into cclip_moments_parts(N, C, D) parts of tpp consecutive tiles; a part is ONE accumulator chain
+// Order.  The rows are split into cclip_moments_parts(N, C, D) parts of tpp consecutive tiles (score_sweep.h's row_parts); a part is ONE accumulator chain
 // in ascending row order, written as an fp32 partial block.  moments_merge_kernel adds the parts in a fixed two-level tree
 // (runs of 8 in ascending order, the runs in ascending order) and writes gram[a, b] and gram[b, a] from the same value.  Every
 // choice is a function of (N, C, D) alone; two calls are bitwise equal.
 // Launches: zero (count, flags), partials, merge.
-#include "score_sweep.h"
+#include "score_pair.h"
 #include "../../include/cclip_hip.h"
 
 #pragma clang fp contract(off)
@@ -32,9 +32,6 @@
 #define MOM_RT 32                                 // rows per tile: one k-step
 #define MOM_CB 128                                // columns (or classes) per block
 #define MOM_MAX_C 256
-#define MOM_MIN_TPP 8                             // a part is at least 8 tiles = 256 rows
-#define MOM_MAX_PARTS 1024
-#define MOM_PART_BYTES (32ll << 20)               // bound of the partial blocks
 #define MOM_BLOCK_FLOATS (MOM_CB * MOM_CB)
 
 namespace CCLIP_NS {
@@ -45,17 +42,12 @@ struct MomGeom {
 };
 
 static inline bool mom_geom(int64_t N, int64_t C, int32_t D, MomGeom& g) {
-  if (!score_rows_ok(N) || C < 1 || C > MOM_MAX_C || D < 32 || (D & 31) || D > 1024) return false;
+  if (!score_rows_ok(N) || C < 1 || C > MOM_MAX_C || !score_dim_ok(D)) return false;
   g.nb = (D + MOM_CB - 1) / MOM_CB;
   g.npairs = g.nb * (g.nb + 1) / 2;
   g.ncb = (int)((C + MOM_CB - 1) / MOM_CB);
   g.jobs = g.npairs + g.ncb * g.nb;
-  g.ntiles = (int)((N + MOM_RT - 1) / MOM_RT);
-  int64_t pmax = MOM_PART_BYTES / ((int64_t)g.jobs * MOM_BLOCK_FLOATS * 4);
-  pmax = pmax < 1 ? 1 : pmax > MOM_MAX_PARTS ? MOM_MAX_PARTS : pmax;
-  const int64_t need = (g.ntiles + pmax - 1) / pmax;
-  g.tpp = (int)(need < MOM_MIN_TPP ? MOM_MIN_TPP : need);
-  g.parts = (g.ntiles + g.tpp - 1) / g.tpp;
+  row_parts(N, (int64_t)g.jobs * MOM_BLOCK_FLOATS * 4, &g.ntiles, &g.tpp, &g.parts);   // a part holds one fp32 block per job
   g.off_flags = (int64_t)4 * g.parts * g.jobs * MOM_BLOCK_FLOATS;
   g.total = g.off_flags + (int64_t)4 * C * D;
   return true;
@@ -83,14 +75,11 @@ __global__ __launch_bounds__(256) void moments_zero_kernel(int* __restrict__ cou
   if (i < nflags) flags[i] = 0;
 }
 
-// concept_codes.hip's concept_frag_tr on a [32][128] image: element j of lane (li, g) is row 16 (j >> 2) + 4 g + (j & 3),
-// column 16 dt + li - the k order both operands share.  Needs EXEC all ones.
+// score_pair.h's tile_frag_tr on a [32][128] image at the row blocks 4 g, 16 + 4 g: element j of lane (li, g) is row
+// 16 (j >> 2) + 4 g + (j & 3), column 16 dt + li - the k order both operands share
 __device__ __forceinline__ bf16x8 mom_frag_tr(const char* tile, const TileGeom& geo, int dt, int lane) {
-  const int g = lane >> 4, qq = (lane >> 2) & 3, p = lane & 3;
-  const int chunk = 2 * dt + (p >> 1), sub = 8 * (p & 1);
-  const bf16x4 lo = lds_read_tr16(tile + geo.off(4 * g + qq, chunk) + sub);
-  const bf16x4 hi = lds_read_tr16(tile + geo.off(16 + 4 * g + qq, chunk) + sub);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  const int g = lane >> 4;
+  return tile_frag_tr(tile, geo, 4 * g, 16 + 4 * g, dt, lane);
 }
 
 __global__ __launch_bounds__(256) void moments_partial_kernel(const MomArgs a) {
@@ -296,7 +285,7 @@ extern "C" int CCLIP_FN(cclip_class_moments)(const void* x, int64_t ldx, int64_t
   if (!x || !count || !sum || !gram || !workspace) return CCLIP_ERR_ARG;
   if (!mom_geom(N, C, D, g)) return CCLIP_ERR_ARG;
   if (!labels && C != 1) return CCLIP_ERR_ARG;
-  if ((ldx & 7) || ldx < D || ((uintptr_t)x & 15) || ((uintptr_t)workspace & 15)) return CCLIP_ERR_ARG;
+  if (!score_operand_ok(x, ldx, D) || ((uintptr_t)workspace & 15)) return CCLIP_ERR_ARG;
   if (((uintptr_t)labels & 3) || ((uintptr_t)count & 3) || ((uintptr_t)sum & 3) || ((uintptr_t)gram & 3)) return CCLIP_ERR_ARG;
   if (workspace_bytes < g.total) return CCLIP_ERR_ARG;
   char* ws = (char*)workspace;

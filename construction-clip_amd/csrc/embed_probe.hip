@@ -1,8 +1,8 @@
 // Linear probe over stored embeddings for gfx950: multinomial logistic regression on 16-bit rows x [N, D] with fp32 weights
 // W [C, D] and bias [C].  One evaluation of the objective and its gradient, without the N x C logits in memory.
 //
-// The objective of hi + lo.  W enters the MFMA as a 16-bit pair hi = round16(W), lo = round16(W - hi) (probe_prep_kernel, into
-// the workspace), and everything below is a function of that pair:
+// The objective of hi + lo.  W enters the MFMA as a 16-bit pair hi = round16(W), lo = round16(W - hi) (score_pair.h's
+// pair_image_kernel, into the workspace), and everything below is a function of that pair:
 //     z[n, c]   = (bias[c] + H[n, c]) + L[n, c],  H = sum_d x[n, d] hi[c, d],  L = sum_d x[n, d] lo[c, d]
 //                 H and L are each ONE fp32 accumulator chain over d = 0, 32, 64 .. on v_mfma_f32_16x16x32; the two adds in
 //                 the order written.
@@ -15,9 +15,8 @@
 // trace.  dW is the gradient of the objective as a function of the pair (d z / d W taken as x: W - (hi + lo) is below 2^-16 |W|
 // for bf16, 2^-22 |W| for fp16); loss and gradient therefore belong to the same function, which is what a line search needs.
 //
-// The image.  Classes are padded to Cp = 16 ceil(C / 16) and laid out in tiles of 16: image rows 32 t .. 32 t + 15 are hi of the
-// classes 16 t .., rows 32 t + 16 .. 32 t + 31 their lo; padding classes are zero.  A tile of 32 image rows is one streamed
-// tile of score_tiles.h whose two sub-tiles are the two chains.
+// The image.  Classes are padded to Cp = 16 ceil(C / 16); a tile of 32 image rows holds hi and lo of 16 classes, the two chains
+// (the layout is pair_image_kernel's).
 //
 // Forward (probe_fwd_kernel): the geometry of kmeans_assign_kernel.  Grid = blocks of 64 * MT rows of x, a work-group keeps its
 // rows as A fragments and streams all class tiles through two LDS buffers (one barrier per tile; its own loop, see
@@ -26,7 +25,8 @@
 // the 16 lanes of a group are combined by a fixed xor butterfly whose two partners compute the same bits.  So a row's outputs
 // depend on neither N nor the row's position nor MT.  Ties in pred go to the LOWER class, NaN ranks lowest (score_key.h).
 //
-// Backward (probe_bwd_kernel): the two products of embed_cache_bwd.hip with the roles of its stored rows taken by the classes.
+// Backward (probe_bwd_kernel): the two products of embed_cache_bwd.hip (the inner step both share is score_pair.h's) with the
+// roles of its stored rows taken by the classes.
 // A wave keeps hi and lo of 16 classes as B fragments in registers, the rows of x stream through two LDS buffers in tiles of
 // 32 (an ignored row's content replaced by zeros: 0 * NaN would be NaN in the second product), z^T comes with the row on the accumulator row and the class on the lane, g is split into a 16-bit hi + lo pair (|g| <= 1:
 // no scale) and dW^T[d, c] += x^T[d, n] g[n, c] takes its A operand from the SAME LDS image through ds_read_b64_tr_b16.
@@ -38,8 +38,8 @@
 // spills.  probe_merge_kernel adds the slots in ascending order, applies scale and l2 (the bias is not regularised), and its
 // further blocks reduce loss[] and W^2 by a fixed tree; probe_objective_kernel finishes the scalar.
 // Slots, tiles per part and every other choice are functions of (N, C, D) alone (probe_geom); no atomics, no fused
-// multiply-add: two calls are bitwise equal.  Every index taken from labels is compared, never used as an address.
-#include "score_sweep.h"
+// multiply-add: two calls are bitwise equal.  The row parts are score_sweep.h's row_parts.  Every index taken from labels is compared, never used as an address.
+#include "score_pair.h"
 #include "../../include/cclip_hip.h"
 
 // the sums below are written out operation by operation: no fused multiply-add may be formed from them
@@ -47,9 +47,6 @@
 
 #define PROBE_MAX_C 256
 #define PROBE_RT 32                               // rows of x per backward tile: one k-step of the second product
-#define PROBE_MIN_TPP 8                           // a row part is at least 8 tiles = 256 rows
-#define PROBE_MAX_PARTS 1024
-#define PROBE_PART_BYTES (32ll << 20)             // bound of the partial slots
 #define PROBE_LOSS_BLOCKS 256
 #define PROBE_NONE (-3.0e38f)                     // running maximum before the first class
 
@@ -61,19 +58,14 @@ struct ProbeGeom {
 };
 
 static inline bool probe_geom(int64_t N, int64_t C, int32_t D, ProbeGeom& g) {
-  if (!score_rows_ok(N) || C < 2 || C > PROBE_MAX_C || D < 32 || (D & 31) || D > 1024) return false;
+  if (!score_rows_ok(N) || C < 2 || C > PROBE_MAX_C || !score_dim_ok(D)) return false;
   g.cpad = (int)((C + 15) / 16 * 16);
   const int nb = g.cpad / 16;
   g.cbw = nb >= 3 ? 4 : nb;                       // class blocks of 16 per work-group
   g.rs = 4 / g.cbw;                               // row streams per work-group
   g.ncb = (nb + g.cbw - 1) / g.cbw;
   g.ds = D > 512 ? 4 : 1;
-  g.ntiles = (int)((N + PROBE_RT - 1) / PROBE_RT);
-  int64_t pmax = PROBE_PART_BYTES / ((int64_t)g.rs * g.cpad * D * 4);
-  pmax = pmax < 1 ? 1 : pmax > PROBE_MAX_PARTS ? PROBE_MAX_PARTS : pmax;
-  const int64_t need = (g.ntiles + pmax - 1) / pmax;
-  g.tpp = (int)(need < PROBE_MIN_TPP ? PROBE_MIN_TPP : need);
-  g.parts = (g.ntiles + g.tpp - 1) / g.tpp;
+  row_parts(N, (int64_t)g.rs * g.cpad * D * 4, &g.ntiles, &g.tpp, &g.parts);      // a part holds rs slots of [cpad][D] fp32
   g.slots = g.parts * g.rs;
   g.wblocks = (int)((C * D + 255) / 256);
   g.off_part = (int64_t)4 * g.cpad * D;                           // behind the image: 2 Cp rows of D 16-bit elements
@@ -81,18 +73,6 @@ static inline bool probe_geom(int64_t N, int64_t C, int32_t D, ProbeGeom& g) {
   g.off_red = g.off_db + (int64_t)4 * g.slots * g.cpad;
   g.total = g.off_red + (int64_t)4 * (g.wblocks + PROBE_LOSS_BLOCKS);
   return true;
-}
-
-__global__ __launch_bounds__(256) void probe_prep_kernel(const float* __restrict__ W, int C, int D, int cpad, bf16* __restrict__ img) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long)cpad * D) return;
-  const int c = (int)(idx / D), d = (int)(idx - (long)c * D);
-  const float w = c < C ? W[idx] : 0.0f;
-  const bf16 hi = (bf16)w;
-  const bf16 lo = (bf16)(w - (float)hi);
-  const long row = (long)(c >> 4) * 32 + (c & 15);
-  img[row * D + d] = hi;
-  img[(row + 16) * D + d] = lo;
 }
 
 // row_weight into [0, 1]; NaN fails the comparison and becomes 0
@@ -218,15 +198,6 @@ struct ProbeBwdArgs {
   float* part; float* dbpart;                     // [slots][cpad][D], [slots][cpad]
 };
 
-// attention_tiles.h's frag_tr on score_tiles.h's image (embed_cache_bwd.hip's tile_frag_tr).  Needs EXEC all ones.
-__device__ __forceinline__ bf16x8 probe_frag_tr(const char* tile, const TileGeom& geo, int rowblk0, int rowblk1, int dt, int lane) {
-  const int qq = (lane >> 2) & 3, p = lane & 3;
-  const int chunk = 2 * dt + (p >> 1), sub = 8 * (p & 1);
-  const bf16x4 lo = lds_read_tr16(tile + geo.off(rowblk0 + qq, chunk) + sub);
-  const bf16x4 hi = lds_read_tr16(tile + geo.off(rowblk1 + qq, chunk) + sub);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 // <KSMAX, DS, PRE>: k-steps of 32 the class fragments are sized for (D <= 32 KSMAX); DS column parts over the grid; PRE: the next
 // tile's loads are in flight under the current tile's products (above D = 512 their 64 staging registers would spill: the tile
 // is loaded at the top of its own step instead)
@@ -289,10 +260,7 @@ __global__ __launch_bounds__(256) void probe_bwd_kernel(const ProbeBwdArgs a) {
     __syncthreads();                              // tile t is whole; every wave has left the tile before last (this buffer's next content)
     if (PRE && t + 1 < t1) { mover.fetch(a.x + ((long)base + GT) * a.ldx, a.ldx, 0, N - 1 - (base + GT)); deadmask = dead_rows(base + GT); }
     if (!active || (t - t0) % a.rs != stream) continue;           // (wave-uniform)
-    // the LDS addresses of a tile are recomputed per tile from an opaque copy of the lane number (embed_cache_bwd.hip)
-    int lane_t = lane;
-    asm volatile("" : "+v"(lane_t));
-    const int li_t = lane_t & 15, g_t = lane_t >> 4;
+    const int lane_t = opaque_lane(lane);         // the tile's LDS addresses are formed per tile (score_pair.h)
 
     // this lane's rows base + 16 st + 4 g + r
     float lse[2][4], w[2][4];
@@ -307,19 +275,9 @@ __global__ __launch_bounds__(256) void probe_bwd_kernel(const ProbeBwdArgs a) {
         y[st][r] = a.labels ? a.labels[qi] : -1;
       }
 
-    // z^T: row of x on the accumulator row, class on the lane; the hi chain and the lo chain
-    f32x4 sh[2], sl[2];
-    sh[0] = sh[1] = sl[0] = sl[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KSMAX; ++ks) {
-      if (ks >= geo.nks) continue;
-#pragma unroll
-      for (int st = 0; st < 2; ++st) {
-        const bf16x8 xf = *(const bf16x8*)(Xs + geo.off(16 * st + li_t, 4 * ks + g_t));
-        sh[st] = CCLIP_MFMA_16x16x32(xf, wf[0][ks], sh[st]);
-        sl[st] = CCLIP_MFMA_16x16x32(xf, wf[1][ks], sl[st]);
-      }
-    }
+    // z^T: row of x on the accumulator row, class on the lane; s[0] the hi chain, s[1] the lo chain
+    f32x4 s[2][2];
+    tile_scores_t<KSMAX, 2>(s, wf, Xs, geo, lane_t);
 
     bf16x8 ghi, glo;
 #pragma unroll
@@ -327,47 +285,26 @@ __global__ __launch_bounds__(256) void probe_bwd_kernel(const ProbeBwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const long qi = (long)base + 16 * st + 4 * g + r;
-        const float z = (b + sh[st][r]) + sl[st][r];
+        const float z = (b + s[0][st][r]) + s[1][st][r];
         const float p = expf(z - lse[st][r]);
         const int yy = y[st][r];
         const bool take = okc && qi < N && yy >= 0 && yy < C && w[st][r] > 0.0f;
         const float gg = take ? w[st][r] * (p - (cls == yy ? 1.0f : 0.0f)) : 0.0f;   // selected, not multiplied
         dbacc += gg;
-        const bf16 hi = (bf16)gg;
-        ghi[4 * st + r] = hi;
-        glo[4 * st + r] = (bf16)(gg - (float)hi);
+        split16(gg, ghi, glo, 4 * st + r);
       }
 
     // dW^T[d, c] += x^T[d, n] g[n, c] over the 32 rows of the tile: k index = (st, g, r) on both operands
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-      if (16 * (dt0 + dt) >= D) continue;         // (wave-uniform)
-      const bf16x8 xt = probe_frag_tr(Xs, geo, 4 * g_t, 16 + 4 * g_t, dt0 + dt, lane_t);
-      acc[dt] = CCLIP_MFMA_16x16x32(xt, ghi, acc[dt]);
-      acc[dt] = CCLIP_MFMA_16x16x32(xt, glo, acc[dt]);
-    }
+    tr_accumulate<NDT>(acc, Xs, geo, dt0, D, ghi, glo, lane_t);
   }
   if (!active) return;
 
   // lane (li, g) holds the slot's [cls][16 dt + 4 g .. + 3]; cls < cpad.  A stream without a tile writes zeros.
   const long slot = (long)part * a.rs + stream;
-  float* out = a.part + (slot * a.cpad + cls) * D + 4 * g;
-#pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) {
-    const int d = 16 * (dt0 + dt);
-    if (d >= D) continue;
-    *(f32x4*)(out + d) = acc[dt];
-  }
+  store_dt_columns<NDT>(a.part + (slot * a.cpad + cls) * D + 4 * g, dt0, D, [&](int dt) CCLIP_SWEEP_INLINE { return acc[dt]; });
   dbacc += __shfl_xor(dbacc, 16, 64);             // the four lane groups (rows 4 g + r), a fixed butterfly
   dbacc += __shfl_xor(dbacc, 32, 64);
   if (blockIdx.x == 0 && g == 0) a.dbpart[slot * a.cpad + cls] = dbacc;
-}
-
-__device__ __forceinline__ float probe_block_sum(float v, float* red) {
-  v = wave_sum(v);                                // xor butterfly: every lane holds the same bits
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 struct ProbeMergeArgs {
@@ -401,7 +338,7 @@ __global__ __launch_bounds__(256) void probe_merge_kernel(const ProbeMergeArgs a
   } else if (a.loss) {
     for (long i = (long)(blk - a.wblocks) * 256 + tid; i < a.N; i += (long)PROBE_LOSS_BLOCKS * 256) v += a.loss[i];
   }
-  v = probe_block_sum(v, red);
+  v = block_sum4(v, red);
   if (tid == 0) a.red[blk] = v;
 }
 
@@ -412,35 +349,23 @@ __global__ __launch_bounds__(256) void probe_objective_kernel(const float* __res
   float sw = 0.0f, sl = 0.0f;
   for (int i = tid; i < wblocks; i += 256) sw += part[i];
   sl = part[wblocks + tid];
-  sw = probe_block_sum(sw, red);
+  sw = block_sum4(sw, red);
   __syncthreads();
-  sl = probe_block_sum(sl, red);
+  sl = block_sum4(sl, red);
   if (tid == 0) objective[0] = scale * sl + (0.5f * l2) * sw;
-}
-
-static void probe_prep_launch(const float* W, int C, int D, const ProbeGeom& g, void* ws, hipStream_t stream) {
-  const long cells = (long)g.cpad * D;
-  hipLaunchKernelGGL(probe_prep_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, W, C, D, g.cpad, (bf16*)ws);
 }
 
 template <int KSMAX, int DS, bool PRE>
 static int probe_bwd_launch(const ProbeBwdArgs& a, const ProbeGeom& g, hipStream_t stream) {
-  const size_t lds = (size_t)2 * PROBE_RT * a.D * 2;
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)probe_bwd_kernel<KSMAX, DS, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)lds) != hipSuccess)
-    return CCLIP_ERR_LAUNCH;
-  hipLaunchKernelGGL((probe_bwd_kernel<KSMAX, DS, PRE>), dim3(DS, g.ncb, g.parts), dim3(256), lds, stream, a);
-  return CCLIP_OK;
+  return score_launch(probe_bwd_kernel<KSMAX, DS, PRE>, dim3(DS, g.ncb, g.parts), (size_t)2 * PROBE_RT * a.D * 2, a, stream);
 }
-
-static inline bool probe_finite(float v) { return v == v && v < __builtin_huge_valf() && v > -__builtin_huge_valf(); }
 
 // the checks the two entries share
 static bool probe_args_ok(const void* x, int64_t ldx, int64_t N, int32_t D, const float* W, const float* bias, int32_t C,
                           const int32_t* labels, const float* rw, const void* ws, int64_t ws_bytes, ProbeGeom& g) {
   if (!x || !W || !ws) return false;
   if (!probe_geom(N, C, D, g)) return false;
-  if ((ldx & 7) || ldx < D || ((uintptr_t)x & 15) || ((uintptr_t)ws & 15)) return false;
+  if (!score_operand_ok(x, ldx, D) || ((uintptr_t)ws & 15)) return false;
   if (((uintptr_t)W & 3) || ((uintptr_t)bias & 3) || ((uintptr_t)labels & 3) || ((uintptr_t)rw & 3)) return false;
   return ws_bytes >= g.total;
 }
@@ -468,7 +393,7 @@ extern "C" int CCLIP_FN(cclip_probe_forward)(const void* x, int64_t ldx, int64_t
   if (!lse || !loss || !pred) return CCLIP_ERR_ARG;
   if (!probe_args_ok(x, ldx, N, D, W, bias, C, labels, row_weight, workspace, workspace_bytes, g)) return CCLIP_ERR_ARG;
   if (((uintptr_t)lse & 3) || ((uintptr_t)loss & 3) || ((uintptr_t)pred & 3) || ((uintptr_t)logits & 3)) return CCLIP_ERR_ARG;
-  probe_prep_launch(W, C, D, g, workspace, stream);
+  pair_image_launch(W, C, D, workspace, stream);
   ProbeFwdArgs a;
   a.x = (const bf16*)x; a.img = (const bf16*)workspace; a.ldx = ldx;
   a.N = (int)N; a.C = C; a.D = D;
@@ -488,12 +413,12 @@ extern "C" int CCLIP_FN(cclip_probe_backward)(const void* x, int64_t ldx, int64_
                                                void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   ProbeGeom g;
   if (!lse || !dW || !db || (loss == nullptr) != (objective == nullptr)) return CCLIP_ERR_ARG;
-  if (!probe_finite(scale) || !probe_finite(l2) || scale < 0.0f || l2 < 0.0f) return CCLIP_ERR_ARG;
+  if (!score_finite(scale) || !score_finite(l2) || scale < 0.0f || l2 < 0.0f) return CCLIP_ERR_ARG;
   if (!probe_args_ok(x, ldx, N, D, W, bias, C, labels, row_weight, workspace, workspace_bytes, g)) return CCLIP_ERR_ARG;
   if (((uintptr_t)lse & 3) || ((uintptr_t)loss & 3) || ((uintptr_t)dW & 3) || ((uintptr_t)db & 3) || ((uintptr_t)objective & 3))
     return CCLIP_ERR_ARG;
   char* ws = (char*)workspace;
-  probe_prep_launch(W, C, D, g, workspace, stream);
+  pair_image_launch(W, C, D, workspace, stream);
   ProbeBwdArgs a;
   a.x = (const bf16*)x; a.img = (const bf16*)workspace; a.ldx = ldx;
   a.N = (int)N; a.C = C; a.D = D; a.cpad = g.cpad;

@@ -2,9 +2,9 @@
 // C centres in the transformed space.  One kernel serves the shared-covariance classifier (T a whitening, centres the whitened
 // class means, offset the log priors), the Mahalanobis outlier score (dmin) and the PCA transform (no centres: z alone).
 //
-// The arithmetic of hi + lo.  T enters the MFMA as the 16-bit pair hi = round16(T), lo = round16(T - hi), exactly the pair of W
-// in embed_probe.hip (gauss_prep_kernel, into the workspace: image rows 32 t .. 32 t + 15 are hi of the transform rows 16 t ..,
-// rows 32 t + 16 .. their lo; padding rows are zero):
+// The arithmetic of hi + lo.  T enters the MFMA as the 16-bit pair hi = round16(T), lo = round16(T - hi), by
+// score_pair.h's pair_image_kernel (into the workspace: a tile of 32 image rows holds hi and lo of 16 transform rows; padding
+// rows are zero):
 //     z[q, r]     = acc - t0[r],  acc ONE fp32 accumulator chain on v_mfma_f32_16x16x32 that takes x * hi then x * lo of
 //                   every k-step d = 0, 32, 64 .. in ascending order
 //     d2[q, c]    = sum_r (z[q, r] - centres[c, r])^2        fp32, r ascending, subtract - multiply - add, never expanded:
@@ -23,7 +23,7 @@
 // probe's forward over the row's lanes.  A row's outputs depend on neither Q nor its position; no atomics, no fused
 // multiply-add; two calls are bitwise equal.  A NaN in a row makes that row's z, d2, lse and dmin NaN (pred = nearest = 0) and
 // touches no other row: a row lives on one accumulator row of every product.
-#include "score_sweep.h"
+#include "score_pair.h"
 #include "../../include/cclip_hip.h"
 
 #pragma clang fp contract(off)
@@ -33,18 +33,6 @@
 #define GAUSS_NONE (-3.0e38f)                     // running maximum before the first class
 
 namespace CCLIP_NS {
-
-__global__ __launch_bounds__(256) void gauss_prep_kernel(const float* __restrict__ T, int R, int D, int rpad, bf16* __restrict__ img) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long)rpad * D) return;
-  const int r = (int)(idx / D), d = (int)(idx - (long)r * D);
-  const float w = r < R ? T[idx] : 0.0f;
-  const bf16 hi = (bf16)w;
-  const bf16 lo = (bf16)(w - (float)hi);
-  const long row = (long)(r >> 4) * 32 + (r & 15);
-  img[row * D + d] = hi;
-  img[(row + 16) * D + d] = lo;
-}
 
 struct GaussArgs {
   const bf16* x; const bf16* img;
@@ -150,7 +138,7 @@ __global__ __launch_bounds__(256) void gauss_scores_kernel(const GaussArgs a) {
 }
 
 static inline bool gauss_sizes_ok(int64_t R, int32_t D) {
-  return !(R < 1 || R > GAUSS_MAX_R || D < 32 || (D & 31) || D > 1024);
+  return !(R < 1 || R > GAUSS_MAX_R || !score_dim_ok(D));
 }
 
 template <int KSMAX, int MT>
@@ -166,7 +154,7 @@ using namespace CCLIP_NS;
 
 #ifndef CCLIP_F16
 extern "C" int64_t cclip_gauss_scores_workspace(int64_t R, int32_t D) {
-  return gauss_sizes_ok(R, D) ? (int64_t)4 * ((R + 15) / 16 * 16) * D : 0;
+  return gauss_sizes_ok(R, D) ? (int64_t)4 * pair_image_rows((int)R) * D : 0;
 }
 #endif
 
@@ -179,14 +167,12 @@ extern "C" int CCLIP_FN(cclip_gauss_scores)(const void* x, int64_t ldx, int64_t 
   if (centres) {
     if (C < 1 || C > GAUSS_MAX_C || !pred || !lse || !nearest || !dmin) return CCLIP_ERR_ARG;
   } else if (!z || offset || d2 || C != 0) return CCLIP_ERR_ARG;
-  if ((ldx & 7) || ldx < D || ((uintptr_t)x & 15) || ((uintptr_t)workspace & 15)) return CCLIP_ERR_ARG;
+  if (!score_operand_ok(x, ldx, D) || ((uintptr_t)workspace & 15)) return CCLIP_ERR_ARG;
   if (((uintptr_t)T | (uintptr_t)t0 | (uintptr_t)centres | (uintptr_t)offset | (uintptr_t)pred | (uintptr_t)lse | (uintptr_t)nearest |
        (uintptr_t)dmin | (uintptr_t)d2 | (uintptr_t)z) & 3)
     return CCLIP_ERR_ARG;
-  const int rpad = (R + 15) / 16 * 16;
-  if (workspace_bytes < (int64_t)4 * rpad * D) return CCLIP_ERR_ARG;
-  const long cells = (long)rpad * D;
-  hipLaunchKernelGGL(gauss_prep_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, T, R, D, rpad, (bf16*)workspace);
+  if (workspace_bytes < (int64_t)4 * pair_image_rows(R) * D) return CCLIP_ERR_ARG;
+  pair_image_launch(T, R, D, workspace, stream);
   GaussArgs a;
   a.x = (const bf16*)x; a.img = (const bf16*)workspace; a.ldx = ldx;
   a.Q = (int)Q; a.D = D; a.R = R; a.C = centres ? C : 0;

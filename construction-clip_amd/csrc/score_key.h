@@ -2,7 +2,8 @@
 // embed_topk.hip and lm_score.hip (through score_tiles.h) rank by score_key, NaN below every number; caption_select.hip and
 // sample_rows.hip rank by mono_bits alone, a total order on every bit pattern in which a NaN keeps the place of its bits.
 // Also the cross-lane steps on such keys and on per-row sums: the 64-bit xor shuffle, and the butterfly over the 16 lanes
-// li = 0 .. 15 of a lane group in the fixed order xor 1, 2, 4, 8 (both partners compute the same bits; float sums depend on it).
+// li = 0 .. 15 of a lane group in the fixed order xor 1, 2, 4, 8 (both partners compute the same bits; float sums depend on it),
+// and the sum over a 256-thread work-group.  (Not in cclip_common.h: the tuned GEMM table is keyed by that file's bytes.)
 #pragma once
 #include "cclip_common.h"
 
@@ -36,6 +37,16 @@ __device__ __forceinline__ T group_sum(T v) {
 #pragma unroll
   for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// The sum of one value per thread of a 256-thread work-group, in every thread, in a fixed tree: the xor butterfly inside a wave
+// (every lane holds the same bits), then the four waves in ascending order through red (4 floats of LDS).  A second call on the
+// same red needs a barrier in between.
+__device__ __forceinline__ float block_sum4(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 }  // namespace CCLIP_NS

@@ -1,7 +1,8 @@
 // What the streamed-score kernels on score_tiles.h share beyond its parts.
 // Host side, used by every one of them (embed_topk, embed_range, embed_kmeans assign, embed_hub, embed_cache, embed_probe
-// forward, lm_score, mst nearest; embed_cache_bwd takes the checks):
+// forward, lm_score, mst nearest; the two-product kernels on score_pair.h take the checks):
 //   gallery_splits  how the streamed rows are cut into splits
+//   row_parts       how the streamed rows are cut into parts with one fp32 partial each (embed_probe backward, embed_moments)
 //   score_dispatch  (D, wide) -> <KSMAX, MT, GT>, with or without the 768 rung
 //   sweep_launch    grid = row blocks x splits, its 2^31 guard, LDS for the tile buffers
 //   segment_of, clamp_index, score_rows_ok   the small change of the same kernels
@@ -15,7 +16,8 @@
 // lm_score (two buffers, rows counted in int from zero) were written on a stream_tiles that also served them and measured
 // slower there than on their own loops - range 4 %, top-k about 1 %, lm_score 0.5 %, cache 4 % at its small shape - with no
 // spill and no lost occupancy; embed_probe's forward took up to 47 more registers.  embed_cache_bwd and embed_probe's backward
-// stream the OTHER operand with their own products, fetch in another place and rewrite the staged tile before the store.
+// stream the OTHER operand with their own products, fetch in another place and rewrite the staged tile before the store; what
+// they, concept_codes and embed_moments share is functions, not a loop: score_pair.h.
 //
 // Rows are counted in long from the work-group's first row (row0), so that no sum of a row index comes near 2^31 whatever N is.
 // Rows beyond the last are loaded clamped - never out of bounds - and row_live says which to store.
@@ -126,6 +128,18 @@ static inline void gallery_splits(int64_t N, int64_t blocks, int64_t groups, int
   const int64_t rows = ((N + s - 1) / s + 63) / 64 * 64;
   s = (N + rows - 1) / rows;
   *splits = (int)s; *rows_per_split = (int)rows;
+}
+
+// Row parts of the kernels that split the streamed rows over the grid and write one fp32 partial per part (embed_probe's
+// backward, embed_moments): N rows in tiles of 32, a part is tpp consecutive tiles.  As many parts as keep the partials within
+// 32 MB at bytes_per_part each, at most 1024, and a part at least 8 tiles = 256 rows; no empty part.  Of its arguments alone.
+static inline void row_parts(int64_t N, int64_t bytes_per_part, int* ntiles, int* tpp, int* parts) {
+  *ntiles = (int)((N + 31) / 32);
+  int64_t pmax = (32ll << 20) / bytes_per_part;
+  pmax = pmax < 1 ? 1 : pmax > 1024 ? 1024 : pmax;
+  const int64_t need = (*ntiles + pmax - 1) / pmax;
+  *tpp = (int)(need < 8 ? 8 : need);
+  *parts = (*ntiles + *tpp - 1) / *tpp;
 }
 
 // The variants: k-steps the A fragments are sized for, operand tiles per wave (two halve the LDS reads per MFMA, same bits

@@ -1,5 +1,5 @@
-// The streamed-tile parts of the scoring kernels (every kernel on score_sweep.h, plus the backward kernels of
-// embed_cache_bwd.hip and embed_probe.hip, which run their own tile loops on these parts).  A work-group of four waves keeps 64 * MT
+// The streamed-tile parts of the scoring kernels (every kernel on score_sweep.h, plus the two-product kernels on
+// score_pair.h, which run their own tile loops on these parts).  A work-group of four waves keeps 64 * MT
 // operand rows as MFMA A fragments in registers and streams a [rows][D] 16-bit matrix through LDS in tiles of GT rows:
 // row-major, 16-byte chunk c of row r stored at chunk c ^ (r & mask) - the swizzle of attention_tiles.h at row length D,
 // conflict-free for the B-fragment reads.  Lane (li, g) of a wave holds the operand rows 4g .. 4g+3 against tile row
@@ -91,17 +91,21 @@ __device__ __forceinline__ void tile_multiply(f32x4 (&acc)[MT][GT / 16], const b
 
 // Launch of a 256-thread partial kernel with `lds` bytes of dynamic LDS; above 64 KB the kernel has to be told first
 template <class Args>
-static int score_launch(void (*kernel)(const Args), unsigned grid, size_t lds, const Args& a, hipStream_t stream) {
+static int score_launch(void (*kernel)(const Args), dim3 grid, size_t lds, const Args& a, hipStream_t stream) {
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return CCLIP_ERR_LAUNCH;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, a);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, a);
   return CCLIP_OK;
 }
 
-// The contract of the two 16-bit operands [rows][D] with row strides lda, ldb (elements) that every C entry checks
+// The contract every C entry checks: the row length D, one 16-bit operand [rows][D] with row stride ldx (elements), two of them
+static inline bool score_dim_ok(int32_t D) { return !(D < 32 || (D & 31) || D > 1024); }
+static inline bool score_operand_ok(const void* x, int64_t ldx, int32_t D) { return !((ldx & 7) || ldx < D || ((uintptr_t)x & 15)); }
 static inline bool score_operands_ok(const void* a, int64_t lda, const void* b, int64_t ldb, int32_t D) {
-  return !(D < 32 || (D & 31) || D > 1024 || (lda & 7) || (ldb & 7) || lda < D || ldb < D || (((uintptr_t)a | (uintptr_t)b) & 15));
+  return score_dim_ok(D) && score_operand_ok(a, lda, D) && score_operand_ok(b, ldb, D);
 }
+// a scalar parameter that is a number: neither NaN nor an infinity
+static inline bool score_finite(float v) { return v == v && v < __builtin_huge_valf() && v > -__builtin_huge_valf(); }
 
 }  // namespace CCLIP_NS

@@ -24,7 +24,7 @@
 //
 // Step (tsne_step_kernel): one thread per row walks its CSR entries in ascending order.  Nothing here is contracted by the
 // compiler; the fmas are written out.
-#include "cclip_common.h"
+#include "score_key.h"
 #include "../../include/cclip_hip.h"
 
 #pragma clang fp contract(off)
@@ -38,6 +38,8 @@
 #define TSNE_MAX_K 63
 
 namespace cclip_tsne {
+
+using CCLIP_NS::block_sum4;                       // the fixed-tree sum of 256 values (score_key.h)
 
 // ---- affinities -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TA_BLOCK) void tsne_affinity_kernel(const float* __restrict__ scores, long ld, int N, int k,
@@ -162,14 +164,6 @@ __global__ __launch_bounds__(TSNE_ROWS) void tsne_repulsion_kernel(const float* 
   }
 }
 
-// the sum of 256 values in a fixed tree: xor butterfly inside a wave (every lane the same bits), the four waves in order
-__device__ __forceinline__ float block_sum256(float v, float* wsum) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-
 __global__ __launch_bounds__(256) void tsne_merge_kernel(const float* __restrict__ ws, int N, int splits, float* __restrict__ zrow,
                                                          float* __restrict__ rep, float* __restrict__ zblock) {
   __shared__ float wsum[4];
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(256) void tsne_merge_kernel(const float* __restrict
     rep[2 * row] = fx;
     rep[2 * row + 1] = fy;
   }
-  const float b = block_sum256(z, wsum);
+  const float b = block_sum4(z, wsum);
   if (threadIdx.x == 0) zblock[blockIdx.x] = b;
 }
 
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256) void tsne_total_kernel(const float* __restrict
   __shared__ float wsum[4];
   float v = 0.0f;
   for (int b = threadIdx.x; b < nblocks; b += 256) v += zblock[b];
-  const float t = block_sum256(v, wsum);
+  const float t = block_sum4(v, wsum);
   if (threadIdx.x == 0) z_sum[0] = t;
 }
 

@@ -17,7 +17,13 @@ The other kernels on csrc/score_sweep.h - similarity_range (self-join on and off
 backward, probe forward and backward, mreach_nearest and mst_boruvka - run over SWEEP_SHAPES in both dtypes: one D per
 dispatch rung and a D that is not a power-of-two number of chunks, 1 / 63 / 65 / 129 operand rows (a partly filled wave, an
 idle wave, both row-tile counts), 1 .. 3000 streamed rows (a partial sub-tile, a partial tile, two tiles, several splits), and
-one case each with padded row strides."""
+one case each with padded row strides.
+The kernels on csrc/score_pair.h and the other users of its host contract and of block_sum4 - class_moments, gauss_scores (with
+centres and as the PCA transform), concept_codes (0, 1 and 5 iterations over 1, 33 and 75 concepts), kmeans_update, coreset_greedy
+(with and without weights), probe forward and backward - run in both dtypes over 1 / 63 / 65 / 257 rows x D = 32, 160, 512, 1024
+(every <KSMAX, DS, PRE, MT> variant and a D that is not a power-of-two number of chunks), with 2, 5, 33 and 130 classes dealt so
+that every D meets every count (the probe's 1, 2 and 4 class blocks a work-group), one case with padded row strides and one
+with a NaN row under an ignored label and an infinity in a live row; tsne_repulsion over 1 .. 3000 points."""
 import argparse
 import os
 import sys
@@ -36,6 +42,8 @@ ROW_R, ROW_C = 9, (1, 63, 64, 255, 256, 257, 300)
 # (operand rows, streamed rows, D)
 SWEEP_SHAPES = [(1, 1, 32), (63, 17, 128), (65, 64, 160), (129, 65, 512), (65, 1025, 768), (129, 3000, 1024), (129, 3000, 128),
                 (1, 1025, 512), (63, 3000, 160)]
+# rows, D, classes and transform rows of pair_cases
+PAIR_ROWS, PAIR_D, PAIR_C, PAIR_T = (1, 63, 65, 257), (32, 160, 512, 1024), (2, 5, 33, 130), (5, 33, 64, 130)
 
 
 def rnd(seed, *shape, scale=1.0):
@@ -126,6 +134,56 @@ def sweep_cases():
             comp = torch.randint(0, 3, (S,), generator=gen).to(torch.int32).cuda()
             yield f"mreach_nearest/{name}", {"keys": ops.mreach_nearest(g, core, comp)}
             yield f"mst_boruvka/{name}", dict(zip(("u", "v", "m"), ops.mst_boruvka(g, core)))
+
+
+def pair_cases():
+    """the two-product kernels on csrc/score_pair.h and the other users of its host contract and of block_sum4"""
+    shapes = [(R, D, PAIR_C[(i + j) % 4], PAIR_T[(i + j) % 4]) for i, R in enumerate(PAIR_ROWS) for j, D in enumerate(PAIR_D)]
+    special = (65, 160, 5, 33)
+    for dt, tag in DTYPES:
+        for i, (R, D, C, Rt) in enumerate(shapes + [special, special]):
+            kind = ("", "/padded", "/nan_row")[max(0, i - len(shapes) + 1)]
+            name = f"{tag}/{R}x{D}c{C}{kind}"
+            gen = torch.Generator().manual_seed(2000 + i)
+            x = unit(2100 + i, R, D, dt)
+            y = torch.randint(-1, C + 1, (R,), generator=gen).to(torch.int32)       # -1 and C: dropped / ignored rows
+            if kind == "/padded":
+                x = padded(x, 24)
+            if kind == "/nan_row":
+                x[7], y[7] = float("nan"), -1                       # ignored by the probe and the moments; gauss, concepts keep it in its row
+                x[9, 3] = float("inf")                              # a live row: the moments' flags
+                y[9] = 1
+            y = y.cuda()
+            yield f"class_moments/{name}", dict(zip(("count", "sum", "gram"), ops.class_moments(x, y, C)))
+            if i % 4 == 0:
+                yield f"class_moments/{name}/no_labels", dict(zip(("count", "sum", "gram"), ops.class_moments(x, None, 1)))
+            T, t0 = rnd(2200 + i, Rt, D, scale=0.5).cuda(), rnd(2300 + i, Rt).cuda()
+            centres, offset = rnd(2400 + i, C, Rt, scale=0.3).cuda(), rnd(2500 + i, C).cuda()
+            names = ("pred", "lse", "nearest", "dmin", "d2", "z")
+            yield f"gauss_scores/{name}", dict(zip(names, ops.gauss_scores(x, T, t0=t0, centres=centres, offset=offset, want_d2=True,
+                                                                          want_z=True)))
+            yield f"gauss_scores/{name}/pca", dict(zip(names, ops.gauss_scores(x, T, want_z=True)))
+            for V in (1, 33, 75):
+                c = unit(2600 + i + V, V, D, dt)
+                for iters in (0, 1, 5):
+                    out = ops.concept_codes(x, c, 0.05, 0.3, iters)
+                    yield f"concept_codes/{name}/V{V}i{iters}", dict(zip(("w", "resid2", "l1norm", "nnz", "delta", "kkt"), out))
+            K = min(C, R)
+            assign = torch.randint(0, K, (R,), generator=gen).cuda()
+            yield f"kmeans_update/{name}", dict(zip(("c", "norm", "count"), ops.kmeans_update(x, assign, K, unit(2700 + i, K, D, dt))))
+            for wtag, weight in (("", None), ("/weight", torch.rand(R, generator=gen).cuda())):
+                mind = torch.full((R,), float("inf"), device="cuda")
+                owner = torch.full((R,), -1, dtype=torch.int32, device="cuda")
+                picks, radius, _ = ops.coreset_greedy(x, mind, owner, min(R, 6), first=R // 2, weight=weight)
+                yield f"coreset_greedy/{name}{wtag}", {"picks": picks, "radius": radius, "mind": mind, "owner": owner}
+            W, bias = rnd(2800 + i, C, D, scale=0.5).cuda(), rnd(2900 + i, C).cuda()
+            rw = torch.rand(R, generator=gen).cuda()
+            lse, loss, pred, logits = ops.probe_forward(x, W, bias, y, row_weight=rw, logits=True)
+            yield f"probe_fwd/{name}", {"lse": lse, "loss": loss, "pred": pred, "logits": logits}
+            dW, db, obj = ops.probe_backward(x, W, bias, y, lse, 1.0 / R, 1e-3, row_weight=rw, loss=loss)
+            yield f"probe_bwd/{name}", {"dW": dW, "db": db, "objective": obj}
+    for N in (1, 63, 65, 257, 3000):                                # tsne_merge_kernel and tsne_total_kernel: one block, a partial one, several
+        yield f"tsne_repulsion/N{N}", dict(zip(("zrow", "rep", "z"), ops.tsne_repulsion(rnd(3000 + N, N, 2, scale=3.0).cuda())))
 
 
 def row_inputs(C, seed):
@@ -227,7 +285,7 @@ def grid_cases():
 
 def cases():
     """(name, {tensor name: tensor}) of every launch, in a fixed order"""
-    for gen in (topk_cases, lm_cases, sweep_cases, row_cases, select_cases, sample_cases, grid_cases):
+    for gen in (topk_cases, lm_cases, sweep_cases, pair_cases, row_cases, select_cases, sample_cases, grid_cases):
         yield from gen()
 
 
