@@ -2041,6 +2041,149 @@ def dense_stitch(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: i
           "cclip_dense_stitch")
 
 
+REFINE_MAX_DILATIONS, REFINE_MAX_DILATION, REFINE_DEFAULT_DILATIONS = 6, 24, (1, 2, 4, 8, 12, 24)
+_INT32_MAX = 2 ** 31 - 1
+
+
+def dense_stitch_maps(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: int, maps: torch.Tensor, *,
+                      cover: Optional[torch.Tensor] = None) -> None:
+    """The stitch's averaged class maps themselves (include/cclip_hip.h, cclip_dense_stitch_maps): probs fp32 [K, C, g, g] and boxes
+    int32 [K, 4] as dense_stitch takes them -> maps fp32 [C, height, width] = u_c (0 where no window covers the pixel) and, when
+    given, cover uint8 [height, width].  Their maximum over c is dense_stitch's conf, bit for bit.  Contiguous cuda tensors on
+    one device; no CPU path.  Two calls give equal bytes."""
+    fname = "dense_stitch_maps"
+    tensors = [(probs, "probs", torch.float32), (boxes, "boxes", torch.int32), (maps, "maps", torch.float32)]
+    if cover is not None:
+        tensors.append((cover, "cover", torch.uint8))
+    _cuda_operands(fname, tensors, probs)
+    if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
+        raise ValueError(f"{fname}: probs must be [K, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
+    K, C, g, _ = probs.shape
+    if K > DENSE_MAX_WINDOWS:
+        raise ValueError(f"{fname}: probs holds {K} windows; at most {DENSE_MAX_WINDOWS}")
+    if C > DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: probs holds {C} classes; at most {DENSE_MAX_CLASSES} (label 255 means none)")
+    if tuple(boxes.shape) != (K, 4):
+        raise ValueError(f"{fname}: boxes must be [{K}, 4] as (x0, y0, x1, y1), got {tuple(boxes.shape)}")
+    if int(height) != height or int(width) != width or not 1 <= height <= OVERLAY_MAX_SIDE or not 1 <= width <= OVERLAY_MAX_SIDE \
+            or g > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: height {height}, width {width}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    H, W = int(height), int(width)
+    if C * H * W > _INT32_MAX:
+        raise ValueError(f"{fname}: {C} x {H} x {W} map values; at most 2^31 - 1")
+    if tuple(maps.shape) != (C, H, W):
+        raise ValueError(f"{fname}: maps must be [{C}, {H}, {W}], got {tuple(maps.shape)}")
+    if cover is not None and tuple(cover.shape) != (H, W):
+        raise ValueError(f"{fname}: cover must be [{H}, {W}], got {tuple(cover.shape)}")
+    if probs.data_ptr() % 4 or maps.data_ptr() % 4 or boxes.data_ptr() % 4:
+        raise ValueError(f"{fname}: probs, maps and boxes must start on a 4-byte boundary")
+    check(lib.cclip_dense_stitch_maps(_p(probs), c_int(K), c_int(C), c_int(g), _p(boxes), c_int(H), c_int(W), _p(maps), _p(cover),
+                                      _stream()), "cclip_dense_stitch_maps")
+
+
+def _refine_maps_shape(fname: str, maps, name: str = "maps"):
+    if maps.dim() != 4 or min(maps.shape) < 1:
+        raise ValueError(f"{fname}: {name} must be [B, C, H, W] with no empty dimension, got {tuple(maps.shape)}")
+    B, C, H, W = maps.shape
+    if C > DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: {name} holds {C} classes; at most {DENSE_MAX_CLASSES} (label 255 means none)")
+    if H > OVERLAY_MAX_SIDE or W > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: height {H}, width {W}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    if B * C * H * W > _INT32_MAX:
+        raise ValueError(f"{fname}: {B} x {C} x {H} x {W} map values; at most 2^31 - 1")
+    return B, C, H, W
+
+
+def dense_maps_label(maps: torch.Tensor, labels: torch.Tensor, conf: torch.Tensor, *, min_conf: float = 0.0,
+                     cover: Optional[torch.Tensor] = None, overlay: Optional[torch.Tensor] = None,
+                     palette: Optional[torch.Tensor] = None, photo: Optional[torch.Tensor] = None, alpha8: int = 256) -> None:
+    """Labels, conf and the picture of class maps at the output size (include/cclip_hip.h, cclip_dense_maps_label): maps fp32
+    [B, C, H, W] -> labels uint8 [B, H, W] (the lowest arg-max class, 255 below min_conf), conf fp32 [B, H, W] and overlay uint8
+    [B, H, W, 3] as dense_label_map makes it.  cover uint8 [B, H, W] is an INPUT: where it is 0 the pixel gets label 255 and conf
+    0.  Contiguous cuda tensors on one device; no CPU path.  Two calls give equal bytes."""
+    fname = "dense_maps_label"
+    tensors = [(maps, "maps", torch.float32), (labels, "labels", torch.uint8), (conf, "conf", torch.float32)]
+    for t, name in ((cover, "cover"), (overlay, "overlay"), (palette, "palette"), (photo, "photo")):
+        if t is not None:
+            tensors.append((t, name, torch.uint8))
+    _cuda_operands(fname, tensors, maps)
+    B, C, H, W = _refine_maps_shape(fname, maps)
+    _label_outputs(fname, (B, H, W), labels, conf, cover, overlay, palette, photo, alpha8)
+    if maps.data_ptr() % 4 or conf.data_ptr() % 4:
+        raise ValueError(f"{fname}: maps and conf must start on a 4-byte boundary")
+    check(lib.cclip_dense_maps_label(_p(maps), c_int(B), c_int(C), c_int(H), c_int(W), _p(cover), c_float(float(min_conf)), _p(labels),
+                                     _p(conf), _p(palette), _p(photo), c_int(int(alpha8)), _p(overlay), _stream()),
+          "cclip_dense_maps_label")
+
+
+def refine_dilations(fname: str, dilations) -> tuple:
+    """the dilations as a tuple of ints, checked: 1 to 6 of them, each in [1, 24]"""
+    try:
+        ds = tuple(dilations)
+    except TypeError:
+        raise ValueError(f"{fname}: dilations must be a sequence of integers, got {dilations!r}") from None
+    if not 1 <= len(ds) <= REFINE_MAX_DILATIONS:
+        raise ValueError(f"{fname}: {len(ds)} dilations; between 1 and {REFINE_MAX_DILATIONS}")
+    for d in ds:
+        if isinstance(d, bool) or int(d) != d or not 1 <= d <= REFINE_MAX_DILATION:
+            raise ValueError(f"{fname}: dilation {d!r}: each must be an integer in [1, {REFINE_MAX_DILATION}]")
+    return tuple(int(d) for d in ds)
+
+
+def _refine_guide(fname: str, guide, B: int, H: int, W: int) -> None:
+    if tuple(guide.shape) != (B, H, W, 3):
+        raise ValueError(f"{fname}: guide must be [{B}, {H}, {W}, 3] (the photo at the maps' size), got {tuple(guide.shape)}")
+
+
+def dense_refine_prepare(guide: torch.Tensor, dilations, key: torch.Tensor) -> None:
+    """The per-pixel key of the refinement (include/cclip_hip.h, cclip_dense_refine_prepare): guide uint8 [B, H, W, 3] -> key fp32
+    [B, H, W, 4] = the three factors 1 / (1e-8 + 0.1 sigma_k) and the log-normaliser of the 8 D neighbour logits.  Contiguous
+    cuda tensors on one device; no CPU path.  Two calls give equal bytes."""
+    fname = "dense_refine_prepare"
+    ds = refine_dilations(fname, dilations)
+    _cuda_operands(fname, [(guide, "guide", torch.uint8), (key, "key", torch.float32)], guide)
+    if guide.dim() != 4 or guide.shape[3] != 3 or min(guide.shape) < 1:
+        raise ValueError(f"{fname}: guide must be [B, H, W, 3] with no empty dimension, got {tuple(guide.shape)}")
+    B, H, W, _ = guide.shape
+    if H > OVERLAY_MAX_SIDE or W > OVERLAY_MAX_SIDE or B * H * W > _INT32_MAX:
+        raise ValueError(f"{fname}: height {H}, width {W}: each must lie in [1, {OVERLAY_MAX_SIDE}], and B H W <= 2^31 - 1")
+    if tuple(key.shape) != (B, H, W, 4):
+        raise ValueError(f"{fname}: key must be [{B}, {H}, {W}, 4], got {tuple(key.shape)}")
+    if key.data_ptr() % 16:
+        raise ValueError(f"{fname}: key must start on a 16-byte boundary")
+    check(lib.cclip_dense_refine_prepare(_p(guide), c_int(B), c_int(H), c_int(W), (c_int * len(ds))(*ds), c_int(len(ds)), _p(key),
+                                         _stream()), "cclip_dense_refine_prepare")
+
+
+def dense_refine_step(maps_in: torch.Tensor, maps_out: torch.Tensor, guide: torch.Tensor, key: torch.Tensor, dilations) -> None:
+    """One iteration of the refinement (include/cclip_hip.h, cclip_dense_refine_step): maps_out[b, c, p] = sum over the 8 D
+    neighbours q_n of p, in ascending n, of exp(a_n(p) - L(p)) maps_in[b, c, q_n], with the guide, the key dense_refine_prepare
+    made from it and the same dilations.  maps_in and maps_out fp32 [B, C, H, W], two different buffers.  Contiguous cuda tensors
+    on one device; no CPU path.  Two calls give equal bytes."""
+    fname = "dense_refine_step"
+    ds = refine_dilations(fname, dilations)
+    for t, name in ((maps_in, "maps_in"), (maps_out, "maps_out")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{fname}: {name} must be a [B, C, H, W] tensor, got {tuple(getattr(t, 'shape', ()))}")
+    if maps_in is maps_out or (maps_in.device == maps_out.device and maps_in.data_ptr() == maps_out.data_ptr()):
+        raise ValueError(f"{fname}: maps_in and maps_out must be two buffers (no in-place step)")
+    _cuda_operands(fname, [(maps_in, "maps_in", torch.float32), (maps_out, "maps_out", torch.float32), (guide, "guide", torch.uint8),
+                           (key, "key", torch.float32)], maps_in)
+    B, C, H, W = _refine_maps_shape(fname, maps_in, "maps_in")
+    if tuple(maps_out.shape) != (B, C, H, W):
+        raise ValueError(f"{fname}: maps_out must be [{B}, {C}, {H}, {W}], got {tuple(maps_out.shape)}")
+    _refine_guide(fname, guide, B, H, W)
+    if tuple(key.shape) != (B, H, W, 4):
+        raise ValueError(f"{fname}: key must be [{B}, {H}, {W}, 4], got {tuple(key.shape)}")
+    n = 4 * maps_in.numel()
+    if maps_in.data_ptr() < maps_out.data_ptr() + n and maps_out.data_ptr() < maps_in.data_ptr() + n:
+        raise ValueError(f"{fname}: maps_in and maps_out overlap (no in-place step)")
+    if maps_in.data_ptr() % 4 or maps_out.data_ptr() % 4 or key.data_ptr() % 16:
+        raise ValueError(f"{fname}: the maps must start on a 4-byte boundary, key on a 16-byte boundary")
+    check(lib.cclip_dense_refine_step(_p(maps_in), _p(maps_out), _p(guide), _p(key), c_int(B), c_int(C), c_int(H), c_int(W),
+                                      (c_int * len(ds))(*ds), c_int(len(ds)), _stream()), "cclip_dense_refine_step")
+
+
 COMPONENTS_GROUP = 1024
 
 

@@ -26,4 +26,5 @@ from .regions import encode_regions, classify_regions  # noqa: F401  (embed / ze
 from .dense import segment, dense_features, DenseResult, default_palette  # noqa: F401  (dense zero-shot maps: per-patch class probabilities, label maps)
 from .dense import segment_photo, plan_windows, PhotoDenseResult, label_boxes  # noqa: F401  (whole photos: sliding windows stitched in one launch)
 from .dense import label_components, ComponentsResult  # noqa: F401  (instances: connected components of a label map, on the device)
+from .dense import refine_maps, RefinedDenseResult  # noqa: F401  (boundaries: image-guided refinement of the class maps, PAMR)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

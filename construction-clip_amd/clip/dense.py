@@ -19,6 +19,11 @@ sliding-window inference, as MaskCLIP, SCLIP and ClearCLIP are evaluated: `plan_
 photo (several sizes for a multi-scale ensemble), `segment_photo` runs the tower on all of them and ops.dense_stitch
 (csrc/dense_stitch.hip) averages the class probabilities where windows overlap, straight into the photo-sized label map,
 confidence map and picture.  `segment(size=(height, width))` is the one-window case: a non-square label map.
+
+Boundaries.  The class maps are a few patches wide and bilinearly stretched: their label boundaries are smooth blobs that ignore
+the photo's edges.  `refine_maps` / `.refine(photo)` run pixel-adaptive mask refinement (PAMR; Araslanov & Roth, CVPR 2020, the
+usual post-processing of training-free dense CLIP) on the maps at the output size: a few iterations of a local propagation
+whose weights come from the photo's own colours (csrc/dense_refine.hip).  No training, no extra model.
 """
 from __future__ import annotations
 
@@ -116,6 +121,22 @@ class DenseResult:
         """one record per connected component: components(connectivity).instances(...) with this result's class names"""
         return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
                                                        class_names=self.class_names)
+
+    def refine(self, photo, *, dilations: Sequence[int] = ops.REFINE_DEFAULT_DILATIONS, iterations: int = 10,
+               min_conf: Optional[float] = None) -> "RefinedDenseResult":
+        """Snap the class maps to the photo's edges: the maps stretched to the labels' size (ops.dense_stitch_maps, one window
+        over the picture per image), `refine_maps` under `photo` (uint8 [B, S, S, 3] or [S, S, 3], already at the map's size, as
+        overlay(photo=) takes it), ops.dense_maps_label.  min_conf: default this result's.  Memory: two C x H x W fp32 buffers
+        plus 16 bytes per pixel and image - about 0.9 GB for 12 megapixels and nine classes; label a smaller picture
+        (segment_images.py --max-side) when that is too much."""
+        B, H, W = self.labels.shape
+        dev = self.probs.device
+        guide = _refine_guide(photo, (B, H, W, 3), dev)
+        maps = torch.empty(B, self.n_classes, H, W, device=dev, dtype=torch.float32)
+        box = _device_boxes(np.array([[0, 0, W, H]]), dev)
+        for b in range(B):
+            ops.dense_stitch_maps(self.probs[b:b + 1], box, H, W, maps[b])
+        return _refined(maps, guide, None, self.class_names, self.min_conf if min_conf is None else min_conf, dilations, iterations)
 
 
 def class_features(model, classes: Union[torch.Tensor, Sequence[str]], tokenize: Optional[Callable] = None):
@@ -420,6 +441,145 @@ class PhotoDenseResult:
         """one record per connected component: components(connectivity).instances(...) with this result's class names"""
         return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
                                                        class_names=self.class_names)
+
+    def refine(self, photo, *, dilations: Sequence[int] = ops.REFINE_DEFAULT_DILATIONS, iterations: int = 10,
+               min_conf: Optional[float] = None) -> "RefinedDenseResult":
+        """Snap the stitched class maps to the photo's edges: ops.dense_stitch_maps over all windows, `refine_maps` under `photo`
+        (the uint8 [H, W, 3] photo itself, as overlay(photo=) takes it), ops.dense_maps_label.  Pixels that no window covers
+        enter as zeros and may receive a class from their neighbours.  min_conf: default this result's.  Memory: two
+        C x H x W fp32 buffers plus 16 bytes per pixel - about 0.9 GB for 12 megapixels and nine classes; label a smaller
+        picture (segment_images.py --max-side) when that is too much."""
+        H, W = self.labels.shape
+        dev = self.probs.device
+        guide = _refine_guide(photo, (H, W, 3), dev)
+        maps = torch.empty(1, self.n_classes, H, W, device=dev, dtype=torch.float32)
+        ops.dense_stitch_maps(self.probs, _device_boxes(self.boxes.numpy(), dev), H, W, maps[0])
+        return _refined(maps, guide[None], (H, W), self.class_names, self.min_conf if min_conf is None else min_conf, dilations,
+                        iterations)
+
+
+REFINE_MAX_ITERATIONS = 64
+
+
+def _refine_guide(photo, shape, dev) -> torch.Tensor:
+    """the photo of refine(photo): checked as overlay(photo=) checks its own, on the device"""
+    if photo is None:
+        raise ValueError(f"overlay: photo must be a uint8 tensor {list(shape)}")
+    return _overlay_inputs(0.0, None, 0, photo, shape, dev)[1]
+
+
+def refine_maps(maps: torch.Tensor, guide: torch.Tensor, *, dilations: Sequence[int] = ops.REFINE_DEFAULT_DILATIONS,
+                iterations: int = 10) -> torch.Tensor:
+    """Pixel-adaptive mask refinement of class maps at the output size: maps fp32 [B, C, H, W] or [C, H, W], guide uint8
+    [B, H, W, 3] or [H, W, 3] (the photo at the same size) -> refined maps of the same shape, a new tensor.  Each of the
+    `iterations` (1 .. 64) steps replaces a pixel's class values by a weighted mean over its 8 neighbours at every dilation (1
+    to 6 of them, each 1 .. 24, coordinates clamped to the image); the weights are a softmax of minus the colour difference to
+    the neighbour over a tenth of the local standard deviation, so values spread inside a region of like colour and stop at an
+    edge.  Rows of weights sum to 1: a constant map stays constant and maps that sum to 1 over the classes keep doing so, up to
+    rounding.  One ops.dense_refine_prepare launch, then one ops.dense_refine_step per iteration between two buffers.  HIP only."""
+    fname = "refine_maps"
+    if not isinstance(maps, torch.Tensor) or maps.dim() not in (3, 4) or maps.dtype != torch.float32:
+        raise ValueError(f"{fname}: maps must be an fp32 [B, C, H, W] or [C, H, W] tensor, got "
+                         f"{getattr(maps, 'dtype', type(maps))} {tuple(getattr(maps, 'shape', ()))}")
+    if not isinstance(guide, torch.Tensor) or guide.dtype != torch.uint8 or guide.dim() != maps.dim():
+        raise ValueError(f"{fname}: guide must be a uint8 tensor {'[B, H, W, 3]' if maps.dim() == 4 else '[H, W, 3]'}, got "
+                         f"{getattr(guide, 'dtype', type(guide))} {tuple(getattr(guide, 'shape', ()))}")
+    m4 = maps if maps.dim() == 4 else maps.unsqueeze(0)
+    g4 = guide if guide.dim() == 4 else guide.unsqueeze(0)
+    B, C, H, W = m4.shape
+    if tuple(g4.shape) != (B, H, W, 3):
+        raise ValueError(f"{fname}: guide must be {[B, H, W, 3] if maps.dim() == 4 else [H, W, 3]} for maps {tuple(maps.shape)}, "
+                         f"got {tuple(guide.shape)}")
+    ds = ops.refine_dilations(fname, dilations)
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= iterations <= REFINE_MAX_ITERATIONS:
+        raise ValueError(f"{fname}: iterations must be an integer in [1, {REFINE_MAX_ITERATIONS}], got {iterations!r}")
+    if not maps.is_cuda:
+        raise ValueError(f"{fname}: maps must be a cuda tensor, got {maps.device} (no CPU path)")
+    return _refine_run(m4, g4.to(maps.device), ds, int(iterations), own=False).view(maps.shape)
+
+
+def _refine_run(m4: torch.Tensor, g4: torch.Tensor, ds, iterations: int, own: bool) -> torch.Tensor:
+    """prepare, then `iterations` steps between two buffers.  own: m4 may serve as the second buffer (it is overwritten);
+    otherwise the caller's tensor is read once and two buffers are made."""
+    mc, g4 = m4.contiguous(), g4.contiguous()
+    own = own or mc is not m4
+    key = torch.empty(*g4.shape[:3], 4, device=mc.device, dtype=torch.float32)
+    ops.dense_refine_prepare(g4, ds, key)
+    cur = torch.empty_like(mc)
+    ops.dense_refine_step(mc, cur, g4, key, ds)
+    nxt = (mc if own else torch.empty_like(mc)) if iterations > 1 else None
+    for _ in range(iterations - 1):
+        ops.dense_refine_step(cur, nxt, g4, key, ds)
+        cur, nxt = nxt, cur
+    return cur
+
+
+@dataclass
+class RefinedDenseResult:
+    """Class maps refined under a photo (`DenseResult.refine`, `PhotoDenseResult.refine`) and what they label."""
+    maps: torch.Tensor                   # fp32 [B, C, H, W], or [C, H, W] from a PhotoDenseResult
+    labels: torch.Tensor                 # uint8 [B, H, W] / [H, W]; 255 = none (conf < min_conf)
+    conf: torch.Tensor                   # fp32, the labels' shape
+    class_names: Optional[List[str]]
+    min_conf: float = 0.0
+    dilations: Tuple[int, ...] = ops.REFINE_DEFAULT_DILATIONS
+    iterations: int = 10
+
+    @property
+    def n_classes(self) -> int:
+        return self.maps.shape[-3]
+
+    def _maps4(self) -> torch.Tensor:
+        return self.maps if self.maps.dim() == 4 else self.maps.unsqueeze(0)
+
+    def overlay(self, photo=None, alpha: float = 0.5, palette: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8, the labels' shape + [3]: the palette colour of every pixel's label, blended over `photo` (at the map's size) as
+        the other results' overlays are.  Re-runs ops.dense_maps_label."""
+        dev = self.maps.device
+        shape = (*self.labels.shape, 3)
+        pal, photo, a8 = _overlay_inputs(alpha, palette, self.n_classes, photo, shape, dev)
+        out = torch.empty(shape, device=dev, dtype=torch.uint8)
+        m4 = self._maps4()
+        pic = (m4.shape[0], *shape[-3:])
+        ops.dense_maps_label(m4, torch.empty_like(self.labels).view(pic[:3]), torch.empty_like(self.conf).view(pic[:3]),
+                             min_conf=self.min_conf, overlay=out.view(pic), palette=pal, photo=None if photo is None else photo.view(pic),
+                             alpha8=a8)
+        return out
+
+    def area_fractions(self) -> torch.Tensor:
+        """fp64 [..., C + 1]: the share of pixels per class, "none" last; integer counts divided once by H * W"""
+        return _area_fractions(self.labels, self.n_classes)
+
+    def top_class(self):
+        """the class with the largest area (None when no pixel has a class): a list per image, one value for a single photo"""
+        top = _top_classes(self.area_fractions())
+        return top if self.labels.dim() == 3 else top[0]
+
+    def components(self, connectivity: int = 4) -> ComponentsResult:
+        """the connected components of the refined label maps with their mean confidences (`label_components`)"""
+        return label_components(self.labels, self.conf, connectivity=connectivity)
+
+    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
+                  connectivity: int = 4) -> List[dict]:
+        """one record per connected component: components(connectivity).instances(...) with this result's class names"""
+        return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
+                                                       class_names=self.class_names)
+
+
+def _refined(maps, guide, shape, class_names, min_conf, dilations, iterations) -> RefinedDenseResult:
+    """refine maps [B, C, H, W] under guide [B, H, W, 3] and label them; `shape` = (H, W) gives a single photo's result"""
+    ds = ops.refine_dilations("refine", dilations)
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= iterations <= REFINE_MAX_ITERATIONS:
+        raise ValueError(f"refine: iterations must be an integer in [1, {REFINE_MAX_ITERATIONS}], got {iterations!r}")
+    out = _refine_run(maps, guide, ds, int(iterations), own=True)          # `maps` is this module's own buffer: the second of the two
+    B, C, H, W = out.shape
+    labels = torch.empty(B, H, W, device=out.device, dtype=torch.uint8)
+    conf = torch.empty(B, H, W, device=out.device, dtype=torch.float32)
+    ops.dense_maps_label(out, labels, conf, min_conf=min_conf)
+    if shape is not None:
+        out, labels, conf = out[0], labels[0], conf[0]
+    return RefinedDenseResult(maps=out, labels=labels, conf=conf, class_names=class_names, min_conf=float(min_conf),
+                              dilations=ds, iterations=int(iterations))
 
 
 def segment_photo(model, image, classes: Union[torch.Tensor, Sequence[str]], *, window=None, stride=None, mode: str = "value",

@@ -1188,6 +1188,53 @@ int cclip_dense_stitch(const float* probs, int32_t K, int32_t C, int32_t g, cons
                        float min_conf, uint8_t* labels, float* conf, uint8_t* cover, const uint8_t* palette, const uint8_t* photo,
                        int32_t a8, uint8_t* overlay, hipStream_t stream);
 
+/* Image-guided refinement of dense class maps (csrc/dense_refine.hip): pixel-adaptive mask refinement (PAMR; Araslanov & Roth,
+ * CVPR 2020), stated here from the paper's formulas - this text is the contract, no other implementation was compared.
+ *
+ * cclip_dense_stitch_maps: cclip_dense_stitch's inputs (probs [K][C][g][g], device boxes int32 [K][4], H, W) and its coverage,
+ *   sampling and averaging rules, but the averaged maps themselves are written: maps [C][H][W] fp32 = u_c, 0 where no window
+ *   covers the pixel; cover NULL, or uint8 [H][W] = min(n, 255).  max_c maps[c] equals cclip_dense_stitch's conf bit for bit.
+ *   CCLIP_ERR_ARG, nothing launched: probs, boxes or maps NULL; K outside [1, 65535]; C outside [1, 255]; g, H or W outside
+ *   [1, CCLIP_OVERLAY_MAX_SIDE]; C H W > 2^31 - 1; probs, boxes or maps not 4-byte aligned.  cover may have any alignment.
+ *
+ * cclip_dense_maps_label: maps [B][C][H][W] fp32 -> conf [B][H][W] = max_c maps, labels = the LOWEST class reaching it, 255 when
+ *   conf < min_conf; cover NULL, or uint8 [B][H][W] (an INPUT): where it is 0 the pixel gets label 255 and conf 0 whatever the
+ *   maps hold.  overlay, palette, photo, a8 as for cclip_dense_label_map, pictures [B][H][W][3] (the same code,
+ *   csrc/label_pixels.h).  cclip_dense_stitch_maps followed by this call with its cover equals cclip_dense_stitch byte for byte.
+ *   CCLIP_ERR_ARG, nothing launched: maps, labels or conf NULL; B < 1; C outside [1, 255]; H or W outside
+ *   [1, CCLIP_OVERLAY_MAX_SIDE]; B C H W > 2^31 - 1; maps or conf not 4-byte aligned; overlay without palette, photo without
+ *   overlay, a8 outside [0, 256].  labels, cover, overlay and photo may have any alignment.
+ *
+ * The refinement.  guide uint8 [B][H][W][3] (the photo at the maps' size, any alignment), channel value x_k = byte / 255;
+ *   dilations d_0 .. d_{D-1} (D ints on the HOST, read during the call), 1 <= D <= CCLIP_REFINE_MAX_DILATIONS,
+ *   1 <= d <= CCLIP_REFINE_MAX_DILATION.  Pixel p = (y, x) has N = 8 D neighbours, n = 8 j + e at q_n = clamp(p + d_j o_e) with
+ *   o_e = (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1) (1,0) (1,1) as (dy, dx), coordinates clamped to the image (replicate
+ *   padding); the centre is no neighbour and nothing crosses from one image of the batch to another.
+ *     sigma_k(p) = the unbiased standard deviation (divisor 9 D - 1) of x_k over the 9 D taps: the N neighbours and the centre
+ *                  once per dilation; formed from integer sums of the bytes, n sum(b^2) - sum(b)^2 exactly
+ *     a_n(p)     = -(1/3) sum_k |x_k(p) - x_k(q_n)| / (1e-8 + 0.1 sigma_k(p))
+ *     w_n(p)     = softmax over n of a_n(p)
+ *     m'_c(p)    = sum_n w_n(p) m_c(q_n)        ascending n, fp32, seeded with the first product, then one fma per neighbour
+ *   cclip_dense_refine_prepare writes key [B][H][W][4] fp32: key[0..2] = 1 / (1e-8 + 0.1 sigma_k), key[3] = L(p) =
+ *     max_n a_n + log sum_n exp(a_n - max), so that w_n = exp(a_n - L) with no reduction per iteration (expf / logf).
+ *   cclip_dense_refine_step runs ONE iteration maps_in -> maps_out, both [B][C][H][W] fp32, with the guide, the key and the
+ *     dilations the key was made with; the caller alternates two buffers.  A flat guide gives w_n = 1 / N whatever its colour.
+ *   No atomics, nothing depends on the launch geometry: two calls give equal bytes.
+ *   CCLIP_ERR_ARG, nothing launched: a NULL pointer; B < 1; H or W outside [1, CCLIP_OVERLAY_MAX_SIDE]; D or a dilation outside
+ *   its range; key not 16-byte aligned; prepare: B H W > 2^31 - 1; step: C outside [1, 255], B C H W > 2^31 - 1, maps_in or
+ *   maps_out not 4-byte aligned, maps_in and maps_out the same or overlapping buffers. */
+#define CCLIP_REFINE_MAX_DILATIONS 6
+#define CCLIP_REFINE_MAX_DILATION 24
+int cclip_dense_stitch_maps(const float* probs, int32_t K, int32_t C, int32_t g, const int32_t* boxes, int32_t H, int32_t W,
+                            float* maps, uint8_t* cover, hipStream_t stream);
+int cclip_dense_maps_label(const float* maps, int32_t B, int32_t C, int32_t H, int32_t W, const uint8_t* cover, float min_conf,
+                           uint8_t* labels, float* conf, const uint8_t* palette, const uint8_t* photo, int32_t a8,
+                           uint8_t* overlay, hipStream_t stream);
+int cclip_dense_refine_prepare(const uint8_t* guide, int32_t B, int32_t H, int32_t W, const int32_t* dilations, int32_t D,
+                               float* key, hipStream_t stream);
+int cclip_dense_refine_step(const float* maps_in, float* maps_out, const uint8_t* guide, const float* key, int32_t B, int32_t C,
+                            int32_t H, int32_t W, const int32_t* dilations, int32_t D, hipStream_t stream);
+
 /* cclip_label_components (csrc/label_components.hip): the connected components of labels uint8 [B][H][W], 255 = "none".
  *   Two pixels are joined when they lie in the same image, carry the same label other than 255 and are 4-neighbours
  *   (connectivity 4) or 8-neighbours (connectivity 8); components are the classes of the transitive closure.  Nothing joins

@@ -9,9 +9,13 @@ crops through the tower, probabilities averaged where they overlap, csrc/dense_s
 multi-scale ensemble.  The JSON line then also carries "windows", "height" and "width", and the PNG has the photo's size.
 With --instances the line gains "instances": one record {"class", "name", "box", "area", "score"} per connected component of the
 label map (`clip.label_components`, csrc/label_components.hip), filtered by --min-area / --min-score, joined by --connectivity.
+With --refine the class maps are first snapped to the photo's edges (`.refine(photo)`: pixel-adaptive mask refinement under the
+photo at the map's size, csrc/dense_refine.hip; --refine-iterations, --refine-dilations); areas, top class, mean confidence,
+instances and the PNG then come from the refined result and the line carries "refine".
 
     python scripts/segment_images.py photos/ --checkpoint clip.pt --prompts "a worker without a helmet" scaffold ground --png maps
     python scripts/segment_images.py photos/ --checkpoint clip.pt --window 224 448 --max-side 2048 --png maps
+    python scripts/segment_images.py photos/ --checkpoint clip.pt --window 224 --refine --instances --png maps
     python scripts/segment_images.py --synthetic --png /tmp/maps                     # offline: seeded model, generated images"""
 from __future__ import annotations
 
@@ -48,6 +52,10 @@ def build_parser():
     ap.add_argument("--min-area", type=int, default=1, help="--instances: drop components of fewer pixels")
     ap.add_argument("--min-score", type=float, default=0.0, help="--instances: drop components of a lower mean confidence")
     ap.add_argument("--connectivity", type=int, choices=(4, 8), default=4, help="--instances: which neighbours join")
+    ap.add_argument("--refine", action="store_true", help="snap the class maps to the photo's edges before labelling (clip.refine_maps)")
+    ap.add_argument("--refine-iterations", type=int, default=10, metavar="T", help="--refine: iterations, 1 .. 64")
+    ap.add_argument("--refine-dilations", type=int, nargs="+", default=[1, 2, 4, 8, 12, 24], metavar="d",
+                    help="--refine: neighbour distances, 1 to 6 values in 1 .. 24")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=3, help="--synthetic: images to segment")
     return ap
@@ -70,9 +78,16 @@ def instance_records(comps, args, prompts, image=None):
             for r in recs if image is None or r["image"] == image]
 
 
+def refined(res, photo, args):
+    """--refine: (the refined result, what the JSON line says about it)"""
+    out = res.refine(photo, dilations=args.refine_dilations, iterations=args.refine_iterations)
+    return out, dict(iterations=out.iterations, dilations=list(out.dilations))
+
+
 def photos(args, model, files, prompts, text):
     """--window / --stride: one clip.segment_photo per photo, at the photo's size"""
     import clip
+    import numpy as np
     from PIL import Image
     from clip.preprocess_device import DevicePreprocess
     windows = list(args.window) if args.window else [model.geo.image_resolution]
@@ -87,15 +102,20 @@ def photos(args, model, files, prompts, text):
             pic = pic.resize((max(1, round(pic.size[0] * k)), max(1, round(pic.size[1] * k))), Image.BICUBIC)
         res = clip.segment_photo(model, pic, text, window=window, stride=stride, mode=args.mode, min_conf=args.min_conf,
                                  temperature=args.temperature, batch=args.bs, preprocess=pre)
+        n_windows = int(res.boxes.shape[0])
+        photo = torch.from_numpy(np.asarray(pic, dtype=np.uint8).copy()) if args.png or args.refine else None
+        note = None
+        if args.refine:
+            res, note = refined(res, photo, args)
         top = res.top_class()
         line = dict(file=f, classes=prompts, area=[round(v, 6) for v in res.area_fractions().tolist()],
                     top_class=None if top is None else prompts[top], mean_conf=round(float(res.conf.mean()), 5),
-                    windows=int(res.boxes.shape[0]), height=int(res.labels.shape[0]), width=int(res.labels.shape[1]))
+                    windows=n_windows, height=int(res.labels.shape[0]), width=int(res.labels.shape[1]))
+        if note is not None:
+            line["refine"] = note
         if args.instances:
             line["instances"] = instance_records(res.components(args.connectivity), args, prompts)
         if args.png:
-            import numpy as np
-            photo = torch.from_numpy(np.asarray(pic, dtype=np.uint8).copy())
             line["png"] = os.path.join(args.png, f"{i:05d}_{os.path.splitext(os.path.basename(f))[0]}.png")
             Image.fromarray(res.overlay(photo=photo, alpha=args.alpha).cpu().numpy()).save(line["png"])
         C.log_line(**line)
@@ -142,17 +162,23 @@ def main(argv=None):
         pics = [Image.open(f).convert("RGB") for f in chunk]
         image = torch.stack([preprocess(p) for p in pics]).to(device)
         res = clip.segment(model, image, text, mode=args.mode, size=S, min_conf=args.min_conf, temperature=args.temperature)
+        photo, note = None, None
+        if args.png or args.refine:
+            import numpy as np
+            photo = torch.stack([torch.from_numpy(np.asarray(p.resize((S, S), Image.BILINEAR)).copy()) for p in pics])
+        if args.refine:
+            res, note = refined(res, photo, args)
         fractions, top = res.area_fractions().cpu(), res.top_class()
         mean_conf = res.conf.flatten(1).mean(dim=1).cpu()
         overlay = None
         if args.png:
-            import numpy as np
-            photo = torch.stack([torch.from_numpy(np.asarray(p.resize((S, S), Image.BILINEAR)).copy()) for p in pics])
             overlay = res.overlay(photo=photo, alpha=args.alpha).cpu().numpy()
         comps = res.components(args.connectivity) if args.instances else None
         for j, f in enumerate(chunk):
             line = dict(file=f, classes=prompts, area=[round(v, 6) for v in fractions[j].tolist()],
                         top_class=None if top[j] is None else prompts[top[j]], mean_conf=round(float(mean_conf[j]), 5))
+            if note is not None:
+                line["refine"] = note
             if comps is not None:
                 line["instances"] = instance_records(comps, args, prompts, image=j)
             if overlay is not None:
