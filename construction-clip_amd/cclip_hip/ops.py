@@ -2003,6 +2003,24 @@ def dense_label_map(probs: torch.Tensor, size: int, labels: torch.Tensor, conf: 
 DENSE_MAX_WINDOWS = 65535
 
 
+def _stitch_inputs(fname: str, probs, boxes, height, width):
+    """The input side of dense_stitch and dense_stitch_maps: probs [K, C, g, g] inside the window and class caps, boxes [K, 4], and
+    height, width and g in [1, OVERLAY_MAX_SIDE]; returns K, C, g, H, W."""
+    if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
+        raise ValueError(f"{fname}: probs must be [K, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
+    K, C, g, _ = probs.shape
+    if K > DENSE_MAX_WINDOWS:
+        raise ValueError(f"{fname}: probs holds {K} windows; at most {DENSE_MAX_WINDOWS}")
+    if C > DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: probs holds {C} classes; at most {DENSE_MAX_CLASSES} (label 255 means none)")
+    if tuple(boxes.shape) != (K, 4):
+        raise ValueError(f"{fname}: boxes must be [{K}, 4] as (x0, y0, x1, y1), got {tuple(boxes.shape)}")
+    if int(height) != height or int(width) != width or not 1 <= height <= OVERLAY_MAX_SIDE or not 1 <= width <= OVERLAY_MAX_SIDE \
+            or g > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: height {height}, width {width}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    return K, C, g, int(height), int(width)
+
+
 def dense_stitch(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: int, labels: torch.Tensor, conf: torch.Tensor, *,
                  min_conf: float = 0.0, cover: Optional[torch.Tensor] = None, overlay: Optional[torch.Tensor] = None,
                  palette: Optional[torch.Tensor] = None, photo: Optional[torch.Tensor] = None, alpha8: int = 256) -> None:
@@ -2020,19 +2038,7 @@ def dense_stitch(probs: torch.Tensor, boxes: torch.Tensor, height: int, width: i
         if t is not None:
             tensors.append((t, name, torch.uint8))
     _cuda_operands(fname, tensors, probs)
-    if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
-        raise ValueError(f"{fname}: probs must be [K, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
-    K, C, g, _ = probs.shape
-    if K > DENSE_MAX_WINDOWS:
-        raise ValueError(f"{fname}: probs holds {K} windows; at most {DENSE_MAX_WINDOWS}")
-    if C > DENSE_MAX_CLASSES:
-        raise ValueError(f"{fname}: probs holds {C} classes; at most {DENSE_MAX_CLASSES} (label 255 means none)")
-    if tuple(boxes.shape) != (K, 4):
-        raise ValueError(f"{fname}: boxes must be [{K}, 4] as (x0, y0, x1, y1), got {tuple(boxes.shape)}")
-    if int(height) != height or int(width) != width or not 1 <= height <= OVERLAY_MAX_SIDE or not 1 <= width <= OVERLAY_MAX_SIDE \
-            or g > OVERLAY_MAX_SIDE:
-        raise ValueError(f"{fname}: height {height}, width {width}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
-    H, W = int(height), int(width)
+    K, C, g, H, W = _stitch_inputs(fname, probs, boxes, height, width)
     _label_outputs(fname, (H, W), labels, conf, cover, overlay, palette, photo, alpha8)
     if probs.data_ptr() % 4 or conf.data_ptr() % 4 or boxes.data_ptr() % 4:
         raise ValueError(f"{fname}: probs, conf and boxes must start on a 4-byte boundary")
@@ -2056,19 +2062,7 @@ def dense_stitch_maps(probs: torch.Tensor, boxes: torch.Tensor, height: int, wid
     if cover is not None:
         tensors.append((cover, "cover", torch.uint8))
     _cuda_operands(fname, tensors, probs)
-    if probs.dim() != 4 or probs.shape[2] != probs.shape[3] or min(probs.shape) < 1:
-        raise ValueError(f"{fname}: probs must be [K, C, g, g] with no empty dimension, got {tuple(probs.shape)}")
-    K, C, g, _ = probs.shape
-    if K > DENSE_MAX_WINDOWS:
-        raise ValueError(f"{fname}: probs holds {K} windows; at most {DENSE_MAX_WINDOWS}")
-    if C > DENSE_MAX_CLASSES:
-        raise ValueError(f"{fname}: probs holds {C} classes; at most {DENSE_MAX_CLASSES} (label 255 means none)")
-    if tuple(boxes.shape) != (K, 4):
-        raise ValueError(f"{fname}: boxes must be [{K}, 4] as (x0, y0, x1, y1), got {tuple(boxes.shape)}")
-    if int(height) != height or int(width) != width or not 1 <= height <= OVERLAY_MAX_SIDE or not 1 <= width <= OVERLAY_MAX_SIDE \
-            or g > OVERLAY_MAX_SIDE:
-        raise ValueError(f"{fname}: height {height}, width {width}, grid {g}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
-    H, W = int(height), int(width)
+    K, C, g, H, W = _stitch_inputs(fname, probs, boxes, height, width)
     if C * H * W > _INT32_MAX:
         raise ValueError(f"{fname}: {C} x {H} x {W} map values; at most 2^31 - 1")
     if tuple(maps.shape) != (C, H, W):

@@ -75,8 +75,34 @@ def _top_classes(fractions: torch.Tensor) -> List[Optional[int]]:
     return [int(r.argmax()) if float(r.max()) > 0 else None for r in fr]
 
 
+class _LabelledResult:
+    """What DenseResult, PhotoDenseResult and RefinedDenseResult do with their labels ([B, H, W], or [H, W] for a single photo),
+    conf, class_names and n_classes.  No fields of its own."""
+
+    def area_fractions(self) -> torch.Tensor:
+        """fp64 [B, C + 1] ([C + 1] for a single photo): the share of pixels per class, "none" last.  Pixel COUNTS are integers,
+        each divided once by H * W: a row sums to 1."""
+        return _area_fractions(self.labels, self.n_classes)
+
+    def top_class(self):
+        """the class with the largest area (None when no pixel has a class): a list per image, one value for a single photo"""
+        top = _top_classes(self.area_fractions())
+        return top if self.labels.dim() == 3 else top[0]
+
+    def components(self, connectivity: int = 4) -> "ComponentsResult":
+        """the connected components of the label maps with their mean confidences, on the device (`label_components`), image by
+        image"""
+        return label_components(self.labels, self.conf, connectivity=connectivity)
+
+    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
+                  connectivity: int = 4) -> List[dict]:
+        """one record per connected component: components(connectivity).instances(...) with this result's class names"""
+        return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
+                                                       class_names=self.class_names)
+
+
 @dataclass
-class DenseResult:
+class DenseResult(_LabelledResult):
     probs: torch.Tensor                  # fp32 [B, C, g, g]
     labels: torch.Tensor                 # uint8 [B, S, S]; 255 = none (conf < min_conf)
     conf: torch.Tensor                   # fp32 [B, S, S]
@@ -102,25 +128,6 @@ class DenseResult:
         else:
             ops.dense_label_map(self.probs, H, lab, conf, min_conf=self.min_conf, overlay=out, palette=pal, photo=photo, alpha8=a8)
         return out
-
-    def area_fractions(self) -> torch.Tensor:
-        """fp64 [B, C + 1]: the share of pixels per class, "none" last.  Pixel COUNTS are integers, each divided once by S * S:
-        a row sums to 1."""
-        return _area_fractions(self.labels, self.n_classes)
-
-    def top_class(self) -> List[Optional[int]]:
-        """per image the class with the largest area, None when no pixel has a class"""
-        return _top_classes(self.area_fractions())
-
-    def components(self, connectivity: int = 4) -> "ComponentsResult":
-        """the connected components of the label maps with their mean confidences (`label_components`), image by image"""
-        return label_components(self.labels, self.conf, connectivity=connectivity)
-
-    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
-                  connectivity: int = 4) -> List[dict]:
-        """one record per connected component: components(connectivity).instances(...) with this result's class names"""
-        return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
-                                                       class_names=self.class_names)
 
     def refine(self, photo, *, dilations: Sequence[int] = ops.REFINE_DEFAULT_DILATIONS, iterations: int = 10,
                min_conf: Optional[float] = None) -> "RefinedDenseResult":
@@ -396,7 +403,7 @@ def label_components(labels: torch.Tensor, conf: Optional[torch.Tensor] = None, 
 
 
 @dataclass
-class PhotoDenseResult:
+class PhotoDenseResult(_LabelledResult):
     probs: torch.Tensor                  # fp32 [K, C, g, g]: the class maps of every window
     boxes: torch.Tensor                  # int64 [K, 4] (CPU): the windows, (x0, y0, x1, y1) in photo pixels
     labels: torch.Tensor                 # uint8 [H, W]; 255 = none
@@ -420,27 +427,9 @@ class PhotoDenseResult:
                          torch.empty_like(self.conf), min_conf=self.min_conf, overlay=out, palette=pal, photo=photo, alpha8=a8)
         return out
 
-    def area_fractions(self) -> torch.Tensor:
-        """fp64 [C + 1]: the share of pixels per class, "none" last; integer counts divided once by H * W: they sum to 1."""
-        return _area_fractions(self.labels, self.n_classes)
-
-    def top_class(self) -> Optional[int]:
-        """the class with the largest area, None when no pixel has a class"""
-        return _top_classes(self.area_fractions())[0]
-
     def class_boxes(self, c: int, min_area: int = 1) -> List[Tuple[int, int, int, int]]:
         """bounding boxes (x0, y0, x1, y1) of the 4-connected components of label c (`label_boxes`): what classify_regions takes"""
         return label_boxes(self.labels, c, min_area)
-
-    def components(self, connectivity: int = 4) -> ComponentsResult:
-        """the connected components of the label map with their mean confidences, on the device (`label_components`)"""
-        return label_components(self.labels, self.conf, connectivity=connectivity)
-
-    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
-                  connectivity: int = 4) -> List[dict]:
-        """one record per connected component: components(connectivity).instances(...) with this result's class names"""
-        return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
-                                                       class_names=self.class_names)
 
     def refine(self, photo, *, dilations: Sequence[int] = ops.REFINE_DEFAULT_DILATIONS, iterations: int = 10,
                min_conf: Optional[float] = None) -> "RefinedDenseResult":
@@ -459,6 +448,12 @@ class PhotoDenseResult:
 
 
 REFINE_MAX_ITERATIONS = 64
+
+
+def _iterations(fname: str, iterations) -> int:
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= iterations <= REFINE_MAX_ITERATIONS:
+        raise ValueError(f"{fname}: iterations must be an integer in [1, {REFINE_MAX_ITERATIONS}], got {iterations!r}")
+    return int(iterations)
 
 
 def _refine_guide(photo, shape, dev) -> torch.Tensor:
@@ -491,11 +486,10 @@ def refine_maps(maps: torch.Tensor, guide: torch.Tensor, *, dilations: Sequence[
         raise ValueError(f"{fname}: guide must be {[B, H, W, 3] if maps.dim() == 4 else [H, W, 3]} for maps {tuple(maps.shape)}, "
                          f"got {tuple(guide.shape)}")
     ds = ops.refine_dilations(fname, dilations)
-    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= iterations <= REFINE_MAX_ITERATIONS:
-        raise ValueError(f"{fname}: iterations must be an integer in [1, {REFINE_MAX_ITERATIONS}], got {iterations!r}")
+    iterations = _iterations(fname, iterations)
     if not maps.is_cuda:
         raise ValueError(f"{fname}: maps must be a cuda tensor, got {maps.device} (no CPU path)")
-    return _refine_run(m4, g4.to(maps.device), ds, int(iterations), own=False).view(maps.shape)
+    return _refine_run(m4, g4.to(maps.device), ds, iterations, own=False).view(maps.shape)
 
 
 def _refine_run(m4: torch.Tensor, g4: torch.Tensor, ds, iterations: int, own: bool) -> torch.Tensor:
@@ -515,7 +509,7 @@ def _refine_run(m4: torch.Tensor, g4: torch.Tensor, ds, iterations: int, own: bo
 
 
 @dataclass
-class RefinedDenseResult:
+class RefinedDenseResult(_LabelledResult):
     """Class maps refined under a photo (`DenseResult.refine`, `PhotoDenseResult.refine`) and what they label."""
     maps: torch.Tensor                   # fp32 [B, C, H, W], or [C, H, W] from a PhotoDenseResult
     labels: torch.Tensor                 # uint8 [B, H, W] / [H, W]; 255 = none (conf < min_conf)
@@ -546,32 +540,12 @@ class RefinedDenseResult:
                              alpha8=a8)
         return out
 
-    def area_fractions(self) -> torch.Tensor:
-        """fp64 [..., C + 1]: the share of pixels per class, "none" last; integer counts divided once by H * W"""
-        return _area_fractions(self.labels, self.n_classes)
-
-    def top_class(self):
-        """the class with the largest area (None when no pixel has a class): a list per image, one value for a single photo"""
-        top = _top_classes(self.area_fractions())
-        return top if self.labels.dim() == 3 else top[0]
-
-    def components(self, connectivity: int = 4) -> ComponentsResult:
-        """the connected components of the refined label maps with their mean confidences (`label_components`)"""
-        return label_components(self.labels, self.conf, connectivity=connectivity)
-
-    def instances(self, min_area: int = 1, min_score: float = 0.0, classes: Optional[Sequence[int]] = None,
-                  connectivity: int = 4) -> List[dict]:
-        """one record per connected component: components(connectivity).instances(...) with this result's class names"""
-        return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
-                                                       class_names=self.class_names)
-
 
 def _refined(maps, guide, shape, class_names, min_conf, dilations, iterations) -> RefinedDenseResult:
     """refine maps [B, C, H, W] under guide [B, H, W, 3] and label them; `shape` = (H, W) gives a single photo's result"""
     ds = ops.refine_dilations("refine", dilations)
-    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= iterations <= REFINE_MAX_ITERATIONS:
-        raise ValueError(f"refine: iterations must be an integer in [1, {REFINE_MAX_ITERATIONS}], got {iterations!r}")
-    out = _refine_run(maps, guide, ds, int(iterations), own=True)          # `maps` is this module's own buffer: the second of the two
+    iterations = _iterations("refine", iterations)
+    out = _refine_run(maps, guide, ds, iterations, own=True)          # `maps` is this module's own buffer: the second of the two
     B, C, H, W = out.shape
     labels = torch.empty(B, H, W, device=out.device, dtype=torch.uint8)
     conf = torch.empty(B, H, W, device=out.device, dtype=torch.float32)
@@ -579,7 +553,7 @@ def _refined(maps, guide, shape, class_names, min_conf, dilations, iterations) -
     if shape is not None:
         out, labels, conf = out[0], labels[0], conf[0]
     return RefinedDenseResult(maps=out, labels=labels, conf=conf, class_names=class_names, min_conf=float(min_conf),
-                              dilations=ds, iterations=int(iterations))
+                              dilations=ds, iterations=iterations)
 
 
 def segment_photo(model, image, classes: Union[torch.Tensor, Sequence[str]], *, window=None, stride=None, mode: str = "value",

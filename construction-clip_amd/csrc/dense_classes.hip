@@ -1,6 +1,6 @@
 // Dense zero-shot maps (training-free dense CLIP: MaskCLIP, Zhou et al. 2022; SCLIP / ClearCLIP-style q.q^T, k.k^T variants):
 // the head that turns per-patch features and C class embeddings into per-patch class probabilities, and those into a label
-// map and picture at display size.  Two kernels, all fp32.
+// map and picture at display size.  Three kernels, all fp32.
 //
 // cclip_dense_class_probs.  feat [M = B * P][E] (row stride ldf), text [C][E], neither normalised:
 //     cos[m][c]      = <feat_m, text_c> * inv(|feat_m|) * inv(|text_c|),  inv(n) = 1 / n, and 0 when n == 0 (no epsilon is added
@@ -20,6 +20,10 @@
 // label's palette colour alone or blended in integers over a photo of the output size.  The selection rule, the ownership of
 // the flat [B * S * S] stream (four consecutive pixels per thread), every store and the picture's formula are label_pixels.h's,
 // shared with dense_stitch.hip: the kernel here is the per-pixel class loop and one call.
+//
+// cclip_dense_maps_label.  maps [B][C][H][W] already at the output size (dense_stitch.hip's averaged maps, refined or not by
+// dense_refine.hip) -> labels, conf and the picture by the same selection and the same writer; a pixel whose cover byte is 0
+// gets label 255 and conf 0, the stitch's n = 0 rule.
 #include "cclip_common.h"
 #include "../../include/cclip_hip.h"
 
@@ -191,5 +195,48 @@ extern "C" int cclip_dense_label_map(const float* probs, int32_t B, int32_t C, i
   const int64_t blocks = (npix + LP_PIX - 1) / LP_PIX;
   if (blocks > 0x7fffffff) return CCLIP_ERR_ARG;
   hipLaunchKernelGGL(dense_label_map_kernel, dim3((unsigned)blocks), dim3(LP_THREADS), 0, stream, a);
+  return cclip_launch_status();
+}
+
+// ---- class maps at the output size -> labels, conf, picture -------------------------------------
+struct ml_args { const float* maps; const uint8_t* cover; int B, C; long plane; lp_out out; };
+
+__global__ __launch_bounds__(LP_THREADS) void dense_maps_label_kernel(const ml_args a) {
+  __shared__ unsigned char pal[256 * 3];
+  lp_load_palette(pal, a.out);
+  __syncthreads();
+  const long npix = a.B * a.plane;
+  const long p0 = lp_first_pixel();
+  if (p0 >= npix) return;
+  const int n_px = lp_live(p0, npix);
+  unsigned lab[4], cov[4];
+  float cf[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    lab[i] = 255u; cov[i] = 0u; cf[i] = 0.0f;
+    if (i >= n_px) continue;
+    const long p = p0 + i;
+    if (a.cover && a.cover[p] == 0) continue;               // the stitch's n = 0 rule
+    const long b = p / a.plane;
+    const float* m = a.maps + b * a.C * a.plane + (p - b * a.plane);
+    lp_pick pk = lp_seed(m[0]);
+    for (int c = 1; c < a.C; ++c) lp_offer(pk, c, m[c * a.plane]);
+    lab[i] = lp_label(pk, a.out.min_conf);
+    cf[i] = pk.best;
+  }
+  lp_store_quad(a.out, pal, p0, n_px, lab, cf, cov);
+}
+
+extern "C" int cclip_dense_maps_label(const float* maps, int32_t B, int32_t C, int32_t H, int32_t W, const uint8_t* cover,
+                                      float min_conf, uint8_t* labels, float* conf, const uint8_t* palette, const uint8_t* photo,
+                                      int32_t a8, uint8_t* overlay, hipStream_t stream) {
+  if (!maps || B < 1 || C < 1 || C > LP_MAX_C || H < 1 || H > CCLIP_OVERLAY_MAX_SIDE || W < 1 || W > CCLIP_OVERLAY_MAX_SIDE) return CCLIP_ERR_ARG;
+  if ((int64_t)B * C * H * W > 0x7fffffffLL || ((uintptr_t)maps & 3)) return CCLIP_ERR_ARG;
+  ml_args a;
+  a.maps = maps; a.cover = cover; a.B = B; a.C = C; a.plane = (long)H * W;
+  a.out = lp_out{labels, conf, nullptr, palette, photo, a8, overlay, min_conf};
+  if (!lp_out_ok(a.out)) return CCLIP_ERR_ARG;
+  const int64_t blocks = ((int64_t)B * a.plane + LP_PIX - 1) / LP_PIX;
+  hipLaunchKernelGGL(dense_maps_label_kernel, dim3((unsigned)blocks), dim3(LP_THREADS), 0, stream, a);
   return cclip_launch_status();
 }

@@ -1,12 +1,11 @@
 // Image-guided refinement of dense class maps (pixel-adaptive mask refinement, PAMR: Araslanov & Roth, "Single-Stage Semantic
 // Segmentation from Image Labels", CVPR 2020), stated from the paper's formulas (include/cclip_hip.h holds the contract; no other
-// implementation was compared).  fp32, four entry points:
+// implementation was compared).  fp32, two entry points (the maps come from dense_stitch.hip's cclip_dense_stitch_maps and are
+// labelled by dense_classes.hip's cclip_dense_maps_label):
 //
-//   cclip_dense_stitch_maps     the stitch's averaged class maps u_c [C][H][W] themselves (dense_stitch.hip keeps only their maximum)
 //   cclip_dense_refine_prepare  guide uint8 [B][H][W][3] -> key float4 per pixel: 1 / (1e-8 + 0.1 sigma_k), k = 0..2, and the
 //                               log-normaliser L of the pixel's 8 D neighbour logits
 //   cclip_dense_refine_step     one iteration maps_in -> maps_out: m'_c(p) = sum_n exp(a_n(p) - L(p)) m_c(q_n), ascending n
-//   cclip_dense_maps_label      maps [B][C][H][W] -> labels, conf and the picture through label_pixels.h
 //
 // Neighbour n = 8 j + e of pixel p is clamp(p + d_j o_e), o_e in the order (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1) (1,0) (1,1).
 // The logit a_n = -(1/3) sum_k |x_k(p) - x_k(q_n)| f_k with x = byte / 255 is formed by ONE function (rf_logit) from the two
@@ -261,180 +260,5 @@ extern "C" int cclip_dense_refine_step(const float* maps_in, float* maps_out, co
     case 5: hipLaunchKernelGGL(dense_refine_step_kernel<5>, grid, block, 0, stream, a); break;
     default: hipLaunchKernelGGL(dense_refine_step_kernel<6>, grid, block, 0, stream, a); break;
   }
-  return cclip_launch_status();
-}
-
-// ---- the stitch's averaged maps -----------------------------------------------------------------
-// dense_stitch.hip's band scan and window walk, restated for a kernel that keeps every u_c: the same coverage test, the same
-// samples (bilinear.h), the same sum in ascending k and the same one division, so max_c of these maps IS dense_stitch's conf.
-// A work-group has the same band of 1024 pixels; thread t owns pixels g0 + t, g0 + 256 + t, .. so that a class's stores are
-// contiguous across the wave.
-#define SM_THREADS 256
-#define SM_PIX 1024
-#define SM_LIST 512
-#define SM_FAST 4
-#define SM_MAX_K 65535
-
-struct sm_args { const float* probs; int K, C, g; const int* boxes; int H, W; float* maps; uint8_t* cover; };
-struct sm_box { int x0, y0, x1, y1; };
-struct sm_win { int k; ov_axis ay, ax; };
-
-__device__ __forceinline__ bool sm_valid(sm_box b) {
-  const long sw = (long)b.x1 - (long)b.x0, sh = (long)b.y1 - (long)b.y0;
-  return sw >= 1 && sw <= CCLIP_OVERLAY_MAX_SIDE && sh >= 1 && sh <= CCLIP_OVERLAY_MAX_SIDE;
-}
-__device__ __forceinline__ bool sm_covers(sm_box b, int x, int y) {
-  return sm_valid(b) && b.x0 <= x && x < b.x1 && b.y0 <= y && y < b.y1;
-}
-__device__ __forceinline__ sm_box sm_load_box(const int* __restrict__ boxes, int k) {
-  const int* p = boxes + 4 * (long)k;
-  sm_box b;
-  b.x0 = p[0]; b.y0 = p[1]; b.x1 = p[2]; b.y1 = p[3];
-  return b;
-}
-
-__global__ __launch_bounds__(SM_THREADS) void dense_stitch_maps_kernel(const sm_args a) {
-  __shared__ sm_box lbox[SM_LIST];
-  __shared__ int lk[SM_LIST];
-  __shared__ int wcnt[SM_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long npix = (long)a.H * a.W;
-  const long g0 = (long)blockIdx.x * SM_PIX;
-  const long g1 = (g0 + SM_PIX < npix ? g0 + SM_PIX : npix) - 1;
-  const int ylo = (int)(g0 / a.W), yhi = (int)(g1 / a.W);
-  const bool one_row = ylo == yhi;
-  const int xlo = one_row ? (int)(g0 - (long)ylo * a.W) : 0;
-  const int xhi = one_row ? (int)(g1 - (long)yhi * a.W) : a.W - 1;
-
-  int total = 0;                                            // the windows that meet the band, in ascending k
-  for (int base = 0; base < a.K; base += SM_THREADS) {
-    const int k = base + tid;
-    bool hit = false;
-    sm_box b = {0, 0, 0, 0};
-    if (k < a.K) {
-      b = sm_load_box(a.boxes, k);
-      hit = sm_valid(b) && b.x0 <= xhi && b.x1 > xlo && b.y0 <= yhi && b.y1 > ylo;
-    }
-    const unsigned long long m = __ballot(hit);
-    if (lane == 0) wcnt[wave] = __popcll(m);
-    __syncthreads();
-    int pos = total + __popcll(m & ((1ull << lane) - 1ull));
-    int sum = 0;
-#pragma unroll
-    for (int w = 0; w < SM_THREADS / 64; ++w) {
-      const int c = wcnt[w];
-      if (w < wave) pos += c;
-      sum += c;
-    }
-    if (hit && pos < SM_LIST) { lbox[pos] = b; lk[pos] = k; }
-    total += sum;
-    __syncthreads();
-  }
-  const bool listed = total <= SM_LIST;
-  const int L = listed ? total : a.K;
-  const long gg = (long)a.g * a.g, cgg = gg * a.C;
-
-  for (int i = 0; i < SM_PIX / SM_THREADS; ++i) {
-    const long p = g0 + i * SM_THREADS + tid;
-    if (p >= npix) return;
-    const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
-    sm_win f[SM_FAST];
-#pragma unroll
-    for (int q = 0; q < SM_FAST; ++q) { f[q].k = 0; f[q].ay = ov_axis{0, 0, 0.0f}; f[q].ax = ov_axis{0, 0, 0.0f}; }
-    int n = 0, jrest = L;
-    for (int j = 0; j < L; ++j) {
-      const sm_box b = listed ? lbox[j] : sm_load_box(a.boxes, j);
-      if (!sm_covers(b, x, y)) continue;
-      if (n < SM_FAST) {
-        sm_win w;
-        w.k = listed ? lk[j] : j;
-        w.ay = ov_coord_exact(y - b.y0, a.g, b.y1 - b.y0);
-        w.ax = ov_coord_exact(x - b.x0, a.g, b.x1 - b.x0);
-#pragma unroll
-        for (int q = 0; q < SM_FAST; ++q)
-          if (n == q) f[q] = w;
-      } else if (n == SM_FAST) {
-        jrest = j;
-      }
-      ++n;
-    }
-    if (a.cover) a.cover[p] = (uint8_t)(n < 255 ? n : 255);
-    const float fn = (float)n;
-    for (int c = 0; c < a.C; ++c) {
-      float u = 0.0f;
-      if (n > 0) {
-        const float* pc = a.probs + c * gg;
-        float s = ov_bil(pc + f[0].k * cgg, a.g, f[0].ay, f[0].ax);
-#pragma unroll
-        for (int q = 1; q < SM_FAST; ++q)
-          if (q < n) s = s + ov_bil(pc + f[q].k * cgg, a.g, f[q].ay, f[q].ax);
-        if (n > SM_FAST) {
-          for (int j = jrest; j < L; ++j) {
-            const sm_box b = listed ? lbox[j] : sm_load_box(a.boxes, j);
-            if (!sm_covers(b, x, y)) continue;
-            const long k = listed ? lk[j] : j;
-            s = s + ov_bil(pc + k * cgg, a.g, ov_coord_exact(y - b.y0, a.g, b.y1 - b.y0), ov_coord_exact(x - b.x0, a.g, b.x1 - b.x0));
-          }
-        }
-        u = s / fn;
-      }
-      a.maps[c * npix + p] = u;
-    }
-  }
-}
-
-extern "C" int cclip_dense_stitch_maps(const float* probs, int32_t K, int32_t C, int32_t g, const int32_t* boxes, int32_t H, int32_t W,
-                                       float* maps, uint8_t* cover, hipStream_t stream) {
-  if (!probs || !boxes || !maps || K < 1 || K > SM_MAX_K || C < 1 || C > LP_MAX_C || g < 1 || g > CCLIP_OVERLAY_MAX_SIDE || H < 1 ||
-      H > CCLIP_OVERLAY_MAX_SIDE || W < 1 || W > CCLIP_OVERLAY_MAX_SIDE)
-    return CCLIP_ERR_ARG;
-  if ((int64_t)C * H * W > 0x7fffffffLL || (((uintptr_t)probs | (uintptr_t)boxes | (uintptr_t)maps) & 3)) return CCLIP_ERR_ARG;
-  sm_args a;
-  a.probs = probs; a.K = K; a.C = C; a.g = g; a.boxes = boxes; a.H = H; a.W = W; a.maps = maps; a.cover = cover;
-  const int64_t blocks = ((int64_t)H * W + SM_PIX - 1) / SM_PIX;
-  hipLaunchKernelGGL(dense_stitch_maps_kernel, dim3((unsigned)blocks), dim3(SM_THREADS), 0, stream, a);
-  return cclip_launch_status();
-}
-
-// ---- maps -> labels, conf, picture --------------------------------------------------------------
-struct ml_args { const float* maps; const uint8_t* cover; int B, C; long plane; lp_out out; };
-
-__global__ __launch_bounds__(LP_THREADS) void dense_maps_label_kernel(const ml_args a) {
-  __shared__ unsigned char pal[256 * 3];
-  lp_load_palette(pal, a.out);
-  __syncthreads();
-  const long npix = a.B * a.plane;
-  const long p0 = lp_first_pixel();
-  if (p0 >= npix) return;
-  const int n_px = lp_live(p0, npix);
-  unsigned lab[4], cov[4];
-  float cf[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    lab[i] = 255u; cov[i] = 0u; cf[i] = 0.0f;
-    if (i >= n_px) continue;
-    const long p = p0 + i;
-    if (a.cover && a.cover[p] == 0) continue;               // the stitch's n = 0 rule
-    const long b = p / a.plane;
-    const float* m = a.maps + b * a.C * a.plane + (p - b * a.plane);
-    lp_pick pk = lp_seed(m[0]);
-    for (int c = 1; c < a.C; ++c) lp_offer(pk, c, m[c * a.plane]);
-    lab[i] = lp_label(pk, a.out.min_conf);
-    cf[i] = pk.best;
-  }
-  lp_store_quad(a.out, pal, p0, n_px, lab, cf, cov);
-}
-
-extern "C" int cclip_dense_maps_label(const float* maps, int32_t B, int32_t C, int32_t H, int32_t W, const uint8_t* cover,
-                                      float min_conf, uint8_t* labels, float* conf, const uint8_t* palette, const uint8_t* photo,
-                                      int32_t a8, uint8_t* overlay, hipStream_t stream) {
-  if (!maps || B < 1 || C < 1 || C > LP_MAX_C || H < 1 || H > CCLIP_OVERLAY_MAX_SIDE || W < 1 || W > CCLIP_OVERLAY_MAX_SIDE) return CCLIP_ERR_ARG;
-  if ((int64_t)B * C * H * W > 0x7fffffffLL || ((uintptr_t)maps & 3)) return CCLIP_ERR_ARG;
-  ml_args a;
-  a.maps = maps; a.cover = cover; a.B = B; a.C = C; a.plane = (long)H * W;
-  a.out = lp_out{labels, conf, nullptr, palette, photo, a8, overlay, min_conf};
-  if (!lp_out_ok(a.out)) return CCLIP_ERR_ARG;
-  const int64_t blocks = ((int64_t)B * a.plane + LP_PIX - 1) / LP_PIX;
-  hipLaunchKernelGGL(dense_maps_label_kernel, dim3((unsigned)blocks), dim3(LP_THREADS), 0, stream, a);
   return cclip_launch_status();
 }

@@ -1,7 +1,7 @@
-// The writer of the per-pixel label kernels (dense_classes.hip: dense_label_map_kernel; dense_stitch.hip: dense_stitch_kernel):
-// which pixels a thread owns, which class a pixel gets, and how labels, conf, cover and the picture reach memory.  Both kernels
-// form a pixel's per-class values their own way and hand the four results to lp_store_quad, so the two agree byte for byte by
-// construction.  Include it BELOW the file's `#pragma clang fp contract(off)` and after bilinear.h, as bilinear.h itself asks:
+// The writer of the per-pixel label kernels (dense_classes.hip: dense_label_map_kernel, dense_maps_label_kernel; dense_stitch.hip:
+// dense_stitch_kernel): which pixels a thread owns, which class a pixel gets, and how labels, conf, cover and the picture reach
+// memory.  The kernels form a pixel's per-class values their own way and hand the four results to lp_store_quad, so they agree
+// byte for byte by construction.  Include it BELOW the file's `#pragma clang fp contract(off)` and after bilinear.h, as bilinear.h itself asks:
 // the selection compares values that must come out the same in both kernels, and so must whatever is added here later.
 //
 // Ownership.  A thread owns FOUR consecutive pixels of the flat stream (B * S * S, or H * W): its labels are one dword, its cover

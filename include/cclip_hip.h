@@ -1188,8 +1188,9 @@ int cclip_dense_stitch(const float* probs, int32_t K, int32_t C, int32_t g, cons
                        float min_conf, uint8_t* labels, float* conf, uint8_t* cover, const uint8_t* palette, const uint8_t* photo,
                        int32_t a8, uint8_t* overlay, hipStream_t stream);
 
-/* Image-guided refinement of dense class maps (csrc/dense_refine.hip): pixel-adaptive mask refinement (PAMR; Araslanov & Roth,
- * CVPR 2020), stated here from the paper's formulas - this text is the contract, no other implementation was compared.
+/* Image-guided refinement of dense class maps (prepare and step: csrc/dense_refine.hip; cclip_dense_stitch_maps: csrc/dense_stitch.hip,
+ * on the functions cclip_dense_stitch runs; cclip_dense_maps_label: csrc/dense_classes.hip): pixel-adaptive mask refinement (PAMR;
+ * Araslanov & Roth, CVPR 2020), stated here from the paper's formulas - this text is the contract, no other implementation was compared.
  *
  * cclip_dense_stitch_maps: cclip_dense_stitch's inputs (probs [K][C][g][g], device boxes int32 [K][4], H, W) and its coverage,
  *   sampling and averaging rules, but the averaged maps themselves are written: maps [C][H][W] fp32 = u_c, 0 where no window

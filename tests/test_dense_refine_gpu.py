@@ -1,9 +1,12 @@
-"""GPU: the image-guided refinement (csrc/dense_refine.hip; ops.dense_stitch_maps, dense_maps_label, dense_refine_prepare,
-dense_refine_step; clip.refine_maps, DenseResult.refine, PhotoDenseResult.refine) on the MI355X against the float64 reference of
-tests/dense_refine_ref.py.
+"""GPU: the image-guided refinement (csrc/dense_refine.hip: ops.dense_refine_prepare, dense_refine_step; the maps it starts from
+and their labels, csrc/dense_stitch.hip: ops.dense_stitch_maps, csrc/dense_classes.hip: ops.dense_maps_label; clip.refine_maps,
+DenseResult.refine, PhotoDenseResult.refine) on the MI355X against the float64 references of tests/dense_refine_ref.py and
+tests/dense_stitch_ref.py.
 
-Exact (==): stitch_maps + maps_label(cover=) against dense_stitch; max_c maps against conf; two calls of every kernel; a flat
-guide of one colour against a flat guide of another; overlay bytes against the integer formula.
+Exact (==): stitch_maps + maps_label(cover=) against dense_stitch, also where a pixel has 40 windows (the recompute loop), on
+the LDS list of K = 300 and on the walk of all K = 600 boxes; max_c maps against conf; two calls of every kernel; a flat guide
+of one colour against a flat guide of another; overlay bytes against the integer formula.
+Every class of dense_stitch_maps against float64 within CONF_TOL + (nmax - 1) 2^-24, test_dense_stitch_gpu.py's bound for conf.
 Bounds: dense_refine_ref.BOUNDS, per case and guide 4 x the error of the fp32 torch restatement against float64 (measured by
 tests/test_dense_refine_ref_cpu.py): the key's factors (relative), L, the maps after 1, 2 and 10 steps.  Labels are compared
 outside the fragile set (float64 top-two margin in (0, FRAGILE_T10 = 2.9e-5)); conf is held to the map bound and the class sums
@@ -137,6 +140,72 @@ def test_stitch_maps_then_maps_label_is_dense_stitch(case):
     photo = torch.randint(0, 256, (H, W, 3), generator=gen, dtype=torch.uint8).cuda()
     _stitch_both(probs, boxes, H, W, pal=pal)
     _stitch_both(probs, boxes, H, W, min_conf=0.5, photo=photo, pal=pal, a8=77)
+
+
+def _path_case(name):
+    """(probs, boxes, H, W, the cover to expect) of test_dense_stitch_gpu.py's path cases, generators and seeds as there: "forty"
+    - 40 windows on a pixel, 36 of them through the recompute loop; "small" - K = 300, the LDS list; "columns" - K = 600 columns
+    of the picture's height meet every band, 600 > 512: each group walks all K boxes from global memory"""
+    if name == "forty":
+        H, W, g, C = 30, 41, 3, 4
+        rng = np.random.default_rng(15)
+        boxes = np.array([[rng.integers(0, 15), rng.integers(0, 10), rng.integers(26, 42), rng.integers(20, 31)] for _ in range(40)])
+        return SR.stitch_maps(40, C, g, seed=15), boxes, H, W, (40, 40)
+    K = {"small": 300, "columns": 600}[name]
+    H, W, g, C = 48, 64, 2, 3
+    rng = np.random.default_rng(16)
+    if name == "small":
+        x0, y0 = rng.integers(-3, W - 2, K), rng.integers(-3, H - 2, K)
+        boxes = np.stack([x0, y0, x0 + rng.integers(4, 13, K), y0 + rng.integers(4, 13, K)], axis=1)
+    else:
+        x0 = rng.integers(0, W - 1, K)
+        boxes = np.stack([x0, np.zeros(K, dtype=np.int64), x0 + rng.integers(1, 3, K), np.full(K, H)], axis=1)
+    return SR.stitch_maps(K, C, g, seed=16), boxes, H, W, (5, 64)
+
+
+PATH_CASES = ("forty", "small", "columns")
+_STITCH_REF = {}
+
+
+def _stitch_reference(case):
+    """(probs, boxes, H, W, float64 stitch_ref, its largest cover) of a STITCH_CASES entry or a path case, computed once; the
+    reference is finite and its largest cover is what the case is there for"""
+    if case not in _STITCH_REF:
+        if case in PATH_CASES:
+            probs, boxes, H, W, (lo, hi) = _path_case(case)
+        else:
+            probs, boxes, H, W = SR.stitch_case(case)
+            lo, hi = 1, 6                                                     # the shared cases: what CONF_TOL alone was stated for
+        ref = SR.stitch_ref(probs, torch.as_tensor(np.asarray(boxes)), H, W)
+        nmax = int(ref["cover"].max())
+        assert bool(torch.isfinite(ref["up"]).all()) and lo <= nmax <= hi, (case, nmax)
+        _STITCH_REF[case] = (probs, boxes, H, W, ref, nmax)
+    return _STITCH_REF[case]
+
+
+@pytest.mark.parametrize("name", PATH_CASES)
+def test_stitch_maps_identity_on_the_recompute_list_and_overflow_paths(name):
+    probs, boxes, H, W, _ = _path_case(name)
+    pal = torch.randint(0, 256, (256, 3), generator=torch.Generator().manual_seed(5), dtype=torch.uint8).cuda()
+    _stitch_both(probs, boxes, H, W, min_conf=0.3, pal=pal)
+
+
+@pytest.mark.parametrize("case", [SR.STITCH_CASES[0], SR.STITCH_CASES[2], SR.STITCH_CASES[3], *PATH_CASES])
+def test_stitch_maps_classes_against_float64(case):
+    """every class of dense_stitch_maps against stitch_ref's "up" within CONF_TOL + (nmax - 1) 2^-24 (test_dense_stitch_gpu.py's
+    _tol, nmax the reference's largest cover); cover exactly"""
+    probs, boxes, H, W, ref, nmax = _stitch_reference(case)
+    C = probs.shape[1]
+    mbuf, maps = _guarded((C, H, W), torch.float32, -7.0)
+    vbuf, cover = _guarded((H, W), torch.uint8, 77)
+    _ops().dense_stitch_maps(probs.cuda(), _boxes(boxes), H, W, maps, cover=cover)
+    torch.cuda.synchronize()
+    assert _intact(mbuf, -7.0) and _intact(vbuf, 77)
+    tol = R.CONF_TOL + (nmax - 1) * 2.0 ** -24
+    err = (maps.double().cpu() - ref["up"]).abs().amax(dim=(1, 2))
+    print(f"dense_stitch_maps {case}: cover up to {nmax}, max |du_c| per class {[f'{e:.2e}' for e in err.tolist()]} (bound {tol:.2e})")
+    assert torch.equal(cover.cpu().long(), ref["cover"].clamp_max(255))
+    assert float(err.max()) <= tol
 
 
 def test_stitch_maps_with_hanging_boxes_and_an_uncovered_strip():
