@@ -2249,6 +2249,46 @@ def component_stats(labels: torch.Tensor, root: torch.Tensor, ids: torch.Tensor,
                                     _p(image), _p(first), _p(area), _p(box), _p(qsum), _stream()), "cclip_component_stats")
 
 
+AGREEMENT_MAX_BAND = 32
+AGREEMENT_HIST_CELLS = 2048     # confusion cells a tile gathers in LDS: n_classes (n_classes + 1) above it takes the wave-combine path
+
+
+def label_agreement(pred: torch.Tensor, gt: torch.Tensor, n_classes: int, band: int, confusion: torch.Tensor, bad: torch.Tensor,
+                    bands: Optional[torch.Tensor] = None, per_image: bool = False, accumulate: bool = False) -> None:
+    """The integer counts behind mean IoU and boundary IoU (include/cclip_hip.h, cclip_label_agreement): pred, gt uint8 [B, H, W]
+    -> confusion int64 [R, C, C + 1] (gt class by pred class, "none" = 255 in the last column; gt == 255 is ignored), bad int64
+    [R, 2] (labels in [C, 254] in gt / in pred) and, with band = d > 0, bands int64 [R, C, 3] = (|G_c|, |P_c|, |G_c n P_c|) of the
+    band of half-width d (None when band == 0).  R = B with per_image, else 1.  accumulate adds to what the outputs hold.
+    Contiguous cuda tensors on one device; no CPU path.  Two calls give equal bytes."""
+    fname = "label_agreement"
+    _cuda_operands(fname, [(pred, "pred", torch.uint8), (gt, "gt", torch.uint8)], pred)
+    if pred.dim() != 3 or min(pred.shape) < 1:
+        raise ValueError(f"{fname}: pred must be [B, H, W] with no empty dimension, got {tuple(pred.shape)}")
+    B, H, W = pred.shape
+    if tuple(gt.shape) != (B, H, W):
+        raise ValueError(f"{fname}: gt must be {[B, H, W]}, got {tuple(gt.shape)}")
+    if H > OVERLAY_MAX_SIDE or W > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: height {H}, width {W}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    if B * H * W > _INT32_MAX:
+        raise ValueError(f"{fname}: pred holds {B * H * W} pixels; at most 2^31 - 1")
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= n_classes <= DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: n_classes must be an integer in [1, {DENSE_MAX_CLASSES}] (label 255 means none), got {n_classes!r}")
+    if isinstance(band, bool) or int(band) != band or not 0 <= band <= AGREEMENT_MAX_BAND:
+        raise ValueError(f"{fname}: band must be an integer in [0, {AGREEMENT_MAX_BAND}], got {band!r}")
+    C, d, R = int(n_classes), int(band), (B if per_image else 1)
+    if (d > 0) != (bands is not None):
+        raise ValueError(f"{fname}: bands goes with band > 0; got band {d} and bands {'given' if bands is not None else 'missing'}")
+    outs = [(confusion, "confusion", (R, C, C + 1)), (bad, "bad", (R, 2))] + ([(bands, "bands", (R, C, 3))] if bands is not None else [])
+    _cuda_operands(fname, [(pred, "pred", torch.uint8)] + [(t, name, torch.int64) for t, name, _ in outs], pred)
+    for t, name, want in outs:
+        if tuple(t.shape) != want:
+            raise ValueError(f"{fname}: {name} must be {list(want)}, got {tuple(t.shape)}")
+        if t.data_ptr() % 8:
+            raise ValueError(f"{fname}: {name} must start on an 8-byte boundary")
+    check(lib.cclip_label_agreement(_p(pred), _p(gt), c_int(B), c_int(H), c_int(W), c_int(C), c_int(d), c_int(int(bool(per_image))),
+                                    c_int(int(bool(accumulate))), _p(confusion), _p(bad), _p(bands), _stream()), "cclip_label_agreement")
+
+
 # --------------------------------------------------------------------------------------------
 # fp8 (e4m3) inference projections
 # --------------------------------------------------------------------------------------------

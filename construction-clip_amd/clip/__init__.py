@@ -27,4 +27,5 @@ from .dense import segment, dense_features, DenseResult, default_palette  # noqa
 from .dense import segment_photo, plan_windows, PhotoDenseResult, label_boxes  # noqa: F401  (whole photos: sliding windows stitched in one launch)
 from .dense import label_components, ComponentsResult  # noqa: F401  (instances: connected components of a label map, on the device)
 from .dense import refine_maps, RefinedDenseResult  # noqa: F401  (boundaries: image-guided refinement of the class maps, PAMR)
+from .dense import evaluate_labels, SegmentationScores  # noqa: F401  (evaluation: mean IoU and boundary IoU against ground-truth masks)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

@@ -28,6 +28,7 @@ whose weights come from the photo's own colours (csrc/dense_refine.hip).  No tra
 from __future__ import annotations
 
 import colorsys
+import math
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple, Union
 
@@ -99,6 +100,16 @@ class _LabelledResult:
         """one record per connected component: components(connectivity).instances(...) with this result's class names"""
         return self.components(connectivity).instances(min_area=min_area, min_score=min_score, classes=classes,
                                                        class_names=self.class_names)
+
+    def evaluate(self, gt: torch.Tensor, *, band: Optional[int] = None, per_image: bool = False) -> "SegmentationScores":
+        """mean IoU and boundary IoU of these labels against a ground-truth mask of the same [H, W] (uint8, class indices, 255 =
+        ignore): `evaluate_labels` with this result's n_classes and class names"""
+        want = tuple(self.labels.shape)
+        got = tuple(getattr(gt, "shape", ()))
+        if got != want and not (len(want) == 3 and want[0] == 1 and got == want[1:]):
+            raise ValueError(f"evaluate: gt must have the labels' shape {list(want)}, got {list(got)}")
+        return evaluate_labels(self.labels, gt.reshape(want), self.n_classes, band=band, per_image=per_image,
+                               class_names=self.class_names)
 
 
 @dataclass
@@ -596,3 +607,227 @@ def segment_photo(model, image, classes: Union[torch.Tensor, Sequence[str]], *, 
     ops.dense_stitch(probs, _device_boxes(boxes, dev), H, W, labels, conf, min_conf=min_conf, cover=cover)
     return PhotoDenseResult(probs=probs, boxes=torch.from_numpy(boxes), labels=labels, conf=conf, cover=cover, class_names=names,
                             min_conf=float(min_conf))
+
+
+# ---- evaluation: mean IoU and boundary IoU against ground-truth masks --------------------------------
+def _mean_defined(values) -> float:
+    """the mean of the values that are not NaN (math.fsum: the exactly rounded sum, whatever the order); NaN over none"""
+    keep = [float(v) for v in values if v == v]
+    return math.fsum(keep) / len(keep) if keep else float("nan")
+
+
+def _ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """num / den in float64, NaN where den == 0 (integer tensors in)"""
+    out = torch.full(num.shape, float("nan"), dtype=torch.float64)
+    ok = den != 0
+    out[ok] = num[ok].double() / den[ok].double()
+    return out
+
+
+class SegmentationScores:
+    """The scores of label maps against ground truth, from integer counts (`evaluate_labels`; or from count tensors directly).
+
+    confusion: int64 [C, C + 1], or [B, C, C + 1] per image: confusion[g, p] pixels of ground-truth class g labelled p; the last
+    column is "none" (255) and counts against the ground-truth class (a false negative of g, a false positive of nobody).
+    bands: None, or int64 [C, 3] / [B, C, 3] = (|G_c|, |P_c|, |G_c n P_c|) of the boundary band of half-width `band` pixels.
+    All arithmetic is float64 on the host.  A class with an empty union has IoU NaN and is left out of the means; a mean over
+    no class is NaN.  Without bands the boundary scores are None.  a + b and a += b add the counts (dataset-level scores over
+    photos of any sizes); both must agree on C, band and shape."""
+
+    def __init__(self, confusion: torch.Tensor, bands: Optional[torch.Tensor] = None, band: int = 0,
+                 class_names: Optional[Sequence[str]] = None):
+        confusion = torch.as_tensor(confusion)
+        if confusion.dtype != torch.int64 or confusion.dim() not in (2, 3) or confusion.shape[-1] != confusion.shape[-2] + 1:
+            raise ValueError(f"SegmentationScores: confusion must be int64 [C, C + 1] or [B, C, C + 1], got {confusion.dtype} "
+                             f"{tuple(confusion.shape)}")
+        C = confusion.shape[-2]
+        if bands is not None:
+            bands = torch.as_tensor(bands)
+            if bands.dtype != torch.int64 or tuple(bands.shape) != (*confusion.shape[:-2], C, 3):
+                raise ValueError(f"SegmentationScores: bands must be int64 {[*confusion.shape[:-2], C, 3]}, got {bands.dtype} "
+                                 f"{tuple(bands.shape)}")
+        if isinstance(band, bool) or int(band) != band or band < 0 or (band > 0) != (bands is not None):
+            raise ValueError(f"SegmentationScores: band must be a positive integer with bands and 0 without, got {band!r}")
+        if class_names is not None and len(class_names) != C:
+            raise ValueError(f"SegmentationScores: {len(class_names)} class names for {C} classes")
+        self.confusion = confusion.detach().cpu().clone()
+        self.bands = None if bands is None else bands.detach().cpu().clone()
+        self.band = int(band)
+        self.class_names = None if class_names is None else [str(n) for n in class_names]
+
+    # -- counts ----
+    @property
+    def n_classes(self) -> int:
+        return self.confusion.shape[-2]
+
+    @property
+    def per_image(self) -> bool:
+        return self.confusion.dim() == 3
+
+    def _tp(self):
+        return torch.diagonal(self.confusion[..., :, :-1], dim1=-2, dim2=-1)
+
+    def _gt(self):
+        return self.confusion.sum(dim=-1)                                       # "none" included
+
+    def _pred(self):
+        return self.confusion[..., :, :-1].sum(dim=-2)
+
+    def _rows(self, per_class: torch.Tensor, fn):
+        """fn over the class vector of every image ([B] of floats), or of the one result (a float)"""
+        if self.per_image:
+            return torch.tensor([fn(r) for r in per_class], dtype=torch.float64)
+        return fn(per_class)
+
+    # -- scores ----
+    @property
+    def iou(self) -> torch.Tensor:
+        tp = self._tp()
+        return _ratio(tp, self._gt() + self._pred() - tp)
+
+    @property
+    def miou(self):
+        return self._rows(self.iou, _mean_defined)
+
+    @property
+    def class_accuracy(self) -> torch.Tensor:
+        return _ratio(self._tp(), self._gt())
+
+    @property
+    def precision(self) -> torch.Tensor:
+        return _ratio(self._tp(), self._pred())
+
+    @property
+    def pixel_accuracy(self):
+        r = _ratio(self._tp().sum(dim=-1), self.confusion.sum(dim=(-2, -1)))
+        return r if self.per_image else float(r)
+
+    @property
+    def none_fraction(self):
+        r = _ratio(self.confusion[..., -1].sum(dim=-1), self.confusion.sum(dim=(-2, -1)))
+        return r if self.per_image else float(r)
+
+    @property
+    def fw_iou(self):
+        """the IoUs weighted by each class's share of the ground-truth pixels (classes without ground truth carry no weight)"""
+        gt, iou = self._gt().double(), self.iou
+
+        def one(i):
+            g, u = (gt, iou) if i is None else (gt[i], iou[i])
+            total = float(g.sum())
+            if total == 0:
+                return float("nan")
+            return math.fsum(float(a) * float(b) for a, b in zip(g, u) if a > 0) / total
+        if self.per_image:
+            return torch.tensor([one(i) for i in range(gt.shape[0])], dtype=torch.float64)
+        return one(None)
+
+    @property
+    def boundary_iou(self) -> Optional[torch.Tensor]:
+        if self.bands is None:
+            return None
+        g, p, i = self.bands[..., 0], self.bands[..., 1], self.bands[..., 2]
+        return _ratio(i, g + p - i)
+
+    @property
+    def mean_boundary_iou(self):
+        return None if self.bands is None else self._rows(self.boundary_iou, _mean_defined)
+
+    # -- sums ----
+    def _check_same(self, other) -> None:
+        if not isinstance(other, SegmentationScores):
+            raise TypeError(f"SegmentationScores: cannot add {type(other).__name__}")
+        if other.n_classes != self.n_classes:
+            raise ValueError(f"SegmentationScores: {self.n_classes} classes against {other.n_classes}")
+        if other.band != self.band:
+            raise ValueError(f"SegmentationScores: band {self.band} against band {other.band}")
+        if other.confusion.shape != self.confusion.shape:
+            raise ValueError(f"SegmentationScores: counts {tuple(self.confusion.shape)} against {tuple(other.confusion.shape)} "
+                             f"(take .total() of per-image results first)")
+
+    def __add__(self, other) -> "SegmentationScores":
+        self._check_same(other)
+        return SegmentationScores(self.confusion + other.confusion, None if self.bands is None else self.bands + other.bands,
+                                  self.band, self.class_names if self.class_names is not None else other.class_names)
+
+    def __iadd__(self, other) -> "SegmentationScores":
+        self._check_same(other)
+        self.confusion += other.confusion
+        if self.bands is not None:
+            self.bands += other.bands
+        if self.class_names is None:
+            self.class_names = other.class_names
+        return self
+
+    def total(self) -> "SegmentationScores":
+        """the counts summed over the images of a per-image result (a pooled result is returned as a copy)"""
+        if not self.per_image:
+            return SegmentationScores(self.confusion, self.bands, self.band, self.class_names)
+        return SegmentationScores(self.confusion.sum(dim=0), None if self.bands is None else self.bands.sum(dim=0), self.band,
+                                  self.class_names)
+
+    def as_dict(self) -> dict:
+        """plain floats and lists, ready for json.dumps: NaN (nothing to score) becomes None"""
+        def plain(v):
+            if v is None:
+                return None
+            if isinstance(v, torch.Tensor):
+                return [plain(x) for x in v.tolist()] if v.dim() else plain(v.item())
+            if isinstance(v, list):
+                return [plain(x) for x in v]
+            return None if v != v else float(v)
+        out = {"n_classes": self.n_classes, "band": self.band, "class_names": self.class_names,
+               "pixels": self.confusion.sum(dim=(-2, -1)).tolist()}
+        for k in ("miou", "pixel_accuracy", "fw_iou", "none_fraction", "mean_boundary_iou", "iou", "class_accuracy", "precision",
+                  "boundary_iou"):
+            out[k] = plain(getattr(self, k))
+        return out
+
+
+def default_band(height: int, width: int) -> int:
+    """the band half-width of Boundary IoU's 2 % of the image diagonal: round(0.02 sqrt(H^2 + W^2)) clipped to [1, 32]"""
+    return max(1, min(ops.AGREEMENT_MAX_BAND, int(round(0.02 * math.sqrt(height * height + width * width)))))
+
+
+def evaluate_labels(pred: torch.Tensor, gt: torch.Tensor, n_classes: int, *, band: Optional[int] = None, per_image: bool = False,
+                    class_names: Optional[Sequence[str]] = None) -> SegmentationScores:
+    """Score label maps against ground truth on the device (csrc/label_agreement.hip): pred and gt uint8 [H, W] or [B, H, W] of
+    equal shape, class indices below n_classes; 255 in gt = ignore the pixel, 255 in pred = "none" (counts against the
+    ground-truth class).  band: the half-width in pixels of the boundary band of Boundary IoU (Cheng et al., CVPR 2021), 1 .. 32;
+    None = `default_band` (2 % of the diagonal, capped), kept on the result; 0 skips the boundary scores.  per_image: one row of
+    counts per image instead of one for the batch.  A label in [n_classes, 254] in either map is a ValueError that says in
+    which map and how many pixels.  One ops.label_agreement launch and one device -> host read of the counts.  HIP only."""
+    fname = "evaluate_labels"
+    for t, name in ((pred, "pred"), (gt, "gt")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{fname}: {name} must be a cuda tensor, got {getattr(t, 'device', type(t))} (no CPU path)")
+        if t.dtype != torch.uint8:
+            raise ValueError(f"{fname}: {name} must be torch.uint8, got {t.dtype}")
+    if pred.dim() not in (2, 3) or min(pred.shape) < 1:
+        raise ValueError(f"{fname}: pred must be [H, W] or [B, H, W] with no empty dimension, got {tuple(pred.shape)}")
+    if tuple(gt.shape) != tuple(pred.shape):
+        raise ValueError(f"{fname}: gt must have pred's shape {list(pred.shape)}, got {list(gt.shape)}")
+    H, W = pred.shape[-2:]
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= n_classes <= NONE_LABEL:
+        raise ValueError(f"{fname}: n_classes must be an integer in [1, {NONE_LABEL}] (label 255 means none), got {n_classes!r}")
+    d = default_band(H, W) if band is None else band
+    if isinstance(d, bool) or int(d) != d or not 0 <= d <= ops.AGREEMENT_MAX_BAND:
+        raise ValueError(f"{fname}: band must be None or an integer in [0, {ops.AGREEMENT_MAX_BAND}], got {band!r}")
+    C, d = int(n_classes), int(d)
+    if class_names is not None and len(class_names) != C:
+        raise ValueError(f"{fname}: {len(class_names)} class names for {C} classes")
+    p3, g3 = pred.reshape(-1, H, W).contiguous(), gt.reshape(-1, H, W).to(pred.device).contiguous()
+    B, dev = p3.shape[0], pred.device
+    R = B if per_image else 1
+    confusion = torch.empty(R, C, C + 1, device=dev, dtype=torch.int64)
+    bad = torch.empty(R, 2, device=dev, dtype=torch.int64)
+    bands = torch.empty(R, C, 3, device=dev, dtype=torch.int64) if d > 0 else None
+    ops.label_agreement(p3, g3, C, d, confusion, bad, bands, per_image=per_image)
+    nbad = bad.cpu().sum(dim=0).tolist()                                               # the one read; the counts follow it
+    if nbad[0] or nbad[1]:
+        what = [f"{n} pixels of {name} hold a label in [{C}, 254]" for n, name in zip(nbad, ("gt", "pred")) if n]
+        raise ValueError(f"{fname}: {' and '.join(what)} (n_classes = {C}; 255 = ignore in gt, none in pred)")
+    conf_c, bands_c = confusion.cpu(), None if bands is None else bands.cpu()
+    if not per_image:
+        conf_c, bands_c = conf_c[0], None if bands_c is None else bands_c[0]
+    return SegmentationScores(conf_c, bands_c, int(d), class_names)

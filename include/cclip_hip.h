@@ -1273,6 +1273,32 @@ int cclip_component_stats(const uint8_t* labels, const float* conf, const int32_
                           int32_t W, int32_t n, uint8_t* label, int32_t* image, int32_t* first, int32_t* area, int32_t* box,
                           uint64_t* qsum, hipStream_t stream);
 
+/* cclip_label_agreement (csrc/label_agreement.hip): how well pred agrees with gt, both uint8 [B][H][W], as the integer counts
+ *   behind mean IoU and boundary IoU (Cheng et al., CVPR 2021; stated from the paper, no bit-level agreement with another
+ *   implementation is claimed).  C classes, R = per_image ? B : 1 rows of results (row b of image b, or one row for the batch).
+ *     confusion [R][C][C+1] int64: confusion[r][g][p] = pixels with gt == g < C and pred == p < C; column C counts pred == 255
+ *                                  ("none").  Pixels with gt == 255 are ignored everywhere.
+ *     bad       [R][2]      int64: pixels with gt in [C, 254]; pixels with gt < C and pred in [C, 254].  Such pixels enter no
+ *                                  other count.
+ *     bands     [R][C][3]   int64: (|G_c|, |P_c|, |G_c n P_c|) for the band half-width d = band; required when d > 0, NULL when
+ *                                  d == 0.
+ *   Band: pixel p is in the band of a map m when some q with |q_x - p_x| <= d and |q_y - p_y| <= d lies outside the image or
+ *   has m[q] != m[p], compared as raw bytes (255 and out-of-range values are values like any other).  Nothing crosses between
+ *   the images of a batch, nothing wraps from the end of a row to the start of the next.  G_c = pixels with gt == c in gt's
+ *   band; P_c = pixels with pred == c and gt < C in pred's band; ignored and bad pixels are in neither.
+ *   accumulate == 0 sets the outputs, accumulate == 1 adds the counts to what they hold (a device-side sum over a dataset).
+ *   Integer sums by 32-bit LDS and 64-bit global atomics: two calls give equal bytes.  No kernel waits for another work-group.
+ *   CCLIP_ERR_ARG, nothing launched, nothing written: pred, gt, confusion or bad NULL; C outside [1, 255]; band outside
+ *   [0, CCLIP_AGREEMENT_MAX_BAND]; bands given with band == 0 or missing with band > 0; per_image or accumulate other than 0 or
+ *   1; B < 1; H or W outside [1, CCLIP_OVERLAY_MAX_SIDE]; B H W > 2^31 - 1 (formed in 64 bits); confusion, bad or bands not
+ *   8-byte aligned; an output that overlaps another output or an input.  pred and gt may have any alignment.
+ *   While C (C + 1) <= CCLIP_AGREEMENT_HIST_CELLS (C <= 44) the confusion counts of a tile are gathered in LDS. */
+#define CCLIP_AGREEMENT_MAX_BAND 32
+#define CCLIP_AGREEMENT_HIST_CELLS 2048
+int cclip_label_agreement(const uint8_t* pred, const uint8_t* gt, int32_t B, int32_t H, int32_t W, int32_t C, int32_t band,
+                          int32_t per_image, int32_t accumulate, int64_t* confusion, int64_t* bad, int64_t* bands,
+                          hipStream_t stream);
+
 /* ---- CLIP-guided caption selection ---------------------------------------------------------------
  * K candidate captions for each of N images, scored against the image (CLIPScore, Hessel et al. 2021), optionally against the
  * image's reference captions (RefCLIPScore), and ranked - one launch, one work-group per image (csrc/caption_select.hip).
