@@ -2289,6 +2289,82 @@ def label_agreement(pred: torch.Tensor, gt: torch.Tensor, n_classes: int, band: 
                                     c_int(int(bool(accumulate))), _p(confusion), _p(bad), _p(bands), _stream()), "cclip_label_agreement")
 
 
+PROTOTYPES_SLAB = 64            # cells of one partial sum: the split of the K g g cells is a function of K and g alone
+
+
+def dense_prototypes_workspace(K: int, grid: int, n_classes: int, embed_dim: int) -> int:
+    """Bytes of scratch ops.dense_prototypes needs (the header's closed form, restated): per slab of PROTOTYPES_SLAB cells and per
+    class, embed_dim partial sums, one weight and one patch count."""
+    return -(-(K * grid * grid) // PROTOTYPES_SLAB) * n_classes * (embed_dim + 2) * 4
+
+
+def dense_prototypes(feat: torch.Tensor, masks: torch.Tensor, boxes: torch.Tensor, grid: int, n_classes: int, min_share8: int,
+                     sums: torch.Tensor, weight: torch.Tensor, patches: torch.Tensor, pixels: torch.Tensor, bad: torch.Tensor, *,
+                     image: Optional[torch.Tensor] = None, accumulate: bool = False, workspace: Optional[torch.Tensor] = None) -> None:
+    """Masked average pooling of per-patch features into class prototypes (include/cclip_hip.h, cclip_dense_prototypes): feat fp32
+    [K * grid * grid, E] (rows may be strided; encode_image_dense viewed flat), masks uint8 [B, H, W] (class index < n_classes,
+    255 = ignore), boxes int32 [K, 4] = (x0, y0, x1, y1) of window k in picture image[k] (int32 [K]; None: picture 0) -> sums fp32
+    [C, E] = sum of w * unit feature over the cells whose share of class c is at least min_share8 / 256 (w = that share), weight
+    fp32 [C], patches int64 [C], pixels int64 [C] and bad int64 [1] (mask values in [C, 254]).  accumulate adds to what the outputs
+    hold.  The boxes are NOT read back: an empty, inverted or oversized box or an image index outside [0, B) contributes nothing.
+    workspace: 16-byte aligned uint8 / fp32 scratch of dense_prototypes_workspace(K, grid, C, E) bytes, allocated when None.
+    cuda tensors on one device; no CPU path.  Two calls give equal bytes."""
+    fname = "dense_prototypes"
+    tensors = [(feat, "feat", torch.float32), (masks, "masks", torch.uint8), (boxes, "boxes", torch.int32), (sums, "sums", torch.float32),
+               (weight, "weight", torch.float32), (patches, "patches", torch.int64), (pixels, "pixels", torch.int64), (bad, "bad", torch.int64)]
+    if image is not None:
+        tensors.append((image, "image", torch.int32))
+    _cuda_operands(fname, tensors, feat, strided=("feat",))
+    if isinstance(grid, bool) or int(grid) != grid or not 1 <= grid <= OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: grid must be an integer in [1, {OVERLAY_MAX_SIDE}], got {grid!r}")
+    if isinstance(n_classes, bool) or int(n_classes) != n_classes or not 1 <= n_classes <= DENSE_MAX_CLASSES:
+        raise ValueError(f"{fname}: n_classes must be an integer in [1, {DENSE_MAX_CLASSES}] (label 255 means ignore), got {n_classes!r}")
+    if isinstance(min_share8, bool) or int(min_share8) != min_share8 or not 0 <= min_share8 <= 256:
+        raise ValueError(f"{fname}: min_share8 must be an integer in [0, 256], got {min_share8!r}")
+    g, C = int(grid), int(n_classes)
+    M, E = feat.shape
+    if E < 4 or E % 4 or E > DENSE_MAX_EMBED:
+        raise ValueError(f"{fname}: feat has embedding width {E}; it must be a multiple of 4 in [4, {DENSE_MAX_EMBED}]")
+    if M < 1 or M % (g * g) or M // (g * g) > DENSE_MAX_WINDOWS:
+        raise ValueError(f"{fname}: feat has {M} rows; it must hold between 1 and {DENSE_MAX_WINDOWS} windows of grid * grid = {g * g} rows")
+    K = M // (g * g)
+    if M > 1 and (feat.stride(0) < E or feat.stride(0) % 4):
+        raise ValueError(f"{fname}: feat must have a row stride >= {E} that is a multiple of 4, got {feat.stride(0)}")
+    if feat.data_ptr() % 16:
+        raise ValueError(f"{fname}: feat must start on a 16-byte boundary")
+    if masks.dim() != 3 or min(masks.shape) < 1:
+        raise ValueError(f"{fname}: masks must be [B, H, W] with no empty dimension, got {tuple(masks.shape)}")
+    B, H, W = masks.shape
+    if H > OVERLAY_MAX_SIDE or W > OVERLAY_MAX_SIDE:
+        raise ValueError(f"{fname}: height {H}, width {W}: each must lie in [1, {OVERLAY_MAX_SIDE}]")
+    if B * H * W > _INT32_MAX:
+        raise ValueError(f"{fname}: masks holds {B * H * W} pixels; at most 2^31 - 1")
+    if tuple(boxes.shape) != (K, 4):
+        raise ValueError(f"{fname}: boxes must be [{K}, 4] as (x0, y0, x1, y1), got {tuple(boxes.shape)}")
+    if image is not None and tuple(image.shape) != (K,):
+        raise ValueError(f"{fname}: image must be [{K}], got {tuple(image.shape)}")
+    for t, name, want, align in ((sums, "sums", (C, E), 4), (weight, "weight", (C,), 4), (patches, "patches", (C,), 8),
+                                 (pixels, "pixels", (C,), 8), (bad, "bad", (1,), 8)):
+        if tuple(t.shape) != want:
+            raise ValueError(f"{fname}: {name} must be {list(want)}, got {tuple(t.shape)}")
+        if t.data_ptr() % align:
+            raise ValueError(f"{fname}: {name} must start on a {align}-byte boundary")
+    need = dense_prototypes_workspace(K, g, C, E)
+    if workspace is None:
+        workspace = torch.empty(need, device=feat.device, dtype=torch.uint8)
+    else:
+        if not isinstance(workspace, torch.Tensor) or workspace.device != feat.device or not workspace.is_contiguous():
+            raise ValueError(f"{fname}: workspace must be a contiguous cuda tensor on {feat.device}, got {getattr(workspace, 'device', type(workspace))}")
+        if workspace.dtype not in (torch.uint8, torch.float32) or workspace.numel() * workspace.element_size() < need or workspace.data_ptr() % 16:
+            raise ValueError(f"{fname}: workspace must be a uint8 or float32 tensor of at least {need} bytes on a 16-byte boundary, got "
+                             f"{workspace.dtype}, {workspace.numel() * workspace.element_size()} bytes, address % 16 = {workspace.data_ptr() % 16}")
+    ldf = feat.stride(0) if M > 1 else E
+    check(lib.cclip_dense_prototypes(_p(feat), c_long(ldf), _p(masks), _p(boxes), _p(image), c_int(K), c_int(g), c_int(C), c_int(E),
+                                     c_int(B), c_int(H), c_int(W), c_int(int(min_share8)), c_int(int(bool(accumulate))), _p(sums),
+                                     _p(weight), _p(patches), _p(pixels), _p(bad), _p(workspace),
+                                     c_long(workspace.numel() * workspace.element_size()), _stream()), "cclip_dense_prototypes")
+
+
 # --------------------------------------------------------------------------------------------
 # fp8 (e4m3) inference projections
 # --------------------------------------------------------------------------------------------

@@ -28,4 +28,5 @@ from .dense import segment_photo, plan_windows, PhotoDenseResult, label_boxes  #
 from .dense import label_components, ComponentsResult  # noqa: F401  (instances: connected components of a label map, on the device)
 from .dense import refine_maps, RefinedDenseResult  # noqa: F401  (boundaries: image-guided refinement of the class maps, PAMR)
 from .dense import evaluate_labels, SegmentationScores  # noqa: F401  (evaluation: mean IoU and boundary IoU against ground-truth masks)
+from .dense_fewshot import DensePrototypes  # noqa: F401  (few-shot dense maps: class prototypes pooled under annotated masks)
 from .score import ClipScores, clip_score, clip_score_features  # noqa: F401  (CLIPScore / RefCLIPScore, best-of-K caption selection)

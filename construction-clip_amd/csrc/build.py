@@ -31,7 +31,7 @@ def _deps_mtime():
 
 # translation units that touch 16-bit operands are built twice: bf16 (default) and IEEE fp16 (-DCCLIP_F16); every other .hip in
 # this directory (capi, gemm_f32, preprocess, transpose16, caption_prompt, class_loss, sigmoid_loss, sample_rows, preprocess_rois,
-# relevance_overlay, caption_select, distill_loss, dense_classes, dense_stitch, dense_refine, label_components, label_agreement) is built once
+# relevance_overlay, caption_select, distill_loss, dense_classes, dense_stitch, dense_refine, label_components, label_agreement, dense_prototypes) is built once
 DUAL = ("gemm_bf16", "attention", "layernorm", "embed", "loss", "optim", "decode", "lm_score", "coreset", "mst", "concept_codes",
         "gauss_scores")   # "attention" also matches attention_small, "embed" embed_moments
 

@@ -1299,6 +1299,49 @@ int cclip_label_agreement(const uint8_t* pred, const uint8_t* gt, int32_t B, int
                           int32_t per_image, int32_t accumulate, int64_t* confusion, int64_t* bad, int64_t* bands,
                           hipStream_t stream);
 
+/* cclip_dense_prototypes (csrc/dense_prototypes.hip): few-shot class prototypes for the dense path by masked average pooling.
+ *   The per-patch features of K windows are pooled under annotated masks into one weighted sum per class; fp32, no fp16 twin.
+ *     feat   fp32 [K g g][E], row stride ldf (floats): window k owns rows k g g .. k g g + g g - 1, row i g + j is cell (row i,
+ *            column j) - encode_image_dense viewed flat, as cclip_dense_class_probs takes it
+ *     masks  uint8 [B][H][W]: class indices < C; 255 = ignore; values in [C, 254] are "bad"
+ *     boxes  int32 [K][4] = (x0, y0, x1, y1), on the device;  image int32 [K] on the device, or NULL = every window is of image 0
+ *   Window validity: 1 <= x1 - x0 <= CCLIP_OVERLAY_MAX_SIDE and 1 <= y1 - y0 <= CCLIP_OVERLAY_MAX_SIDE, the sides formed without
+ *     32-bit overflow, and 0 <= image[k] < B.  Any other window contributes nothing; a box may hang over the picture's edge.  The
+ *     launcher cannot see boxes or image: for ANY values in them the kernel reads nothing outside its inputs and writes nothing
+ *     outside its outputs and workspace.
+ *   Cells: pixel (x, y) of a valid window lies in cell column j = ((2 (x - x0) + 1) g) / (2 (x1 - x0)) and row i likewise from y
+ *     (integer division, the pixel-centre rule, consistent with the align_corners=False geometry of cclip_dense_stitch).
+ *     area(k,i,j) = the box pixels in the cell, inside the picture or not; count_c(k,i,j) = those of them inside the picture with
+ *     mask == c < C.  A side shorter than g leaves cells with area == 0, which contribute nothing.
+ *   Contribution: a cell contributes to class c when count_c > 0 and 256 count_c >= min_share8 area (64-bit products; min_share8 in
+ *     [0, 256], the a8 idiom: 256 = only cells wholly of one class, 0 = any overlap), with weight w = (float)count_c / (float)area,
+ *     one fp32 division.  f^_p = feat_p / |feat_p|, the zero vector when the norm is 0 (no epsilon, cclip_dense_class_probs's
+ *     rule; the cell still counts in patches).
+ *   Outputs - accumulate == 0 sets them, accumulate == 1 adds to what they hold (one fp32 add per float element, integer adds):
+ *     sums    fp32  [C][E] = the sum over contributing cells of w f^        weight  fp32 [C] = the sum of w
+ *     patches int64 [C]    = the number of contributing cells
+ *     pixels  int64 [C]    = the sum of count_c over ALL cells of all valid windows (a pixel under two windows counts twice;
+ *                            cells below the threshold count as well)
+ *     bad     int64 [1]    = pixels inside the picture and inside a valid window with a mask value in [C, 254]
+ *     A class that nothing contributes to gets sums exactly 0, weight 0 and patches 0.
+ *   Determinism: the K g g cells are cut into slabs of CCLIP_PROTOTYPES_SLAB consecutive cells, a function of K and g alone; one
+ *     work-group walks a slab in ascending cell order into its own partial, a second kernel adds the slabs in ascending order.
+ *     No float atomics (integer atomics for the counts), nothing depends on the device or the launch geometry: two calls give
+ *     equal bytes.
+ *   workspace: 16-byte aligned, at least cclip_dense_prototypes_workspace(K, g, C, E) bytes =
+ *     ceil(K g g / CCLIP_PROTOTYPES_SLAB) * C * (E + 2) * 4   (per slab and class: E partial sums, a weight, a patch count).
+ *   CCLIP_ERR_ARG, nothing launched, nothing written: a NULL pointer other than image; K outside [1, 65535]; C outside [1, 255];
+ *   g, H or W outside [1, CCLIP_OVERLAY_MAX_SIDE]; B < 1; B H W > 2^31 - 1 (formed in 64 bits); E outside [4, 1024] or not a
+ *   multiple of 4; ldf < E or not a multiple of 4; K g g ldf > 2^62 (row indices stay inside 64 bits); feat or workspace not 16-byte aligned; sums, weight, boxes or image not 4-byte
+ *   aligned; patches, pixels or bad not 8-byte aligned; min_share8 outside [0, 256]; accumulate other than 0 or 1; a workspace
+ *   that is too small; an output (the workspace is one) that overlaps another output or an input.  masks may have any alignment. */
+#define CCLIP_PROTOTYPES_SLAB 64
+int64_t cclip_dense_prototypes_workspace(int32_t K, int32_t g, int32_t C, int32_t E);
+int cclip_dense_prototypes(const float* feat, int64_t ldf, const uint8_t* masks, const int32_t* boxes, const int32_t* image,
+                           int32_t K, int32_t g, int32_t C, int32_t E, int32_t B, int32_t H, int32_t W, int32_t min_share8,
+                           int32_t accumulate, float* sums, float* weight, int64_t* patches, int64_t* pixels, int64_t* bad,
+                           void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- CLIP-guided caption selection ---------------------------------------------------------------
  * K candidate captions for each of N images, scored against the image (CLIPScore, Hessel et al. 2021), optionally against the
  * image's reference captions (RefCLIPScore), and ranked - one launch, one work-group per image (csrc/caption_select.hip).

@@ -7,7 +7,8 @@
 --mode / --window / --stride / --max-side / --min-conf); a mask whose size differs from the processed photo is resized with
 PIL NEAREST.  One JSON line per photo, then one summary line made from the SUMMED counts (dataset-level mIoU, the number
 MaskCLIP, SCLIP and ClearCLIP report).  With --refine (segment_images.py's --refine-iterations / --refine-dilations) every line
-carries the scores of the unrefined and of the refined maps: {"scores": ..., "refined": ...}.
+carries the scores of the unrefined and of the refined maps: {"scores": ..., "refined": ...}.  With --prototypes FILE (fit_prototypes.py)
+the class rows are the few-shot prototypes, blended with the prompts' embeddings by --text-weight.
 
     python scripts/eval_segmentation.py --images photos/ --masks masks/ --classes scaffold ground sky --checkpoint clip.pt
     python scripts/eval_segmentation.py --images photos/ --masks masks/ --classes scaffold ground sky --window 224 448 --refine
@@ -41,6 +42,8 @@ def build_parser():
     ap.add_argument("--refine", action="store_true", help="also score the maps after image-guided refinement (clip.refine_maps)")
     ap.add_argument("--refine-iterations", type=int, default=10, metavar="T", help="--refine: iterations, 1 .. 64")
     ap.add_argument("--refine-dilations", type=int, nargs="+", default=[1, 2, 4, 8, 12, 24], metavar="d", help="--refine: neighbour distances")
+    ap.add_argument("--prototypes", default=None, metavar="FILE", help="few-shot class prototypes of fit_prototypes.py: the classes are these rows, not the prompts alone")
+    ap.add_argument("--text-weight", type=float, default=0.0, help="--prototypes: weight of a class's text embedding in its row, 0 .. 1 (a class without support takes its text row)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=3, help="--synthetic: photos to score")
     return ap
@@ -101,6 +104,9 @@ def main(argv=None):
     model.eval()
     with torch.no_grad():
         text = model.encode_text(C.get_tokenize(model)(prompts).to(device)).float()
+    if args.prototypes:                                       # few-shot rows: the fitted prototypes, blended with the prompts' embeddings
+        from fit_prototypes import load_prototypes
+        text = load_prototypes(args.prototypes, len(prompts), model.geo.embed_dim, device).features(text, args.text_weight)
     windows = list(args.window) if args.window else [model.geo.image_resolution]
     window = windows if len(windows) > 1 else windows[0]
     stride = None if args.stride is None else ([args.stride] * len(windows) if len(windows) > 1 else args.stride)

@@ -56,6 +56,8 @@ def build_parser():
     ap.add_argument("--refine-iterations", type=int, default=10, metavar="T", help="--refine: iterations, 1 .. 64")
     ap.add_argument("--refine-dilations", type=int, nargs="+", default=[1, 2, 4, 8, 12, 24], metavar="d",
                     help="--refine: neighbour distances, 1 to 6 values in 1 .. 24")
+    ap.add_argument("--prototypes", default=None, metavar="FILE", help="few-shot class prototypes of fit_prototypes.py: the classes are these rows, not the prompts alone")
+    ap.add_argument("--text-weight", type=float, default=0.0, help="--prototypes: weight of a class's text embedding in its row, 0 .. 1 (a class without support takes its text row)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--n_images", type=int, default=3, help="--synthetic: images to segment")
     return ap
@@ -146,6 +148,9 @@ def main(argv=None):
     prompts = class_prompts(args)
     with torch.no_grad():
         text = model.encode_text(C.get_tokenize(model)(prompts).to(device)).float()      # once for every image
+    if args.prototypes:                                       # few-shot rows: the fitted prototypes, blended with the prompts' embeddings
+        from fit_prototypes import load_prototypes
+        text = load_prototypes(args.prototypes, len(prompts), model.geo.embed_dim, device).features(text, args.text_weight)
     S = args.size or model.geo.image_resolution
     if args.png:
         os.makedirs(args.png, exist_ok=True)
